@@ -711,6 +711,22 @@ def _kernel_row(d, steps, ms_per_step, traffic=None):
     return row
 
 
+DUMP_MAX_BYTES = 64 << 20           # --dump-outputs: all arrays of one run together
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs DIR: every array as DIR/<name>.npy in float32.  The byte budget is split evenly over the arrays;
+    an array larger than its share is written as a fixed sample of its flattened elements (the same seeded index set
+    for the same size, so two builds' files compare element for element)."""
+    os.makedirs(dirname, exist_ok=True)
+    cap = DUMP_MAX_BYTES // 4 // len(arrays)
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.size > cap:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, cap, replace=False))]
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def _shared_gpu_debug():
     """PCOPS_BENCH_SHARED_GPU=1: every rank on cuda:0 over gloo -- exercises the N > 1 control flow (barriers, gathers,
     the two measurement passes) on a one-GPU box.  The line is tagged `shared_gpu_debug`; its value means nothing."""
@@ -755,6 +771,10 @@ def main():
     ap.add_argument("--sync_bn", action="store_true", help="all-reduce the BN batch statistics over the ranks")
     ap.add_argument("--deterministic", action="store_true",
                     help="bit-reproducible backward passes (pcops_set_deterministic); reported in config, not the metric run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0) as DIR/<name>.npy: "
+                         "logits, loss, flat gradient and batch-norm moving statistics (--forward-only: logits); that "
+                         "step starts from the seeded initial training state")
     args = ap.parse_args()
 
     assert torch.cuda.is_available(), "bench.py needs the MI355X (the HIP path has no CPU fallback)"
@@ -769,6 +789,7 @@ def main():
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
     _lib.load()
+    torch.manual_seed(4321 + rank)              # the global generators (dropout masks): the same inputs in every run
 
     import gc
     import importlib
@@ -802,6 +823,19 @@ def main():
     gen = torch.Generator(device=dev)
     gen.manual_seed(4321 + rank)
     ar_events = []                              # (start, end) HIP events around the gradient all-reduce
+    # --dump-outputs: the last timed step starts from the seeded initial training state, so that what it computes depends
+    # on the arguments alone -- not on the summation order of the float atomics of the steps before it, which training
+    # would carry forward and Adam amplify (a gradient that is exactly 0 but for rounding still moves its variable by ~lr)
+    initial = [t.clone() for t in [fp.flat, opt.m, opt.v] + list(net.buffers())] if args.dump_outputs else None
+
+    @torch.no_grad()
+    def restore_initial_state():
+        for dst, src in zip([fp.flat, opt.m, opt.v] + list(net.buffers()), initial):
+            dst.copy_(src)
+        opt.t = 0
+        state["step"] = 0
+        torch.manual_seed(4321 + rank)
+        gen.manual_seed(4321 + rank)
 
     def train_step():
         s = state["step"]
@@ -816,6 +850,8 @@ def main():
             loss = mod.get_loss(out[0], out[1], y, mask)[0]
         else:
             loss = mod.get_loss(out[0], y, out[1])
+        if args.dump_outputs:
+            state["out"] = (out[0].detach(), loss.detach())
         loss.backward()
         if world > 1:
             # the ranges of the flat bucket whose gradients the backward pass finished early are already travelling
@@ -833,10 +869,14 @@ def main():
 
     def fwd_step():
         with torch.no_grad():
-            return net(inputs["x"], is_training=False)
+            out = net(inputs["x"], is_training=False)
+        if args.dump_outputs:
+            state["out"] = (out[0], None)
+        return out
 
-    def measure(step, steps, warmup, with_kernels, only=None):
-        """W untimed steps, then exactly K steps between barrier + synchronize on both sides; max over ranks."""
+    def measure(step, steps, warmup, with_kernels, only=None, before_last=None):
+        """W untimed steps, then exactly K steps between barrier + synchronize on both sides; max over ranks.
+        before_last: called ahead of the last timed step"""
         for _ in range(warmup):
             step()
         # the host only has to stay ahead of the GPU: a generation-2 garbage collection in the middle of the timed
@@ -856,6 +896,8 @@ def main():
         nhost = min(steps, 10)
         host_elapsed = 0.0
         for i in range(steps):
+            if before_last is not None and i + 1 == steps:
+                before_last()
             step()
             if i + 1 == nhost:
                 host_elapsed = (time.perf_counter() - t0) * steps / nhost     # scaled to K steps (reported per step)
@@ -881,10 +923,20 @@ def main():
     clock = None
     if rank == 0 and not os.environ.get("PCOPS_BENCH_NO_CLOCK"):
         with ClockPoller() as poller:
-            elapsed, local_elapsed, host_elapsed, dom_live = measure(step, args.steps, args.warmup, dom_key is not None, dom_key)
+            elapsed, local_elapsed, host_elapsed, dom_live = measure(step, args.steps, args.warmup, dom_key is not None, dom_key,
+                                                                     restore_initial_state if args.dump_outputs else None)
         clock = poller.summary()
     else:
-        elapsed, local_elapsed, host_elapsed, dom_live = measure(step, args.steps, args.warmup, dom_key is not None, dom_key)
+        elapsed, local_elapsed, host_elapsed, dom_live = measure(step, args.steps, args.warmup, dom_key is not None, dom_key,
+                                                                     restore_initial_state if args.dump_outputs else None)
+    if args.dump_outputs and rank == 0:
+        # before anything below steps the model again or swaps the input batch
+        logits, loss = state["out"]
+        arrays = {"logits": logits}
+        if loss is not None:
+            # not the parameters after the update: Adam maps rounding noise in an exactly-0 gradient to a step of ~lr
+            arrays.update(loss=loss, grad=fp.grad, bn_moving_stats=torch.cat([b.reshape(-1) for b in net.buffers()]))
+        dump_outputs(args.dump_outputs, arrays)
     # N > 1: the SAME invocation also measures rank 0 running alone (no collective, the other ranks parked at a barrier), so a
     # scaling curve built from the per-N lines has its own single-GPU baseline from the same box, build and clock state
     solo = None

@@ -48,6 +48,27 @@ def qbp_cases():
     return cases
 
 
+def reference_fresh():
+    """reference_fresh.npz: ball query, three_nn and top-k on inputs no other golden case uses
+    (tests/test_oracle_golden.py::test_oracle_vs_compiled_reference_fresh_inputs).
+    Alone:  python -c 'import make_golden; make_golden.reference_fresh()'  (in tests/golden)"""
+    assert O.have_ref(), "run `make -C oracle` in the build container first"
+    rng = np.random.default_rng(123)
+    d = {}
+    for seed, (n, m, r, s) in enumerate([(512, 128, 0.2, 32), (300, 77, 0.4, 64), (128, 128, 0.1, 16)]):
+        c = synth_clouds(3, n, seed=100 + seed, kind="ball" if seed % 2 else "surface")
+        q = c[:, rng.permutation(n)[:m]].copy()
+        name = "cloud%d" % seed
+        d[name + "/xyz1"], d[name + "/xyz2"] = c, q
+        d[name + "/radius"], d[name + "/nsample"] = np.float32(r), np.int32(s)
+        d[name + "/idx"] = O.ref_query_ball_point(r, s, c, q)
+        d[name + "/nn_dist"], d[name + "/nn_idx"] = O.ref_three_nn(c, q)
+    dist = rng.integers(0, 9, (2, 7, 33)).astype(np.float32)
+    d["top_k/dist"], d["top_k/k"] = dist, np.int32(12)
+    d["top_k/outi"], d["top_k/out"] = O.ref_select_top_k(12, dist)
+    np.savez_compressed(os.path.join(OUT, "reference_fresh.npz"), **d)
+
+
 def main():
     assert O.have_ref(), "run `make -C oracle` in the build container first"
     rng = np.random.default_rng(0)
@@ -108,6 +129,7 @@ def main():
         d[name + "/grad_points"] = O.ref_three_interpolate_grad(pts.shape, idx, w, go)
     np.savez_compressed(os.path.join(OUT, "three_interp.npz"), **d)
 
+    reference_fresh()
     for f in sorted(os.listdir(OUT)):
         if f.endswith(".npz"):
             print(f, os.path.getsize(os.path.join(OUT, f)), "bytes")

@@ -38,6 +38,26 @@ def test_bench_line_contract():
     assert abs(d["value"] - 16 * 3 / (d["ms_per_step"] * 3e-3)) / d["value"] < 1e-6
 
 
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs: the last timed step's logits, loss, gradient and BN statistics as float32 .npy files within 64 MB.
+    That step starts from the seeded initial state and the inputs are seeded (clouds, labels, weights, dropout masks),
+    so a second run with the same arguments writes the same arrays up to the summation order of the float atomics"""
+    import numpy as np
+    runs = []
+    for name in ("a", "b"):
+        d = _bench(["--dump-outputs", str(tmp_path / name)])
+        assert d["steps"] == 3
+        runs.append({f[:-4]: np.load(tmp_path / name / f) for f in sorted(os.listdir(tmp_path / name))})
+    a, b = runs
+    assert sorted(a) == ["bn_moving_stats", "grad", "logits", "loss"]
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert a["logits"].shape == (16, 15) and a["loss"].shape == ()
+    assert np.abs(a["grad"]).max() > 0
+    for k, v in a.items():
+        assert v.dtype == np.float32 and np.isfinite(v).all(), k
+        np.testing.assert_allclose(v, b[k], rtol=1e-5, atol=1e-5 * float(np.abs(v).max()), err_msg=k)
+
+
 def test_bench_two_ranks_control_flow():
     d = _bench(["--gpus", "2"], env={"PCOPS_BENCH_SHARED_GPU": "1"})
     assert d["n_gpus"] == 2 and d["rccl_ranks"] == 2 and len(d["per_rank_clouds_per_s"]) == 2
