@@ -83,6 +83,16 @@ int pcops_get_option(int option);
 /* diagnostics: the matrix pipe the calling thread's LAST matrix-product launch took (0 fp32 pipe or not a product, 1 bf16
  * pipe with split operands, 2 the one-pass backward's fp32 dW + split dX) -- what a roofline label should be priced on */
 int pcops_last_launch_pipe(void);
+/* ... and the variant it took, as up to n ints into out; returns the number of fields (5) or PCOPS_ERR_NULL_POINTER:
+ *   [0] path   0 none yet, 1 tiled fp32 kernel, 2 wave-stream kernel, 3 one-pass backward (pcops_mlp_bwd_fused*),
+ *              4 / 5 / 6 / 7 weight gradient: split-operand / producer-consumer / wave-stream / legacy split-K kernel
+ *   [1] split  1 when the operands are split into bf16 pieces (the one-pass backward: 1 its dX half, 2 both halves)
+ *   [2] bn     output columns per block (64, 96, 128; the weight gradients: columns of their dW tile; 0 tiled)
+ *   [3] wst    1 when the weights are streamed rather than resident in LDS
+ *   [4] pool   pooled operand form: 0 none, 1 whole 32-row tiles, 2 arbitrary groups, 3 s4 groups (pcops_mlp_gemm_fwd_pool
+ *              with S % 32 != 0), 4 compacted rows; the Gram form of the one-pass backward adds 8
+ * A diagnostic like the one above: no product path reads it. */
+int pcops_last_launch_plan(int *out, int n);
 
 /* ------------------------------------------------------------------ sampling */
 /* farthestpointsamplingLauncher(b,n,m,inp,temp,out)   sampling/tf_sampling.cpp:94,
@@ -603,8 +613,12 @@ int pcops_edge_first_moments(int b, int n, int m, int s, const float *xyz, const
 int pcops_edge_first_wgrad(int b, int n, int m, int s, int c, const float *G, const float *xyz, const int *idx,
                            float *wpartial, pcops_stream_t stream);
 /* the one-pass backward (pcops_mlp_bwd_fused_rows) of the POOLED layer above such a first layer: the masked gradient of
- * the first layer is not written -- E^T Gm leaves as edge_stats [pcops_mlp_bwd_fused_groups(M, K, N, S, 1)][6][K], in the
- * place of pcops_edge_first_wgrad's wpartial.  Groups of S rows that are not whole 32-row tiles (the k neighbours). */
+ * the first layer is not written -- E^T Gm leaves as edge_stats [pcops_mlp_bwd_fused_edge_groups(M, K, N, S, 0)][6][K], in
+ * the place of pcops_edge_first_wgrad's wpartial.  Groups of S rows that are not whole 32-row tiles (the k neighbours).
+ *   pcops_mlp_bwd_fused_edge_groups  the edge forms' own query: 0 when pcops_mlp_bwd_fused_edge (gram = 0) or
+ *                                    pcops_mlp_bwd_fused_edge_gw (gram = 1) does not take (M, K, N, S), otherwise the
+ *                                    partial copies -- pcops_mlp_bwd_fused_groups / _gw_groups with S % 32 == 0 refused */
+int pcops_mlp_bwd_fused_edge_groups(long long M, int K, int N, int S, int gram);
 int pcops_mlp_bwd_fused_edge(long long M, int K, int N, const float *Yprev, const float *a_scale, const float *a_shift,
                                   const float *Y, const float *p, const float *q, const float *t, const float *gpool,
                                   const unsigned char *argmax, int S, const float *W, float *partial, float *dW, float *db,
@@ -616,8 +630,9 @@ int pcops_mlp_bwd_fused_edge(long long M, int K, int N, const float *Yprev, cons
  * -- a 64 x 64 Gram matrix on the matrix pipe instead of the K x N product (half the weight gradient's matrix time at
  * N = 128), the arg rows as vector work, the K x N product once on the summed partials.  Same reference op as
  * pcops_mlp_bwd_fused (tf.gradients of conv2d + batch_norm + reduce_max, pointnet2/utils/pointnet_util.py:117-127,
- * dgcnn/models/transform_nets.py:19-27); results equal to it to fp32 rounding.  Uncompacted rows, S % 32 == 0 or
- * 11 <= S <= 255, PCOPS_OPT_BWD_FUSED_DX_SPLIT_BF16 on; bias [N] may be NULL (a layer without bias).
+ * dgcnn/models/transform_nets.py:19-27); results equal to it to fp32 rounding.  Uncompacted rows, 11 <= S <= 255
+ * (whole 32-row tiles included; the edge form: S % 32 != 0 only, pcops_mlp_bwd_fused_edge_groups(M, K, N, S, 1)),
+ * PCOPS_OPT_BWD_FUSED_DX_SPLIT_BF16 on; bias [N] may be NULL (a layer without bias).
  *   pcops_mlp_bwd_fused_gw_groups  workgroups = partial copies, 0 when the shape is not taken
  *   partial: groups (K N + N + K K + K) floats of scratch */
 int pcops_mlp_bwd_fused_gw_groups(long long M, int K, int N, int S);

@@ -129,6 +129,7 @@ PLAIN = {
     "pcops_mlp_wgrad_splits": ([_LL, _I, _I], _I),
     "pcops_mlp_bwd_fused_groups": ([_LL, _I, _I, _I, _I], _I),
     "pcops_mlp_bwd_fused_gw_groups": ([_LL, _I, _I, _I], _I),
+    "pcops_mlp_bwd_fused_edge_groups": ([_LL, _I, _I, _I, _I], _I),
     "pcops_gather_stack_rows_supported": ([_I, _I, _I, _I, _I, _I, _P], _I),
     "pcops_sa_scatter_rows_supported": ([_I, _I, _I, _I], _I),
     "pcops_sa_gather_stats_rows": ([_LL], _I),
@@ -151,6 +152,7 @@ PLAIN = {
     "pcops_mlp_pool_top_supported": ([_I, _I, _I, _I], _I),
     "pcops_knn_graph_path": ([_I, _I, _I, _I, _P], _I),
     "pcops_last_launch_pipe": ([], _I),
+    "pcops_last_launch_plan": ([_P, _I], _I),
     "pcops_set_option": ([_I, _I], _I),
     "pcops_get_option": ([_I], _I),
     "pcops_set_deterministic": ([_I], None),

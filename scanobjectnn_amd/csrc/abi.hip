@@ -40,6 +40,12 @@ int env_int(const char *name, int dflt) {
     const char *e = getenv(name);
     return e ? atoi(e) : dflt;
 }
+// an environment seed is held to the range pcops_set_option accepts (0..hi): a 3, 7 or -1 from the environment would
+// otherwise be returned by pcops_get_option and reach launchers that only know 0..2
+int env_opt(const char *name, int dflt, int hi) {
+    const int v = env_int(name, dflt);
+    return v < 0 ? 0 : (v > hi ? hi : v);
+}
 std::atomic<int> g_options[PCOPS_OPT_COUNT] = {};
 std::atomic<int> g_options_init{0};
 void options_init() {
@@ -47,11 +53,11 @@ void options_init() {
     static std::atomic_flag busy = ATOMIC_FLAG_INIT;
     while (busy.test_and_set(std::memory_order_acquire)) {}
     if (!g_options_init.load(std::memory_order_relaxed)) {
-        g_options[PCOPS_OPT_GEMM_SPLIT_BF16].store(env_int("PCOPS_GEMM_BF3", 1));
+        g_options[PCOPS_OPT_GEMM_SPLIT_BF16].store(env_opt("PCOPS_GEMM_BF3", 1, 2));
         g_options[PCOPS_OPT_WGRAD_SPLIT_BF16].store(env_int("PCOPS_WGRAD_BF3", 1) != 0);
-        g_options[PCOPS_OPT_BWD_FUSED_DX_SPLIT_BF16].store(env_int("PCOPS_BWD_FUSED_DX3", 2));
+        g_options[PCOPS_OPT_BWD_FUSED_DX_SPLIT_BF16].store(env_opt("PCOPS_BWD_FUSED_DX3", 2, 2));
         g_options[PCOPS_OPT_KNN_F16_PREFILTER].store(env_int("PCOPS_KNN_F16", 1) != 0);
-        g_options[PCOPS_OPT_DGRAD_SPLIT_BF16].store(env_int("PCOPS_DGRAD_BF3", 1));
+        g_options[PCOPS_OPT_DGRAD_SPLIT_BF16].store(env_opt("PCOPS_DGRAD_BF3", 1, 2));
         g_options[PCOPS_OPT_BWD_FUSED_GRAM_WGRAD].store(env_int("PCOPS_BWD_FUSED_GW", 0) != 0);
         g_options_init.store(1, std::memory_order_release);
     }
@@ -81,6 +87,17 @@ extern "C" int pcops_get_deterministic(void) { return g_deterministic.load(); }
 static thread_local int t_last_pipe = 0;
 void pcops_note_pipe(int pipe) { t_last_pipe = pipe; }
 extern "C" int pcops_last_launch_pipe(void) { return t_last_pipe; }
+
+// ... and which variant it was (pcops.h pcops_last_launch_plan): noted by the launchers where they decide, like the pipe
+static thread_local int t_last_plan[5] = {0, 0, 0, 0, 0};
+void pcops_note_plan(int path, int split, int bn, int wst, int pool) {
+    t_last_plan[0] = path; t_last_plan[1] = split; t_last_plan[2] = bn; t_last_plan[3] = wst; t_last_plan[4] = pool;
+}
+extern "C" int pcops_last_launch_plan(int *out, int n) {
+    if (!out || n < 0) return PCOPS_ERR_NULL_POINTER;
+    for (int i = 0; i < n && i < 5; ++i) out[i] = t_last_plan[i];
+    return 5;
+}
 
 // ---------------------------------------------------------------------------------------------------------------
 // The training step's parameter update as ONE launch over the flat buffers (host: train_util.TFAdam).  TensorFlow's Adam

@@ -31,6 +31,8 @@ static inline unsigned cdiv(long long a, long long b) { return (unsigned)((a + b
 extern "C" int pcops_get_deterministic(void);     // abi.hip: bit-reproducible backward passes requested
 extern "C" int pcops_get_option(int option);      // abi.hip: the arithmetic options of pcops.h (read at every call)
 void pcops_note_pipe(int pipe);                   // abi.hip: what pcops_last_launch_pipe() reports (0 fp32, 1 split bf16, 2 both)
+// abi.hip: what pcops_last_launch_plan() reports -- the variant the last product launch took (codes in pcops.h)
+void pcops_note_plan(int path, int split, int bn, int wst, int pool);
 
 constexpr int kWave = 64;  // CDNA wavefront
 

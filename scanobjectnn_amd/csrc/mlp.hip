@@ -280,15 +280,11 @@ __global__ __launch_bounds__(256) void gemm_rt_kernel(GemmArgs a) {
         float4 ra[4], rb[B_PASS];
         auto load_chunk = [&](int kc) {
             const int k = kc * kBK + a_kq;
-            float4 c0, c1, c2, c3, c4;
+            float4 c0, c1, c2;
             if (AM != A_PLAIN) {
                 c0 = ld4(a.v0, true, k, (K + 3) & ~3);
                 c1 = ld4(a.v1, true, k, (K + 3) & ~3);
                 if (AM >= A_DY) c2 = ld4(a.v2, true, k, (K + 3) & ~3);
-                if (AM == A_DYPOOL) {
-                    c3 = ld4(a.v3, true, k, (K + 3) & ~3);
-                    c4 = ld4(a.v4, true, k, (K + 3) & ~3);
-                }
             }
 #pragma unroll
             for (int p = 0; p < 4; ++p) {
@@ -310,19 +306,19 @@ __global__ __launch_bounds__(256) void gemm_rt_kernel(GemmArgs a) {
                         x.y = fmaf(c0.y, g.y, fmaf(c1.y, y.y, c2.y));
                         x.z = fmaf(c0.z, g.z, fmaf(c1.z, y.z, c2.z));
                         x.w = fmaf(c0.w, g.w, fmaf(c1.w, y.w, c2.w));
-                    } else {  // A_DYPOOL: G is non-zero only at the arg-max row of each (group, channel)
+                    } else {  // A_DYPOOL: G is non-zero only at the arg-max row of each (group, channel); gpool
+                              // already carries the pooled rows' ReLU mask (ABI 3: pool_scale / pool_shift are not read)
                         const float4 y = ld4(a.X2 + r * a.ldx, xvec, k, K);
                         const long long g = (long long)((unsigned)r / (unsigned)a.S);   // rows < 2^31 (launcher)
                         const int s = (int)((unsigned)r - (unsigned)g * (unsigned)a.S);
                         const float yy[4] = {y.x, y.y, y.z, y.w};
                         const float cc0[4] = {c0.x, c0.y, c0.z, c0.w}, cc1[4] = {c1.x, c1.y, c1.z, c1.w};
-                        const float cc2[4] = {c2.x, c2.y, c2.z, c2.w}, cc3[4] = {c3.x, c3.y, c3.z, c3.w};
-                        const float cc4[4] = {c4.x, c4.y, c4.z, c4.w};
+                        const float cc2[4] = {c2.x, c2.y, c2.z, c2.w};
                         float o[4];
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
                             float gm = 0.f;
-                            if (k + e < K && a.argmax[g * K + k + e] == s && fmaf(yy[e], cc3[e], cc4[e]) > 0.f)
+                            if (k + e < K && a.argmax[g * K + k + e] == s)
                                 gm = a.gpool[g * K + k + e];
                             o[e] = (k + e < K) ? fmaf(cc0[e], gm, fmaf(cc1[e], yy[e], cc2[e])) : 0.f;
                         }
@@ -1676,6 +1672,9 @@ PCOPS_HIDDEN int launch_gemm_ws(GemmArgs &a, const WsPlan &pl, hipStream_t st) {
         hipLaunchKernelGGL(kern, dim3(pl.gy > P_ ? pl.gy : P_, pl.ncb), dim3(512), pl.lds, st, a);    \
     } while (0)
     pcops_note_pipe(pl.bf3 ? 1 : 0);
+    pcops_note_plan(2, pl.bf3 ? 1 : 0, pl.bn, pl.wst ? 1 : 0,
+                    (EM == E_FWD && a.pool_s4 > 0) ? 3 : ((EM == E_FWD && a.pool_sub > 0) ? 1 : (AM == A_DYPOOLU ? 1 :
+                    (AM == A_DYPOOL ? 2 : (AM == A_DYPOOLB ? 4 : 0)))));
     if constexpr (EM == E_FWD || (EM == E_MASK && is_dy(AM)) || has_add(EM)) {
     if (pl.bf3) {
 #define PCOPS_WS3_LAUNCH(NT_, EH_)                                                                    \
@@ -1802,6 +1801,7 @@ static int launch_gemm(GemmArgs &a, hipStream_t st) {
     }
     if (a.blocks) return PCOPS_ERR_UNSUPPORTED;      // compacted rows: wave-stream kernels only
     pcops_note_pipe(0);                              // the tiled kernel: fp32 MFMA
+    pcops_note_plan(1, 0, 0, 0, AM == A_DYPOOL ? 2 : ((EM == E_FWD && a.pool_sub > 0) ? 1 : 0));
     return launch_gemm_rt<AM, EM>(a, st);
 }
 
@@ -2251,7 +2251,7 @@ __global__ __launch_bounds__(256) void wgrad_kernel(WgradArgs a) {
     const int half = lane >> 5, li = lane & 31;
 
     // per-lane channel constants
-    float asc[VK], ash[VK], cp[VN], cq[VN], ct[VN], dsc[VN], dsh[VN];
+    float asc[VK], ash[VK], cp[VN], cq[VN], ct[VN];
     bool kin[VK], nin[VN];
 #pragma unroll
     for (int e = 0; e < VK; ++e) {
@@ -2267,8 +2267,6 @@ __global__ __launch_bounds__(256) void wgrad_kernel(WgradArgs a) {
         cp[e] = nin[e] ? a.p[n] : 0.f;
         cq[e] = nin[e] ? a.q[n] : 0.f;
         ct[e] = nin[e] ? a.t[n] : 0.f;
-        dsc[e] = (a.dmode == A_DYPOOL && nin[e]) ? a.dsc[n] : 0.f;
-        dsh[e] = (a.dmode == A_DYPOOL && nin[e]) ? a.dsh[n] : 0.f;
     }
 
     f32x16 acc[VK][VN];
@@ -2308,7 +2306,7 @@ __global__ __launch_bounds__(256) void wgrad_kernel(WgradArgs a) {
                 } else {
                     const long long g = (long long)((unsigned)r / (unsigned)a.S);   // rows < 2^31 (launcher)
                     const int s = (int)((unsigned)r - (unsigned)g * (unsigned)a.S);
-                    gm = (a.argmax[g * N + n] == s && fmaf(y, dsc[e], dsh[e]) > 0.f) ? a.gpool[g * N + n] : 0.f;
+                    gm = a.argmax[g * N + n] == s ? a.gpool[g * N + n] : 0.f;      // (gpool is already masked, ABI 3)
                 }
                 d = fmaf(cp[e], gm, fmaf(cq[e], y, ct[e]));
             }
@@ -2410,8 +2408,6 @@ __global__ __launch_bounds__(256, 1) void wgrad_ws_kernel(WgradArgs a) {
     const float4 cp = *reinterpret_cast<const float4 *>(&coefD[dcq]);
     const float4 cq = *reinterpret_cast<const float4 *>(&coefD[NB + dcq]);
     const float4 ct = *reinterpret_cast<const float4 *>(&coefD[2 * NB + dcq]);
-    const float4 cds = *reinterpret_cast<const float4 *>(&coefD[3 * NB + dcq]);
-    const float4 cdh = *reinterpret_cast<const float4 *>(&coefD[4 * NB + dcq]);
 
     f32x16 acc[TK][TN];
 #pragma unroll
@@ -2480,10 +2476,10 @@ __global__ __launch_bounds__(256, 1) void wgrad_ws_kernel(WgradArgs a) {
                 unsigned s;
                 prs.split(r, glast, gdummy, s);
                 const unsigned am = pm[j];
-                g.x = ((am & 0xffu) == s && fmaf(y.x, cds.x, cdh.x) > 0.f) ? g.x : 0.f;
-                g.y = (((am >> 8) & 0xffu) == s && fmaf(y.y, cds.y, cdh.y) > 0.f) ? g.y : 0.f;
-                g.z = (((am >> 16) & 0xffu) == s && fmaf(y.z, cds.z, cdh.z) > 0.f) ? g.z : 0.f;
-                g.w = ((am >> 24) == s && fmaf(y.w, cds.w, cdh.w) > 0.f) ? g.w : 0.f;
+                g.x = (am & 0xffu) == s ? g.x : 0.f;          // (gpool is already masked, ABI 3)
+                g.y = ((am >> 8) & 0xffu) == s ? g.y : 0.f;
+                g.z = ((am >> 16) & 0xffu) == s ? g.z : 0.f;
+                g.w = (am >> 24) == s ? g.w : 0.f;
             }
             float4 d;
             d.x = fmaf(cp.x, g.x, fmaf(cq.x, y.x, ct.x));
@@ -5063,6 +5059,7 @@ int wgrad_impl(WgradArgs &a, float *partial, float *dW, float *db, hipStream_t s
     if (ws_enabled() && wgrad_pc_enabled() && !self && a.amode != A_XYZ &&
         wgrad_bf3_plan(M, K, N, ldx, X, G, Y, gpool, argmax, &b3)) {
         pcops_note_pipe(1);
+        pcops_note_plan(4, 1, 128, 0, a.blocks ? 4 : (a.dmode == A_DY ? 0 : (a.S % 32 == 0 ? 1 : 2)));
         splits = b3.groups;
         a.part = partial; a.dbpart = partial + (long long)splits * K * N;
         const dim3 grid(b3.groups, b3.kblocks, b3.nblocks);
@@ -5094,6 +5091,7 @@ int wgrad_impl(WgradArgs &a, float *partial, float *dW, float *db, hipStream_t s
         splits = pc.groups;
         a.part = partial; a.dbpart = partial + (long long)splits * K * N;
         const dim3 grid(pc.groups, pc.kblocks, pc.nblocks);
+        pcops_note_plan(5, 0, 64 * pc.tn, 0, a.blocks ? 4 : (a.dmode == A_DY || self ? 0 : (a.S % 32 == 0 ? 1 : 2)));
 #define PCOPS_PC_LAUNCH(TK_, TN_, AM_, DM_)                                                                \
     do {                                                                                                   \
         auto kern = wgrad_pc_kernel<TK_, TN_, AM_, DM_, K96_>;                                                \
@@ -5138,6 +5136,7 @@ int wgrad_impl(WgradArgs &a, float *partial, float *dW, float *db, hipStream_t s
         splits = pl.groups;
         a.part = partial; a.dbpart = partial + (long long)splits * K * N;
         const dim3 grid(pl.groups, pl.kblocks, pl.nblocks);
+        pcops_note_plan(6, 0, 32 * pl.tn, 0, a.dmode == A_DY ? 0 : 2);
 #define PCOPS_WG_LAUNCH(TK_, TN_, RS_, AM_, DM_)                                                           \
     do {                                                                                                   \
         auto kern = wgrad_ws_kernel<TK_, TN_, RS_, AM_, DM_>;                                              \
@@ -5160,6 +5159,7 @@ int wgrad_impl(WgradArgs &a, float *partial, float *dW, float *db, hipStream_t s
 #undef PCOPS_WG_LAUNCH
     } else {
         splits = wgrad_legacy_splits(M, K, N);
+        pcops_note_plan(7, 0, 128, 0, a.dmode == A_DY ? 0 : 2);
         a.rows_per_block = (int)((((M + splits - 1) / splits) + 7) / 8 * 8);
         a.part = partial; a.dbpart = partial + (long long)splits * K * N;
         hipLaunchKernelGGL((wgrad_kernel<2, 4>), dim3((K + 63) / 64, (N + 127) / 128, splits), dim3(256), 0, st, a);
@@ -5219,6 +5219,7 @@ int bwd_fused_launch(WgradArgs &a, bool xyz, int groups, float *partial, float *
     const bool pooled = a.gpool != nullptr;
     const bool nsk = nsk_on() && tn == 2 && N <= 96;
     pcops_note_pipe(dw3 ? 1 : (dx3 ? 2 : 0));
+    pcops_note_plan(3, dw3 ? 2 : (dx3 ? 1 : 0), NB, 0, (gw ? 8 : 0) + (a.blocks ? 4 : (!pooled ? 0 : (a.S % 32 == 0 && !side ? 1 : 2))));
     if (gw) {
         if (!dx3 || xyz || a.blocks || !a.gpool) return PCOPS_ERR_UNSUPPORTED;
 #define PCOPS_BFG_LAUNCH(TN_, DM_, NSK_, SIDE_)                                                            \
@@ -5889,6 +5890,8 @@ int pcops_mlp_bwd_fused_rows(long long M, int K, int N, const float *Yprev, cons
     return bwd_fused_launch(a, false, groups, partial, dW, db, as_stream(stream));
 }
 
+static int bwd_fused_edge_groups(long long M, int K, int N, int S, int gram);
+
 int pcops_mlp_bwd_fused_edge(long long M, int K, int N, const float *Yprev, const float *a_scale, const float *a_shift,
                                   const float *Y, const float *p, const float *q, const float *t, const float *gpool,
                                   const unsigned char *argmax, int S, const float *W, float *partial, float *dW, float *db,
@@ -5898,8 +5901,8 @@ int pcops_mlp_bwd_fused_edge(long long M, int K, int N, const float *Yprev, cons
     PCOPS_REQUIRE_PTR(p); PCOPS_REQUIRE_PTR(q); PCOPS_REQUIRE_PTR(t); PCOPS_REQUIRE_PTR(W); PCOPS_REQUIRE_PTR(gpool);
     PCOPS_REQUIRE_PTR(argmax); PCOPS_REQUIRE_PTR(partial); PCOPS_REQUIRE_PTR(dW); PCOPS_REQUIRE_PTR(stats_partial);
     PCOPS_REQUIRE_PTR(edge_rows); PCOPS_REQUIRE_PTR(edge_stats);
-    const int groups = bwd_fused_groups(M, K, N, S, true);
-    if (groups == 0 || S % 32 == 0) return PCOPS_ERR_UNSUPPORTED;       // (whole-tile groups take another operand form)
+    const int groups = bwd_fused_edge_groups(M, K, N, S, 0);
+    if (groups == 0) return PCOPS_ERR_UNSUPPORTED;
     if ((reinterpret_cast<uintptr_t>(Yprev) & 15) || (reinterpret_cast<uintptr_t>(Y) & 15) ||
         (reinterpret_cast<uintptr_t>(gpool) & 15) || (reinterpret_cast<uintptr_t>(W) & 15) ||
         (reinterpret_cast<uintptr_t>(argmax) & 3) || (reinterpret_cast<uintptr_t>(edge_rows) & 15))
@@ -5914,7 +5917,8 @@ int pcops_mlp_bwd_fused_edge(long long M, int K, int N, const float *Yprev, cons
 }
 
 /* ---- the one-pass backward of a POOLED layer with its weight gradient in the Gram form (round 6; bwd_fused_kernel<.., GW>):
- * uncompacted rows, groups of S % 32 == 0 or 11 <= S <= 255 rows, split-operand dX half.  bias [N] (may be NULL) is the
+ * uncompacted rows, groups of 11 <= S <= 255 rows (whole 32-row tiles included; the edge form below: S % 32 != 0 only),
+ * split-operand dX half.  bias [N] (may be NULL) is the
  * layer's own bias -- Y = X W + bias is what the form substitutes.  partial: groups (K N + N + K K + K) floats. */
 static int bwd_fused_gw_groups(long long M, int K, int N, int S) {
     if (pcops_get_option(PCOPS_OPT_BWD_FUSED_GRAM_WGRAD) == 0 || S < 11 || S > 255) return 0;
@@ -5923,6 +5927,17 @@ static int bwd_fused_gw_groups(long long M, int K, int N, int S) {
 }
 
 int pcops_mlp_bwd_fused_gw_groups(long long M, int K, int N, int S) { return bwd_fused_gw_groups(M, K, N, S); }
+
+// the edge forms (pcops_mlp_bwd_fused_edge / _edge_gw) take groups that are NOT whole 32-row tiles only (whole-tile groups
+// take another operand form), so they have a query of their own: gram = 0 the plain weight gradient, 1 the Gram form
+static int bwd_fused_edge_groups(long long M, int K, int N, int S, int gram) {
+    if (S < 1 || S % 32 == 0) return 0;
+    return gram ? bwd_fused_gw_groups(M, K, N, S) : bwd_fused_groups(M, K, N, S, 1);
+}
+
+int pcops_mlp_bwd_fused_edge_groups(long long M, int K, int N, int S, int gram) {
+    return bwd_fused_edge_groups(M, K, N, S, gram);
+}
 
 static void gw_carve(WgradArgs &a, float *partial, int groups, int K, int N) {
     a.gram_part = partial + (long long)groups * ((long long)K * N + N);
@@ -5965,8 +5980,8 @@ int pcops_mlp_bwd_fused_edge_gw(long long M, int K, int N, const float *Yprev, c
     PCOPS_REQUIRE_PTR(p); PCOPS_REQUIRE_PTR(q); PCOPS_REQUIRE_PTR(t); PCOPS_REQUIRE_PTR(W); PCOPS_REQUIRE_PTR(gpool);
     PCOPS_REQUIRE_PTR(argmax); PCOPS_REQUIRE_PTR(partial); PCOPS_REQUIRE_PTR(dW); PCOPS_REQUIRE_PTR(db);
     PCOPS_REQUIRE_PTR(stats_partial); PCOPS_REQUIRE_PTR(edge_rows); PCOPS_REQUIRE_PTR(edge_stats);
-    const int groups = bwd_fused_gw_groups(M, K, N, S);
-    if (groups == 0 || S % 32 == 0) return PCOPS_ERR_UNSUPPORTED;       // (whole-tile groups take another operand form)
+    const int groups = bwd_fused_edge_groups(M, K, N, S, 1);
+    if (groups == 0) return PCOPS_ERR_UNSUPPORTED;
     if ((reinterpret_cast<uintptr_t>(Yprev) & 15) || (reinterpret_cast<uintptr_t>(Y) & 15) ||
         (reinterpret_cast<uintptr_t>(gpool) & 15) || (reinterpret_cast<uintptr_t>(W) & 15) ||
         (reinterpret_cast<uintptr_t>(argmax) & 3) || (reinterpret_cast<uintptr_t>(edge_rows) & 15))

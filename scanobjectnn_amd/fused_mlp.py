@@ -133,8 +133,8 @@ class FusedMLPStack(torch.autograd.Function):
                     # ... and, where the layer above takes the one-pass backward, the edge rows themselves (32 bytes each):
                     # E^T Gm is then reduced inside that kernel and the masked gradient is never written
                     N1 = layers[1][0].shape[-1]
-                    if (EDGE_DIRECT_FUSED and BWD_FUSED and L == 2 and pool and S % 32 != 0
-                            and lib.pcops_mlp_bwd_fused_groups(R, N, N1, S, 1)):
+                    if (EDGE_DIRECT_FUSED and BWD_FUSED and L == 2 and pool
+                            and lib.pcops_mlp_bwd_fused_edge_groups(R, N, N1, S, 0)):
                         ctx.edge_rows = _f32((R, 8), dev)
                     _lib.call("pcops_edge_first_moments", B, Nsrc, M, S, xyz.data_ptr(), idx.data_ptr(), mom.data_ptr(),
                               _p(getattr(ctx, "edge_rows", None)))
@@ -418,16 +418,20 @@ class FusedMLPStack(torch.autograd.Function):
                 # the bandwidth-bound narrow layers: data and weight gradient in ONE pass over Y / Yprev
                 fused_groups = lib.pcops_mlp_bwd_fused_groups(R, K, N, S if pooled else 0, 1 if pooled else 0)
             if fused_groups:
+                edge_rows = getattr(ctx, "edge_rows", None) if (l == 1 and pooled and getattr(ctx, "direct", False)) else None
+                if edge_rows is not None and lib.pcops_mlp_bwd_fused_edge_groups(R, K, N, S, 0) != fused_groups:
+                    edge_rows = None
                 # pooled layer on uncompacted rows: the weight gradient in its Gram form (pcops.h, round 6) -- a K x K
-                # product on the matrix pipe + the arg rows as vector work instead of the K x N product
+                # product on the matrix pipe + the arg rows as vector work instead of the K x N product.  The query asked
+                # is the one of the launcher that runs: the edge forms take fewer group sizes (S % 32 != 0)
                 gw = (pooled and rows is None and not xyz_prev and
-                      lib.pcops_mlp_bwd_fused_gw_groups(R, K, N, S) == fused_groups)
+                      (lib.pcops_mlp_bwd_fused_edge_groups(R, K, N, S, 1) if edge_rows is not None
+                       else lib.pcops_mlp_bwd_fused_gw_groups(R, K, N, S)) == fused_groups)
                 scratch = _f32(fused_groups * (K * N + N + ((K * K + K) if gw else 0)), dev)
                 dW, db = _f32((K, N), dev), _f32(N, dev)
                 P = fused_groups
                 part = _f32((P, 2, K), dev)
                 bl = ctx.biases[l]
-                edge_rows = getattr(ctx, "edge_rows", None) if (l == 1 and pooled and getattr(ctx, "direct", False)) else None
                 if edge_rows is not None:   # the first EdgeConv layer below, input without gradient: E^T Gm reduced in the kernel
                     xstats = _f32((P, 6, K), dev)
                     if gw:

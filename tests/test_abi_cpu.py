@@ -65,6 +65,27 @@ def test_argument_validation_without_gpu():
     assert lib.pcops_scatter_rows_sorted_supported(1 << 30, 64) == 0
 
 
+def test_environment_seeds_stay_within_the_setter_range():
+    """the environment seeds the option table once per process (options_init); a value pcops_set_option would refuse
+    (3, 7, -1) is held to the setter's range, so pcops_get_option never returns what no caller could have set"""
+    code = ("from scanobjectnn_amd import _lib; lib = _lib.load(); "
+            "print(' '.join(str(lib.pcops_get_option(o)) for o in range(1, 7)))")
+    env = dict(os.environ, PCOPS_BWD_FUSED_DX3="7", PCOPS_GEMM_BF3="-1", PCOPS_DGRAD_BF3="3",
+               PCOPS_WGRAD_BF3="-1", PCOPS_KNN_F16="5", PCOPS_BWD_FUSED_GW="-1")
+    out = subprocess.run([sys.executable, "-c", code], cwd=ROOT, env=env, capture_output=True, text=True)
+    vals = [int(v) for v in out.stdout.split()]
+    assert len(vals) == 6, out.stderr
+    gemm, wgrad, dx3, knn, dgrad, gw = vals
+    assert gemm == 0 and dx3 == 2 and dgrad == 2          # 0..2 options: clamped into the range
+    assert wgrad in (0, 1) and knn in (0, 1) and gw in (0, 1)
+    # and the library's own defaults are untouched when nothing is set
+    env = {k: v for k, v in os.environ.items()
+           if k not in ("PCOPS_BWD_FUSED_DX3", "PCOPS_GEMM_BF3", "PCOPS_DGRAD_BF3", "PCOPS_WGRAD_BF3",
+                        "PCOPS_KNN_F16", "PCOPS_BWD_FUSED_GW")}
+    out = subprocess.run([sys.executable, "-c", code], cwd=ROOT, env=env, capture_output=True, text=True)
+    assert out.stdout.split() == ["1", "1", "2", "1", "1", "0"], out.stderr
+
+
 def test_compacted_stack_support_is_one_library_answer():
     """`fused_mlp._compactable` asks the library whether EVERY launch of a stack on compacted rows has a kernel (the
     *_rows entry points have no tiled fallback) instead of restating the kernels' shape conditions in Python"""
