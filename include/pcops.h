@@ -830,6 +830,48 @@ int pcops_transform3_fwd(int b, int n, const float *x, const float *T, float *ou
 int pcops_transform3_bwd(int b, int n, const float *x, const float *T, const float *grad_out, float *dT, float *dx,
                          pcops_stream_t stream);
 
+/* ------------------------------------------------------------------ SpiderConv (csrc/spider.hip)
+ * One SpiderConv layer of SpiderCNN (SpiderCNN/utils/tf_util.py:127-236, group_norm_for_conv :407-429).  P = b n centre
+ * points, k neighbours, t = 5 Taylor channels, feat (b, n, c), idx (b, n, k) int32 in [0, n) (self first), delta (b, n, k, 3)
+ * = neighbour - centre.  theta (19, t) holds the weight_* variables in the order x y z xyz xy yz xz xx yy zz xxy xyy xxz
+ * xzz yyz yzz xxx yyy zzz, tbias (t) is taylor/biases:
+ *   g (b, n, k, t)        g[p,j,t] = tbias[t] + sum_m theta[m,t] phi_m(delta[p,j])
+ *   y (b, n, o)           y[p,o] = bias[o] + sum_{j,c,t} feat[idx[p,j],c] g[p,j,t] w[(j c_ + c) t_ + t][o]; w is conv/weights
+ *                         [1, k, c t, o] read as a (k c t) x o row-major matrix.  The expanded operand A[p,(j,c,t)] is formed
+ *                         tile by tile in LDS and never written to memory (fp32 MFMA).
+ * Backward: wgrad dw = A^T dy, dbias = column sums of dy (may be NULL); dgrad dfeat_grouped (b, n, k, c) = sum_t (dy w^T) g
+ * (NULL: not wanted, e.g. the raw cloud of the first layer) and dg (b, n, k, t) = sum_c (dy w^T) feat[idx]; the caller
+ * scatters dfeat_grouped with pcops_group_point_grad / pcops_scatter_rows_sorted; taylor_bwd reduces dg to dtheta (19, t)
+ * and dtbias (t).  Every output is written whole (no accumulation); every sum is taken in a fixed order, with no float
+ * atomics, so two backward passes are bit-identical whatever pcops_set_deterministic says.
+ * Supported: 1 <= k <= 64 and k <= n (PCOPS_ERR_BAD_ARGUMENT), t == 5, 1 <= c <= 256, o % 16 == 0 with 16 <= o <= 512,
+ * b n k max(c, t) < 2^31; PCOPS_ERR_UNSUPPORTED outside.  Workspaces are caller-owned device buffers of the queried size
+ * (0: may be NULL). */
+int pcops_spider_taylor_fwd(long long rows, int t, const float *delta, const float *theta, const float *tbias, float *g,
+                            pcops_stream_t stream);
+unsigned long long pcops_spider_taylor_bwd_workspace_bytes(long long rows, int t);
+int pcops_spider_taylor_bwd(long long rows, int t, const float *delta, const float *dg, float *dtheta, float *dtbias,
+                            void *workspace, pcops_stream_t stream);
+int pcops_spider_conv_fwd(int b, int n, int c, int k, int t, int o, const float *feat, const int *idx, const float *g,
+                          const float *w, const float *bias, float *y, pcops_stream_t stream);
+unsigned long long pcops_spider_conv_wgrad_workspace_bytes(int b, int n, int c, int k, int t, int o);
+int pcops_spider_conv_wgrad(int b, int n, int c, int k, int t, int o, const float *feat, const int *idx, const float *g,
+                            const float *dy, float *dw, float *dbias, void *workspace, pcops_stream_t stream);
+int pcops_spider_conv_dgrad(int b, int n, int c, int k, int t, int o, const float *feat, const int *idx, const float *g,
+                            const float *w, const float *dy, float *dfeat_grouped, float *dg, pcops_stream_t stream);
+
+/* Group norm + ReLU over x (b, n, c): `groups` groups of c / groups contiguous channels, each normalised per cloud over
+ * its n points and channels with the biased variance (two-pass moments), then y = max(gamma xhat + beta, 0).  mean / rstd
+ * (b, groups) receive the statistics.  Backward through the ReLU mask y > 0: dx, and dgamma / dbeta summed over the
+ * clouds in ascending order through pcops_group_norm_relu_workspace_bytes(b, c) bytes of workspace.
+ * groups must divide c (PCOPS_ERR_BAD_ARGUMENT); c / groups <= 256 and c <= 4096 (PCOPS_ERR_UNSUPPORTED). */
+unsigned long long pcops_group_norm_relu_workspace_bytes(int b, int c);
+int pcops_group_norm_relu_fwd(int b, int n, int c, int groups, float eps, const float *x, const float *gamma,
+                              const float *beta, float *y, float *mean, float *rstd, pcops_stream_t stream);
+int pcops_group_norm_relu_bwd(int b, int n, int c, int groups, const float *dout, const float *x, const float *y,
+                              const float *gamma, const float *mean, const float *rstd, float *dx, float *dgamma,
+                              float *dbeta, void *workspace, pcops_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -114,6 +114,14 @@ SIGNATURES = {
     "pcops_fc_bn_bwd": ([_I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P], True),
     "pcops_softmax_ce": ([_I, _I, _P, _P, _F, _P, _P], True),
     "pcops_three_nn_weights": ([_I, _I, _P, _P], True),
+    # SpiderConv (csrc/spider.hip)
+    "pcops_spider_taylor_fwd": ([_LL, _I, _P, _P, _P, _P], True),
+    "pcops_spider_taylor_bwd": ([_LL, _I, _P, _P, _P, _P, _P], True),
+    "pcops_spider_conv_fwd": ([_I] * 6 + [_P] * 6, True),
+    "pcops_spider_conv_wgrad": ([_I] * 6 + [_P] * 7, True),
+    "pcops_spider_conv_dgrad": ([_I] * 6 + [_P] * 7, True),
+    "pcops_group_norm_relu_fwd": ([_I, _I, _I, _I, _F] + [_P] * 6, True),
+    "pcops_group_norm_relu_bwd": ([_I, _I, _I, _I] + [_P] * 10, True),
 }
 PLAIN = {
     "pcops_strerror": ([_I], C.c_char_p),
@@ -157,6 +165,9 @@ PLAIN = {
     "pcops_get_option": ([_I], _I),
     "pcops_set_deterministic": ([_I], None),
     "pcops_get_deterministic": ([], _I),
+    "pcops_spider_taylor_bwd_workspace_bytes": ([_LL, _I], _U64),
+    "pcops_spider_conv_wgrad_workspace_bytes": ([_I] * 6, _U64),
+    "pcops_group_norm_relu_workspace_bytes": ([_I, _I], _U64),
 }
 
 

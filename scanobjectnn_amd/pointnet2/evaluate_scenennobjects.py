@@ -55,11 +55,28 @@ def accuracy_summary(pred, labels, num_classes=NUM_CLASSES):
     return float((pred == labels).mean()), float(np.nanmean(per_class)), per_class
 
 
+def split_output(out):
+    """a classifier's output -> (logits, end_points): (logits, end_points) of the PointNet / PointNet++ / DGCNN models,
+    or the bare logits of SpiderCNN (SpiderCNN/models/spidercnn_cls_xyz.py:71), whose end points are None"""
+    if isinstance(out, (tuple, list)):
+        return out[0], out[1]
+    return out, None
+
+
+def model_loss(mod, logits, labels, end_points):
+    """the model's get_loss: (pred, label, end_points), or (pred, label) for a bare-logits model
+    (SpiderCNN/train.py:142-143)"""
+    if end_points is None:
+        return mod.get_loss(logits, labels)
+    return mod.get_loss(logits, labels, end_points)
+
+
 @torch.no_grad()
 def eval_one_epoch(net, data, labels, batch_size, num_votes=1, device="cuda:0", num_classes=NUM_CLASSES, loss_fn=None):
     """net: graph.Model of a classifier get_model; data (K,N,3), labels (K,).  Whole batches only (like the
     reference: num_batches = K // BATCH_SIZE).  loss_fn(logits, labels, end_points) -> scalar: the reference's
-    per-vote loss, averaged over the votes and weighted by the batch size (`:187,198`) -> "mean_loss"."""
+    per-vote loss, averaged over the votes and weighted by the batch size (`:187,198`) -> "mean_loss".  A model that
+    returns bare logits passes end_points = None."""
     preds, seen = [], []
     labels = _host(labels)
     loss_sum = 0.0
@@ -67,13 +84,13 @@ def eval_one_epoch(net, data, labels, batch_size, num_votes=1, device="cuda:0", 
         pts = torch.as_tensor(data[b * batch_size:(b + 1) * batch_size], dtype=torch.float32, device=device)
         lab_b = np.asarray(labels[b * batch_size:(b + 1) * batch_size])
         if loss_fn is None:
-            logits = vote_logits(lambda p: net(p.contiguous(), is_training=False)[0], pts, num_votes)
+            logits = vote_logits(lambda p: split_output(net(p.contiguous(), is_training=False))[0], pts, num_votes)
         else:
             y = torch.as_tensor(lab_b.astype(np.int64), device=device)
             losses = []
 
             def predict(p):
-                out, end_points = net(p.contiguous(), is_training=False)
+                out, end_points = split_output(net(p.contiguous(), is_training=False))
                 losses.append(loss_fn(out, y, end_points))
                 return out
             logits = vote_logits(predict, pts, num_votes)
@@ -225,7 +242,7 @@ def evaluate(args):
         cur, lab = data_utils.get_current_data_h5(data, labels, args.num_point, rng=rng)  # :159
     lab = np.squeeze(lab)
     ev = eval_one_epoch(net, cur, lab, args.batch_size, num_votes=args.num_votes, device=dev,
-                        num_classes=args.num_class, loss_fn=lambda out, y, ep: mod.get_loss(out, y, ep))
+                        num_classes=args.num_class, loss_fn=lambda out, y, ep: model_loss(mod, out, y, ep))
     with open(os.path.join(args.dump_dir, "pred_label.txt"), "w") as fout:                 # :209
         for p, l in zip(ev["pred"], ev["label"]):
             fout.write("%s, %s\n" % (names[p], names[l]))

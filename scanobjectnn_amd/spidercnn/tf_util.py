@@ -1,6 +1,9 @@
 """SpiderCNN layers -- mirror of `SpiderCNN/utils/tf_util.py`: conv2d with group norm (:59-125), spiderConv (:127-236),
 topk_pool (:363-377), group_norm_for_conv (:407-429).  The neighbourhood front end (kNN + grouping) runs on the
-libpcops ops; the Taylor-kernel algebra is a handful of dense torch ops (no new kernels)."""
+libpcops ops.  spiderConv with group norm and ReLU runs on the SpiderConv kernels of libpcops (spider_ops.py);
+PCOPS_SPIDER_NATIVE=0 keeps the dense torch form below (the expanded operand + torch.addmm) as the A/B baseline."""
+import os
+
 import torch
 
 from ..graph import constant_initializer, get_variable, variable_scope, xavier_initializer
@@ -10,6 +13,11 @@ from ..pointnet2.tf_util import dropout, fully_connected  # noqa: F401  (tf.cont
 relu = torch.relu
 _TAYLOR = ('x', 'y', 'z', 'xyz', 'xy', 'yz', 'xz', 'xx', 'yy', 'zz', 'xxy', 'xyy', 'xxz', 'xzz', 'yyz', 'yzz',
            'xxx', 'yyy', 'zzz')
+
+
+def native_enabled():
+    """PCOPS_SPIDER_NATIVE=0: the dense torch form (the A/B baseline); read at every layer build"""
+    return os.environ.get("PCOPS_SPIDER_NATIVE", "1") != "0"
 
 
 def group_norm_for_conv(x, G=32, esp=1e-6, scope='gn'):
@@ -43,13 +51,31 @@ def conv2d(inputs, num_output_channels, kernel_size, scope, stride=(1, 1), paddi
         return activation_fn(out) if activation_fn is not None else out
 
 
+def _spider_native(feat, idx, delta, num_conv, taylor_channel, w, biases, G):
+    """the same variables, created in the same order, contracted by the SpiderConv kernels (spider_ops.py)"""
+    from . import spider_ops
+    b, n, c = feat.shape
+    k = idx.shape[2]
+    with variable_scope('conv'):
+        kernel = get_variable('weights', [1, k, c * taylor_channel, num_conv], xavier_initializer())
+        cbias = get_variable('biases', [num_conv], constant_initializer(0.0))
+        with variable_scope('gn'):
+            gamma = get_variable('gamma', [num_conv], constant_initializer(1.0))
+            beta = get_variable('beta', [num_conv], constant_initializer(0.0))
+    theta = torch.cat([w[name].reshape(1, taylor_channel) for name in _TAYLOR])
+    return spider_ops.spider_conv(feat, idx, delta, theta, biases.reshape(taylor_channel),
+                                  kernel.reshape(k * c * taylor_channel, num_conv), cbias, gamma, beta,
+                                  min(G, num_conv))
+
+
 def spiderConv(feat, idx, delta, num_conv, taylor_channel, gn=False, G=32, activation_fn=relu, scope='taylor'):
     """feat (B,N,C), idx (B,N,k) int32, delta (B,N,k,3) -> (B,N,num_conv): neighbour features weighted by
-    taylor_channel order-3 polynomials of the offset, then a [1,k] conv (:168-236)"""
+    taylor_channel order-3 polynomials of the offset, then a [1,k] conv (:168-236).  With group norm and ReLU (the
+    only form the classifier uses) on the native kernels unless PCOPS_SPIDER_NATIVE=0.  The kernels take 1 <= C <= 256,
+    1 <= k <= 64, taylor_channel = 5, num_conv % 16 == 0 up to 512 (spider_ops.supported); other shapes raise PcopsError
+    on the native route -- the torch form (PCOPS_SPIDER_NATIVE=0) takes any shape."""
+    native = gn and activation_fn is relu and native_enabled()
     with variable_scope(scope):
-        grouped = group_point(feat.contiguous(), idx)                       # (B,N,k,C)
-        b, n, k, c = grouped.shape
-        X, Y, Z = delta[..., 0:1], delta[..., 1:2], delta[..., 2:3]
         w = {}
         for name in _TAYLOR[:4]:
             w[name] = get_variable('weight_' + name, [1, 1, 1, taylor_channel], xavier_initializer())
@@ -58,6 +84,11 @@ def spiderConv(feat, idx, delta, num_conv, taylor_channel, gn=False, G=32, activ
         biases = get_variable('biases', [1, 1, 1, taylor_channel], constant_initializer(0.0))
         for name in _TAYLOR[7:]:
             w[name] = get_variable('weight_' + name, [1, 1, 1, taylor_channel], xavier_initializer())
+        if native:
+            return _spider_native(feat.contiguous(), idx, delta.contiguous(), num_conv, taylor_channel, w, biases, G)
+        grouped = group_point(feat.contiguous(), idx)                       # (B,N,k,C)
+        b, n, k, c = grouped.shape
+        X, Y, Z = delta[..., 0:1], delta[..., 1:2], delta[..., 2:3]
         g1 = w['x'] * X + w['y'] * Y + w['z'] * Z + w['xyz'] * X * Y * Z
         g2 = w['xy'] * X * Y + w['yz'] * Y * Z + w['xz'] * X * Z + biases
         g3 = w['xx'] * X * X + w['yy'] * Y * Y + w['zz'] * Z * Z
