@@ -67,6 +67,13 @@ int pcops_abi_version(void);
  *   PCOPS_OPT_BWD_FUSED_GRAM_WGRAD     0 (default) / 1: pcops_mlp_bwd_fused_gw* take shapes (pcops_mlp_bwd_fused_gw_groups > 0);
  *                                      measured -4 % .. +1 % time against the direct form (its vector arg-row term costs what
  *                                      the halved matrix work saves); superseded by value 2 of the option above
+ *   PCOPS_OPT_SCATTER_QFORM            0 / 1 (default): the chunked feature-gradient walk of pcops_sa_scatter_bwd(_rows) takes its
+ *                                      Q form -- Y is a function of fwd_Q, fwd_Wxyz, fwd_bias and the offsets, so its rows are
+ *                                      not read (see there); 0 keeps the walk that reads Y
+ *   PCOPS_OPT_XYZ_STATS_MOMENTS        0 (default) / 1: pcops_sa_gather_fwd(_rows) of a layer that is arithmetic in the offsets
+ *                                      (no Q, no Ctr, Y == NULL, moments and stats_partial wanted) takes its statistics from
+ *                                      the nine offset moments instead of summing the b m s x c outputs it never stores
+ *                                      (opt-in: the statistics agree with float64 to 3e-7, but not bit for bit with the summed form)
  * pcops_set_option returns the PREVIOUS value (>= 0) or PCOPS_ERR_BAD_ARGUMENT.  The environment variables of rounds 3-4
  * (PCOPS_GEMM_BF3, PCOPS_WGRAD_BF3, PCOPS_BWD_FUSED_DX3, PCOPS_KNN_F16; round 6: PCOPS_DGRAD_BF3, PCOPS_BWD_FUSED_GW) only seed the initial values (test overrides). */
 typedef enum pcops_option {
@@ -76,7 +83,9 @@ typedef enum pcops_option {
     PCOPS_OPT_KNN_F16_PREFILTER = 4,
     PCOPS_OPT_DGRAD_SPLIT_BF16 = 5,
     PCOPS_OPT_BWD_FUSED_GRAM_WGRAD = 6,
-    PCOPS_OPT_COUNT = 7
+    PCOPS_OPT_SCATTER_QFORM = 7,
+    PCOPS_OPT_XYZ_STATS_MOMENTS = 8,
+    PCOPS_OPT_COUNT = 9
 } pcops_option;
 int pcops_set_option(int option, int value);
 int pcops_get_option(int option);
@@ -85,7 +94,9 @@ int pcops_get_option(int option);
 int pcops_last_launch_pipe(void);
 /* ... and the variant it took, as up to n ints into out; returns the number of fields (5) or PCOPS_ERR_NULL_POINTER:
  *   [0] path   0 none yet, 1 tiled fp32 kernel, 2 wave-stream kernel, 3 one-pass backward (pcops_mlp_bwd_fused*),
- *              4 / 5 / 6 / 7 weight gradient: split-operand / producer-consumer / wave-stream / legacy split-K kernel
+ *              4 / 5 / 6 / 7 weight gradient: split-operand / producer-consumer / wave-stream / legacy split-K kernel,
+ *              8 / 9 pcops_sa_scatter_bwd(_rows) over the inverse index: chunked walk with atomics ([1] = 1: its Q form,
+ *              [2] sorted rows per chunk, [4] = 4 compacted rows) / owner walk (deterministic mode)
  *   [1] split  1 when the operands are split into bf16 pieces (the one-pass backward: 1 its dX half, 2 both halves)
  *   [2] bn     output columns per block (64, 96, 128; the weight gradients: columns of their dW tile; 0 tiled)
  *   [3] wst    1 when the weights are streamed rather than resident in LDS
@@ -518,7 +529,11 @@ int pcops_mlp_wgrad_xyz(long long M, int K, int N, const float *off4, const floa
  * (dx, dy, dz, 0) per grouped row, float [b*m*s][4]: when the layer has NO Q / Ctr term it is arithmetic in those
  * three numbers, and the pcops_mlp_*_xyz entry points rebuild it on the fly instead of reading a (b,m,s,c) tensor.
  * moments (may be NULL; needs the coordinate term): float [pcops_sa_gather_stats_rows(b*m)][9] partial sums of
- * (dx dx, dx dy, dx dz, dy dy, dy dz, dz dz, dx, dy, dz) -- see pcops_mlp_gemm_dgrad_xyz. */
+ * (dx dx, dx dy, dx dz, dy dy, dy dz, dz dz, dx, dy, dz) -- see pcops_mlp_gemm_dgrad_xyz.
+ * With Q, Ctr and Y all NULL and moments given, y_c = w_c . o + bias_c, and the statistics are taken from the moments
+ * (M1 = sum o, M2 = sum o o^T, R rows):  sum (y_c - pv_c) = w_c . M1 + R (bias_c - pv_c),  sum (y_c - pv_c)^2 =
+ * w_c^T M2 w_c + 2 (bias_c - pv_c) w_c . M1 + R (bias_c - pv_c)^2, formed in double and written as row 0 of stats_partial,
+ * the other rows zero (PCOPS_OPT_XYZ_STATS_MOMENTS = 1; the default 0 sums over the rebuilt outputs as in every other form). */
 int pcops_sa_gather_stats_rows(long long groups);
 /* rows of stats_partial a pcops_sa_gather_fwd(_rows) call of this form writes: the Q + Ctr form with a stored Y runs on
  * the 64-channel-slice kernel of csrc/edgeconv.hip (one row per 64 groups) when the shape fits; everything else writes
@@ -538,6 +553,11 @@ int pcops_sa_gather_fwd(int b, int n, int m, int s, int c, const float *Q, const
  * the forward had no Q / Ctr term (Y = (xyz[idx]-new_xyz) Wxyz + bias) the streaming kernel REBUILDS Y in the
  * forward's own operation order instead of reading it (bit-identical, one (b,m,s,c) tensor less to stream); Y may
  * be NULL only in that case with dQ == NULL.
+ * With fwd_Q != NULL and fwd_Ctr == NULL the chunked walk below (G materialised, workspace given, no dCtr, not
+ * deterministic) uses them too: Y[r] = fwd_Q[idx] + offsets fwd_Wxyz + fwd_bias, so the sums over a point's rows are
+ *     dQ[i] = p.sum G + q.(W_i (Q[i] + bias) + Wxyz^T O_i) + W_i t,   W_i = sum of the row weights, O_i = sum weight * offset
+ * and dWxyz / dbias follow from the same sums and nine global offset moments -- the rows of Y are not read (they must
+ * still be the forward's: PCOPS_OPT_SCATTER_QFORM = 0 reads them, and both forms agree to fp32 summation order).
  * workspace (may be NULL): pcops_sa_scatter_workspace_bytes(b,n,m,s) bytes, 16-byte aligned; with it the feature
  * gradient is computed as a GATHER over a per-cloud inverse index (counting sort of idx) -- one wave per source
  * point, no float atomics; without it (or when dCtr / the pooled form is requested) dQ is accumulated with atomics

@@ -286,6 +286,8 @@ def check(t, dtype, name, ndim=None):
 
 OPT_GEMM_SPLIT_BF16, OPT_WGRAD_SPLIT_BF16, OPT_BWD_FUSED_DX_SPLIT_BF16, OPT_KNN_F16_PREFILTER = 1, 2, 3, 4
 OPT_DGRAD_SPLIT_BF16, OPT_BWD_FUSED_GRAM_WGRAD = 5, 6            # round 6
+OPT_SCATTER_QFORM = 7                                            # pcops_sa_scatter_bwd(_rows): Q form of the chunked walk
+OPT_XYZ_STATS_MOMENTS = 8                                        # pcops_sa_gather_fwd(_rows): arithmetic first layer's statistics
 
 
 def set_option(option, value):

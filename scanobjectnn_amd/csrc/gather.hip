@@ -274,6 +274,97 @@ __global__ __launch_bounds__(256) void sa_gather_fwd_kernel(long long G, int n, 
     }
 }
 
+// A first layer that is ARITHMETIC in the offsets (no Q, no Ctr, Y not stored: y_c = w_c . o + b_c) needs no pass over its
+// b m S x C outputs for the batch statistics: with M1 = sum wt o, M2 = sum wt o o^T and R = sum wt (the uncompacted row count)
+//   sum wt (y_c - pv_c)   = w_c . M1 + R (b_c - pv_c)
+//   sum wt (y_c - pv_c)^2 = w_c^T M2 w_c + 2 (b_c - pv_c) w_c . M1 + R (b_c - pv_c)^2
+// sa_gather_offsets_kernel is the staging phase of sa_gather_fwd_kernel on its own (same rows per thread, same order of the
+// sums: off4 and the moment partials come out bit-identical), xyz_stats_from_moments_kernel adds the partials in double,
+// forms the two sums per channel in double and writes them as row 0 of stats_partial, the other rows zero.
+__global__ __launch_bounds__(256) void sa_gather_offsets_kernel(long long G, int n, int m, int S,
+                                                                const float *__restrict__ xyz,
+                                                                const float *__restrict__ new_xyz,
+                                                                const int *__restrict__ idx, float *__restrict__ off4,
+                                                                float *__restrict__ moments, int groups_per_block,
+                                                                const RowBlock *__restrict__ blocks,
+                                                                const int *__restrict__ bstart) {
+    __shared__ float mm[9 * 256];
+    const long long g0 = (long long)blockIdx.x * groups_per_block;
+    const long long g1 = min(G, g0 + groups_per_block);
+    const int gch = S >= 1024 ? 1 : 1024 / S;                         // groups per chunk, as the full kernel stages them
+    float mo[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};      // offset moments: xx xy xz yy yz zz | x y z
+    for (long long gb = g0; gb < g1; gb += gch) {
+        const long long ge = min(g1, gb + gch);
+        const int nrows = (int)(ge - gb) * S;
+        for (int t = threadIdx.x; t < nrows; t += 256) {
+            const long long r = gb * S + t;
+            const long long g = gb + t / S;
+            const long long b = g / m;
+            const int i = idx[r];
+            const float *px = xyz + (b * n + i) * 3;
+            const float dx = px[0] - new_xyz[g * 3 + 0], dy = px[1] - new_xyz[g * 3 + 1], dz = px[2] - new_xyz[g * 3 + 2];
+            long long ro = r;                 // output row
+            float wt = 1.f;                   // weight of the row in the sums
+            if (blocks) {
+                const int sg = t % S, b0 = bstart[g];
+                if (sg >= (bstart[g + 1] - b0) * kBlk) continue;
+                ro = (long long)b0 * kBlk + sg;
+                if (sg == 0) wt = blocks[b0].w;
+            }
+            if (off4) *reinterpret_cast<float4 *>(off4 + ro * 4) = make_float4(dx, dy, dz, 0.f);
+            const float wx = wt * dx, wy = wt * dy, wz = wt * dz;
+            mo[0] = fmaf(wx, dx, mo[0]); mo[1] = fmaf(wx, dy, mo[1]); mo[2] = fmaf(wx, dz, mo[2]);
+            mo[3] = fmaf(wy, dy, mo[3]); mo[4] = fmaf(wy, dz, mo[4]); mo[5] = fmaf(wz, dz, mo[5]);
+            mo[6] += wx; mo[7] += wy; mo[8] += wz;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 9; ++k) mm[k * 256 + threadIdx.x] = mo[k];
+    __syncthreads();
+    if (threadIdx.x < 9) {
+        float t = 0.f;
+        for (int j = 0; j < 256; ++j) t += mm[threadIdx.x * 256 + j];
+        moments[(long long)blockIdx.x * 9 + threadIdx.x] = t;
+    }
+}
+
+// stats [P][2][C]: row 0 = the two shifted sums from the P moment partials (workgroup 0), rows 1 .. P-1 = 0 (all workgroups)
+__global__ __launch_bounds__(256) void xyz_stats_from_moments_kernel(int P, int C, double R, const float *__restrict__ moments,
+                                                                     const float *__restrict__ Wxyz,
+                                                                     const float *__restrict__ bias,
+                                                                     const float *__restrict__ pivot,
+                                                                     float *__restrict__ stats) {
+    const long long rest = (long long)(P - 1) * 2 * C;
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < rest; e += (long long)gridDim.x * 256)
+        stats[2 * C + e] = 0.f;
+    if (blockIdx.x != 0) return;
+    __shared__ double sm[9][256];
+    double mo[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    for (int p = threadIdx.x; p < P; p += 256)
+#pragma unroll
+        for (int k = 0; k < 9; ++k) mo[k] += (double)moments[(long long)p * 9 + k];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) sm[k][threadIdx.x] = mo[k];
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (threadIdx.x < o)
+#pragma unroll
+            for (int k = 0; k < 9; ++k) sm[k][threadIdx.x] += sm[k][threadIdx.x + o];
+        __syncthreads();
+    }
+    const double xx = sm[0][0], xy = sm[1][0], xz = sm[2][0], yy = sm[3][0], yz = sm[4][0], zz = sm[5][0];
+    const double mx = sm[6][0], my = sm[7][0], mz = sm[8][0];
+    for (int c = threadIdx.x; c < C; c += 256) {
+        const double w0 = Wxyz[c], w1 = Wxyz[C + c], w2 = Wxyz[2 * C + c];
+        const double d = (bias ? (double)bias[c] : 0.0) - (pivot ? (double)pivot[c] : 0.0);
+        const double wm1 = w0 * mx + w1 * my + w2 * mz;
+        const double wm2w = w0 * (w0 * xx + w1 * xy + w2 * xz) + w1 * (w0 * xy + w1 * yy + w2 * yz) +
+                            w2 * (w0 * xz + w1 * yz + w2 * zz);
+        stats[c] = (float)(wm1 + R * d);
+        stats[C + c] = (float)(wm2w + 2.0 * d * wm1 + R * d * d);
+    }
+}
+
 // backward.  One lane per CHANNEL (a wave covers 64 consecutive floats of one row, so every atomic instruction is
 // two full cache lines).  Rows that repeat the group's first index -- the padding ball query appends when fewer
 // than S points are in range -- are summed in registers and leave as ONE atomic per channel, which removes the
@@ -687,6 +778,7 @@ struct CsrArgs {
     const RowBlock *blocks;      // compacted rows: see sa_csr_build_kernel; the first row of a block carries a weight
     const int *bstart;
     const int *start;            // [b][n+1] list boundaries (owner kernel)
+    const float *fq, *fwxyz, *fbias;   // Q form (sa_scatter_csr_q_kernel): the forward's Q (b,n,C), Wxyz (3,C) / bias (C) or NULL
 };
 
 // YONLY: the pooled form -- dY = q.Y + t everywhere plus p.gpool at the arg-max rows, which the streaming
@@ -803,6 +895,229 @@ __global__ __launch_bounds__(256) void sa_scatter_csr_kernel(CsrArgs a) {
                     float v = aw[i][e];
 #pragma unroll
                     for (int off = 32; off >= LPR; off >>= 1) v += __shfl_xor(v, off, 64);
+                    if (rsub == 0) red[wave][i][quad * 4 + e] = v;
+                }
+            __syncthreads();
+            for (int e = tid; e < 4 * 4 * LPR; e += 256) {
+                const int i = e / (4 * LPR), c = e % (4 * LPR);
+                a.wpart[((long long)blockIdx.x * 4 + i) * C + cb + c] =
+                    red[0][i][c] + red[1][i][c] + red[2][i][c] + red[3][i][c];
+            }
+            __syncthreads();
+        }
+    }
+}
+
+// Q FORM of the chunked walk: the rows of Y are never read.  The forward made Y[r] = Q[i_r] + Wxyz^T o_r + bias with
+// o_r = xyz[i_r] - new_xyz[g_r], so the sum of d[r] = p.G[r] + wt_r (q.Y[r] + t) over the rows of a source point i is
+//   dQ[i]      = p.sum G[r] + q.(W_i (Q[i] + bias) + Wxyz^T O_i) + W_i t            W_i = sum wt_r,  O_i = sum wt_r o_r
+//   dbias      = sum_i dQ[i]
+//   dWxyz[a,:] = p.sum_r o_r[a] G[r] + q.(sum_i O_i[a] Q[i] + (M2 Wxyz)[a,:] + M1[a] bias) + M1[a] t
+//                M2 = sum wt_r o_r o_r^T,  M1 = sum wt_r o_r = sum_i O_i
+// Every line is linear in the rows, so it holds just as well for the PIECE of a list that one lane set walks: a piece
+// flushes its share of dQ[i] with the same atomics as the Y form.  Per row the kernel reads the order entry and one quad
+// of G (+ the block record where rows are compacted, six coordinate words where the layer has a coordinate term); Q[i]
+// is read once per (point, piece), requested together with the G row that opens the piece.  M2 / M1 cost nine scalars
+// per lane and enter dWxyz once per wave.
+// The walk is software-pipelined: the order entries of batch k+1 are requested before batch k is consumed, so the
+// dependent chain of a batch is the rows' own latency, not order entry -> rows -> block record -> coordinates.
+template <int LPR, int CH>
+// Registers: the batch in flight (4 rows of G, up to 4 of Q, records, coordinates) + the running sums need ~165 VGPRs, i.e.
+// three waves per SIMD -- the launcher sizes the grid for that (kCsrQGrid).
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void sa_scatter_csr_q_kernel(CsrArgs a) {
+    constexpr int RW = 64 / LPR, RUN = CH / RW, U = RUN < 4 ? RUN : 4;   // RUN: sorted rows per lane set and chunk
+    __shared__ float red[4][4][256];
+    // what only a flush needs (q, t, bias, Wxyz of the lane's four channels) waits in LDS: 24 registers less in the walk
+    __shared__ __attribute__((aligned(16))) float cst[6][256];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // uniform: the chunk bookkeeping and every base pointer stay scalar
+    const int rsub = lane / LPR, quad = lane % LPR;
+    const int n = a.n, m = a.m, S = a.S, C = a.C, mS = m * S;
+    const int nch = (mS + CH - 1) / CH;
+    const int nchunks = a.b * nch, wstride = (int)gridDim.x * 4;      // (the launcher keeps b m S below 2^31)
+    const bool has_o = a.xyz != nullptr, has_w = a.wpart != nullptr;
+    // scalar base + 32-bit BYTE offset of the lane: one VGPR of address per load instead of a 64-bit pair
+    auto at = [](auto *base, unsigned bytes) {
+        typedef std::remove_pointer_t<decltype(base)> T;
+        typedef std::conditional_t<std::is_const<T>::value, const char, char> Ch;
+        return reinterpret_cast<T *>(reinterpret_cast<Ch *>(base) + bytes);
+    };
+    auto ld4 = [](const float *ptr, float *v) {
+        const float4 x = *reinterpret_cast<const float4 *>(ptr);
+        v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w;
+    };
+    for (int cb = 0; cb < C; cb += 4 * LPR) {
+        const int c0 = cb + quad * 4;
+        float pv[4];
+        ld4(a.p + c0, pv);
+        __syncthreads();                 // (C > 256: the previous block of channels is done with cst)
+        for (int e = tid; e < 6 * 4 * LPR; e += 256) {           // rows: q | t | bias | Wxyz 0..2 of channels cb .. cb + 4 LPR
+            const int r = e / (4 * LPR), c = e % (4 * LPR);
+            const float *src = r == 0 ? a.q : r == 1 ? a.t : r == 2 ? a.fbias : (a.fwxyz ? a.fwxyz + (r - 3) * C : nullptr);
+            cst[r][c] = src ? src[cb + c] : 0.f;
+        }
+        __syncthreads();
+        float aw[4][4];                  // this lane's share of dWxyz rows 0..2 (without the M2 / M1 terms) and of dbias
+#pragma unroll
+        for (int i = 0; i < 4; ++i) aw[i][0] = aw[i][1] = aw[i][2] = aw[i][3] = 0.f;
+        float m2[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, m1[3] = {0.f, 0.f, 0.f};     // xx xy xz yy yz zz | x y z
+        for (int ch = (int)blockIdx.x * 4 + wave; ch < nchunks; ch += wstride) {
+            const int b = ch / nch;
+            int rowoff = b * mS, nrows = mS;
+            if (a.blocks) {
+                rowoff = __builtin_amdgcn_readfirstlane(a.bstart[b * m] * kBlk);
+                nrows = __builtin_amdgcn_readfirstlane(a.bstart[(b + 1) * m] * kBlk) - rowoff;
+            }
+            const int kb = (ch - b * nch) * CH, ke = min(nrows, kb + CH);
+            if (kb >= nrows) continue;                   // wave-uniform
+            // scalar bases of the cloud + 32-bit lane offsets (the launcher checks that a cloud's G rows and Q fit 2^31 bytes)
+            const int2 *ob = a.order + rowoff;
+            const float *gb = a.Gm + (long long)rowoff * C;
+            const float *qb = a.fq + (long long)b * n * C;
+            float *dqb = a.dQ + (long long)b * n * C;
+            const float *xb = has_o ? a.xyz + (long long)b * n * 3 : nullptr;
+            const RowBlock *bb = a.blocks ? a.blocks + rowoff / kBlk : nullptr;
+            int cur = -1;
+            float sg[4] = {0.f, 0.f, 0.f, 0.f}, W = 0.f, O[3] = {0.f, 0.f, 0.f}, cqv[4] = {0.f, 0.f, 0.f, 0.f};
+            auto flush = [&]() {         // the piece of point `cur` is complete: sg = p.sum G, W, O, cqv = Q[cur]
+                float dq[4], qv[4], tv[4], bv[4], wv[3][4];
+                ld4(&cst[0][quad * 4], qv); ld4(&cst[1][quad * 4], tv); ld4(&cst[2][quad * 4], bv);
+                ld4(&cst[3][quad * 4], wv[0]); ld4(&cst[4][quad * 4], wv[1]); ld4(&cst[5][quad * 4], wv[2]);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float wo = fmaf(O[2], wv[2][e], fmaf(O[1], wv[1][e], O[0] * wv[0][e]));
+                    dq[e] = sg[e] + fmaf(qv[e], fmaf(W, cqv[e] + bv[e], wo), W * tv[e]);
+                }
+                float *dst = at(dqb, (unsigned)(cur * C + c0) * 4u);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) atomicAdd(dst + e, dq[e]);
+                if (has_w) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) aw[3][e] += dq[e];
+                    if (has_o) {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            const float qq = qv[e] * cqv[e];
+                            aw[0][e] = fmaf(O[0], qq, aw[0][e]);
+                            aw[1][e] = fmaf(O[1], qq, aw[1][e]);
+                            aw[2][e] = fmaf(O[2], qq, aw[2][e]);
+                        }
+                        m1[0] += O[0]; m1[1] += O[1]; m1[2] += O[2];
+                    }
+                }
+            };
+            // each row-lane set owns a CONTIGUOUS run of RUN sorted rows, as in the Y form
+            const int ks = kb + rsub * RUN, kse = min(ke, ks + RUN);
+            int2 on[U];                  // order entries of the NEXT batch (positions past the run's end read entry kb)
+#pragma unroll
+            for (int u = 0; u < U; ++u) on[u] = *at(ob, (unsigned)(ks + u < kse ? ks + u : kb) * 8u);
+            int prev = -1;               // point of the row before the batch: Q is requested where the point changes
+#pragma unroll 1
+            for (int k0 = 0; k0 < RUN; k0 += U) {
+                if (kb + k0 >= ke) break;               // wave-uniform: nothing left for any lane set
+                int ee[U], ii[U], rg[U], w0 = 0;         // w0: bit u set where row u opens its 16-row block
+                float rw[U], px[U][3], cx[U][3];
+                float4 gg[U], qq[U];
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    ee[u] = on[u].x;
+                    ii[u] = on[u].y;
+                    w0 |= (ee[u] % kBlk == 0 ? 1 : 0) << u;
+                }
+                // everything that depends on the order entries alone; the narrow records first, so that the wait for
+                // them (the centres' addresses) leaves the G rows in flight
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    rg[u] = (int)((unsigned)ee[u] / (unsigned)S) + b * m;          // group of the row
+                    rw[u] = 1.f;
+                    if (a.blocks) {
+                        const RowBlock *rb = at(bb, (unsigned)ee[u] / kBlk * 16u);
+                        rg[u] = rb->g;
+                        rw[u] = rb->w;
+                    }
+                    if (has_o) {
+                        const float *pp = at(xb, (unsigned)ii[u] * 12u);
+                        px[u][0] = pp[0]; px[u][1] = pp[1]; px[u][2] = pp[2];
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    gg[u] = *reinterpret_cast<const float4 *>(at(gb, (unsigned)(ee[u] * C + c0) * 4u));
+                    qq[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+                    if (ii[u] != (u ? ii[u - 1] : prev) && ks + k0 + u < kse)
+                        qq[u] = *reinterpret_cast<const float4 *>(at(qb, (unsigned)(ii[u] * C + c0) * 4u));
+                }
+                prev = ii[U - 1];
+#pragma unroll
+                for (int u = 0; u < U; ++u) {            // the next batch's order entries
+                    const int k = ks + k0 + U + u;
+                    on[u] = *at(ob, (unsigned)(k < kse ? k : kb) * 8u);
+                }
+                if (has_o) {
+#pragma unroll
+                    for (int u = 0; u < U; ++u) {
+                        const float *cc = at(a.new_xyz, (unsigned)rg[u] * 12u);
+                        cx[u][0] = cc[0]; cx[u][1] = cc[1]; cx[u][2] = cc[2];
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    if (ks + k0 + u >= kse) continue;
+                    const int i = ii[u];
+                    if (i != cur) {
+                        if (cur >= 0) flush();
+                        cur = i;
+                        cqv[0] = qq[u].x; cqv[1] = qq[u].y; cqv[2] = qq[u].z; cqv[3] = qq[u].w;
+                        sg[0] = sg[1] = sg[2] = sg[3] = W = O[0] = O[1] = O[2] = 0.f;
+                    }
+                    const float wt = (w0 >> u & 1) ? rw[u] : 1.f;       // only a block's row 0 is weighted (uncompacted: 1)
+                    const float pg[4] = {pv[0] * gg[u].x, pv[1] * gg[u].y, pv[2] * gg[u].z, pv[3] * gg[u].w};
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) sg[e] += pg[e];
+                    W += wt;
+                    if (has_o) {
+                        const float o[3] = {px[u][0] - cx[u][0], px[u][1] - cx[u][1], px[u][2] - cx[u][2]};
+                        const float wo[3] = {wt * o[0], wt * o[1], wt * o[2]};
+                        O[0] += wo[0]; O[1] += wo[1]; O[2] += wo[2];
+                        if (has_w) {
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) {
+                                aw[0][e] = fmaf(o[0], pg[e], aw[0][e]);
+                                aw[1][e] = fmaf(o[1], pg[e], aw[1][e]);
+                                aw[2][e] = fmaf(o[2], pg[e], aw[2][e]);
+                            }
+                            m2[0] = fmaf(wo[0], o[0], m2[0]); m2[1] = fmaf(wo[0], o[1], m2[1]); m2[2] = fmaf(wo[0], o[2], m2[2]);
+                            m2[3] = fmaf(wo[1], o[1], m2[3]); m2[4] = fmaf(wo[1], o[2], m2[4]); m2[5] = fmaf(wo[2], o[2], m2[5]);
+                        }
+                    }
+                }
+            }
+            if (cur >= 0) flush();
+        }
+        if (a.wpart) {
+            // the wave's M2 / M1 (every quad lane of a lane set holds the same values: sum over the lane sets)
+#pragma unroll
+            for (int off = 32; off >= LPR; off >>= 1) {
+#pragma unroll
+                for (int k = 0; k < 6; ++k) m2[k] += __shfl_xor(m2[k], off, 64);
+#pragma unroll
+                for (int k = 0; k < 3; ++k) m1[k] += __shfl_xor(m1[k], off, 64);
+            }
+            const float mr[3][3] = {{m2[0], m2[1], m2[2]}, {m2[1], m2[3], m2[4]}, {m2[2], m2[4], m2[5]}};
+            float qv[4], tv[4], bv[4], wv[3][4];
+            ld4(&cst[0][quad * 4], qv); ld4(&cst[1][quad * 4], tv); ld4(&cst[2][quad * 4], bv);
+            ld4(&cst[3][quad * 4], wv[0]); ld4(&cst[4][quad * 4], wv[1]); ld4(&cst[5][quad * 4], wv[2]);
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    float v = aw[i][e];
+#pragma unroll
+                    for (int off = 32; off >= LPR; off >>= 1) v += __shfl_xor(v, off, 64);
+                    if (i < 3) {
+                        const float mw = fmaf(mr[i][2], wv[2][e], fmaf(mr[i][1], wv[1][e], mr[i][0] * wv[0][e]));
+                        v += fmaf(qv[e], fmaf(m1[i], bv[e], mw), m1[i] * tv[e]);
+                    }
                     if (rsub == 0) red[wave][i][quad * 4 + e] = v;
                 }
             __syncthreads();
@@ -1028,6 +1343,7 @@ __global__ __launch_bounds__(256) void cloud_bias_reduce_kernel(int ppg, int C, 
 }
 
 constexpr int kCsrGrid = 1024;      // persistent workgroups of the gather pass (= rows of its wpart)
+constexpr int kCsrQGrid = 768;      // ... of its Q form: 3 waves per SIMD x 4 SIMDs x 256 CUs / 4 waves per workgroup
 
 // gradients of an ARITHMETIC first layer from a handful of sums (see pcops_mlp_gemm_dgrad_xyz in pcops.h):
 //   dWxyz[i][c] = p[c] A[i][c] + q[c] B[i][c] + t[c] S[i],   B = M33 Wxyz + S^T b,   dbias[c] = p sumG + q sumY + t rows
@@ -1684,6 +2000,18 @@ int pcops_sa_gather_fwd_rows(int b, int n, int m, int s, int c, const float *Q, 
         // pcops_sa_gather_stats_rows(G): ABI version 4, pcops.h)
         return ec_gather_fwd(b, n, m, s, c, Q, c, Ctr, c, idx, Y, stats_partial, stat_pivot, as_stream(stream));
     }
+    if (!Y && !Q && !Ctr && Wxyz && moments && stats_partial && pcops_get_option(PCOPS_OPT_XYZ_STATS_MOMENTS) != 0) {
+        // arithmetic first layer, statistics only: its two sums per channel follow from the nine offset moments
+        const int P = pcops_sa_gather_stats_rows(G);
+        hipStream_t st = as_stream(stream);
+        hipLaunchKernelGGL(sa_gather_offsets_kernel, dim3(P), dim3(256), 0, st, G, n, m, s, xyz, new_xyz, idx, off4, moments,
+                           gather_groups_per_block(G), rows ? static_cast<const RowBlock *>(rows->blocks) : nullptr,
+                           rows ? rows->block_start : nullptr);
+        const unsigned zg = cdiv((long long)(P - 1) * 2 * c, 256 * 8);
+        hipLaunchKernelGGL(xyz_stats_from_moments_kernel, dim3(zg < 1u ? 1u : (zg > 1024u ? 1024u : zg)), dim3(256), 0, st, P, c,
+                           (double)G * s, moments, Wxyz, bias, stat_pivot, stats_partial);
+        return pcops_launch_status();
+    }
     const int rl = 256 / (c / 4);
     static const bool nt_on = [] { const char *e = getenv("PCOPS_NT_STORE"); return !(e && e[0] == '0'); }();   // kernel A/B only
     const size_t staged = (size_t)(s >= 1024 ? s : 1024) * 4;      // floats: (dx, dy, dz, index) per staged row
@@ -1802,8 +2130,10 @@ int pcops_sa_scatter_bwd_rows(int b, int n, int m, int s, int c, const float *G,
         hipLaunchKernelGGL(sa_csr_build_kernel, dim3(b), dim3(1024), blds, st, n, m * s, idx, order, start, m, s, rblocks,
                            rbstart, sorted);
         float *wp2 = split ? nullptr : wp;
-        CsrArgs a = {b, n, m, s, c, G, Y, p, q, t, xyz, new_xyz, sorted ? sorted : order, dQ, wp2, rblocks, rbstart, start};
+        CsrArgs a = {b, n, m, s, c, G, Y, p, q, t, xyz, new_xyz, sorted ? sorted : order, dQ, wp2, rblocks, rbstart, start,
+                     fwd_Q, fwd_Wxyz, fwd_bias};
         if (owner) {
+            pcops_note_plan(9, 0, 0, 0, rows ? 4 : 0);
             switch (lpr) {
                 case 8: hipLaunchKernelGGL(sa_scatter_owner_kernel<8>, dim3(kCsrGrid), dim3(256), 0, st, a); break;
                 case 16: hipLaunchKernelGGL(sa_scatter_owner_kernel<16>, dim3(kCsrGrid), dim3(256), 0, st, a); break;
@@ -1821,6 +2151,27 @@ int pcops_sa_scatter_bwd_rows(int b, int n, int m, int s, int c, const float *G,
             return rc;
         }
         const bool small = (long long)b * ((m * s + 63) / 64) < 4 * kCsrGrid;   // fewer 64-row chunks than waves
+        // Q form (sa_scatter_csr_q_kernel): Y = Q[idx] + offsets Wxyz + bias is a function of what the call was handed
+        // (its lane offsets are 32-bit: a cloud's rows of G and its Q stay below 2^31 bytes)
+        const bool qform = G && !split && fwd_Q && !fwd_Ctr && pcops_get_option(PCOPS_OPT_SCATTER_QFORM) != 0 &&
+                           (long long)m * s * c * 4 < (1ll << 31) && (long long)n * c * 4 < (1ll << 31) &&
+                           (long long)b * m * (s > 12 ? s : 12) < (1ll << 31);
+        pcops_note_plan(8, qform ? 1 : 0, small ? 16 : 64, 0, rows ? 4 : 0);
+        if (qform) {
+#define PCOPS_CSRQ_CASE(LPR_)                                                                                          \
+    case LPR_:                                                                                                         \
+        if (small) hipLaunchKernelGGL((sa_scatter_csr_q_kernel<LPR_, 16>), dim3(kCsrQGrid), dim3(256), 0, st, a);       \
+        else hipLaunchKernelGGL((sa_scatter_csr_q_kernel<LPR_, 64>), dim3(kCsrQGrid), dim3(256), 0, st, a);            \
+        break;
+            switch (lpr) {
+                PCOPS_CSRQ_CASE(8)
+                PCOPS_CSRQ_CASE(16)
+                PCOPS_CSRQ_CASE(32)
+                PCOPS_CSRQ_CASE(64)
+                default: return PCOPS_ERR_UNSUPPORTED;
+            }
+#undef PCOPS_CSRQ_CASE
+        } else {
 #define PCOPS_CSR_LAUNCH(LPR_, Y_, CH_)                                                                            \
     hipLaunchKernelGGL((sa_scatter_csr_kernel<LPR_, Y_, CH_>), dim3(kCsrGrid), dim3(256), 0, st, a)
 #define PCOPS_CSR_CASE(LPR_)                                             \
@@ -1842,11 +2193,13 @@ int pcops_sa_scatter_bwd_rows(int b, int n, int m, int s, int c, const float *G,
         }
 #undef PCOPS_CSR_LAUNCH
 #undef PCOPS_CSR_CASE
+        }
         int rc = pcops_launch_status();
         if (rc) return rc;
         if (wp2) {
-            if (dWxyz) hipLaunchKernelGGL(sum_rows_kernel, dim3(3 * c), dim3(256), 0, st, kCsrGrid, 4 * c, wp2, dWxyz);
-            if (dbias) hipLaunchKernelGGL(sum_rows_kernel, dim3(c), dim3(256), 0, st, kCsrGrid, 4 * c, wp2 + 3 * c, dbias);
+            const int wrows = qform ? kCsrQGrid : kCsrGrid;
+            if (dWxyz) hipLaunchKernelGGL(sum_rows_kernel, dim3(3 * c), dim3(256), 0, st, wrows, 4 * c, wp2, dWxyz);
+            if (dbias) hipLaunchKernelGGL(sum_rows_kernel, dim3(c), dim3(256), 0, st, wrows, 4 * c, wp2 + 3 * c, dbias);
             rc = pcops_launch_status();
         }
         return rc;

@@ -43,7 +43,8 @@ KEYS = [
     ("wgrad_pc_kernel<2, 2, 1, 7, false>", None, "pcops_mlp_wgrad(2097152, 128, 128, 'compacted')"),
     ("gemm_ws_kernel<4, 1, 4, 64, 8, 2, 2>", None, "pcops_mlp_gemm_dgrad_top(32768, 512)"),
     ("wgrad_pc_kernel<2, 4, 1, 8, false>", None, "pcops_mlp_gram(32768, 512)"),
-    ("sa_scatter_csr_kernel<32, false, 64>", None, "pcops_sa_scatter_bwd(256, 512, 128, 64, 128, 'compacted')"),
+    ("sa_scatter_csr_q_kernel<32, 64>", None, "pcops_sa_scatter_bwd(256, 512, 128, 64, 128, 'compacted')"),      # Q form (default)
+    ("sa_scatter_csr_kernel<32, false, 64>", None, "pcops_sa_scatter_bwd(256, 512, 128, 64, 128, 'compacted')"),  # PCOPS_SCATTER_QFORM=0
     ("gemm_ws_kernel<4, 1, 0, 64, 8, 2, 1>", 512 * 512, "pcops_mlp_gemm_fwd_pool(4194304, 64, 128, 32)"),
     ("bwd_fused_kernel<2, 4, false, false", None, "pcops_mlp_bwd_fused(4194304, 64, 128)"),            # round 3: one pass for ...
     ("bwd_fused_kernel<1, 2, true, false", None, "pcops_mlp_bwd_fused_xyz(4194304, 64, 64)"),
