@@ -741,7 +741,9 @@ int pcops_mlp_wgrad_xyz_rows(long long M, int K, int N, const float *off4, const
                              const pcops_rows_t *rows, pcops_stream_t stream);
 /* last layer of a max-pooled stack over compacted rows, pooling fused into the epilogue: ypart / ppart
  * [pcops_rows_max_blocks][N] receive, per 16-row block, the selected raw value (max for gamma >= 0, min otherwise)
- * and its row-in-group; pcops_mlp_pool_combine_rows picks per group -> out = relu(scale*ysel + shift), argmax, ysel */
+ * and its row-in-group; pcops_mlp_pool_combine_rows picks per group -> out = relu(scale*ysel + shift), argmax, ysel
+ * Y == NULL: the activation is not stored (its backward is the algebraic one, or there is none); the other outputs are
+ * bit for bit those of the storing call. */
 int pcops_mlp_gemm_fwd_pool_rows_supported(int M, int K, int N);
 int pcops_mlp_gemm_fwd_pool_rows(int M, int K, int N, const float *X, int ldx, const float *pro_scale,
                                  const float *pro_shift, const float *W, const float *bias, const float *gamma,
@@ -755,6 +757,37 @@ int pcops_mlp_pool_combine_rows(long long G, int C, const float *ypart, const un
 int pcops_mlp_bn_relu_maxpool_rows(long long G, int C, const float *Y, const float *scale, const float *shift,
                                    const pcops_rows_t *rows, float *out, unsigned char *argmax, float *ysel,
                                    pcops_stream_t stream);
+/* ---- the algebraic backward of a pooled top layer over compacted rows.  With the weight w_r on the first row of a group,
+ * dY_r = (p.G)_r + w_r (q.Y_r + t) and sum w_r = M (the uncompacted count); substituting Y = X W + b:
+ *   dX_r = w_r (X_r Mq + v) + (p.G)_r W^T                              Mq = W diag(q) W^T, v = W (q.b + t)
+ *   dW   = (X^T diag(w) X)(W diag(q)) + (X^T w)(q.b + t)^T + X^T (p.G)
+ *   db   = 1^T (p.G) + q.((X^T w) W + M b) + M t
+ * The weight enters the dense terms only: the arg-max row of a group is its first maximiser, counted once.
+ * pcops_mlp_pool_top_prep / _finish and the small products are the uncompacted ones (finish with M = the uncompacted
+ * count).  argmax is the row-in-group in compacted numbering (pcops_mlp_pool_combine_rows); the row of slot (g, a) is
+ * 16 block_start[g] + a; rowmap and the addend are indexed by the compacted row (slot = row: addend [M][Kp],
+ * addend_rows = M).  The sparse halves are built for MANY SMALL groups (W^T / a group's rows of X held in LDS);
+ * pcops_mlp_pool_top_wsparse_rows takes a scratch of pcops_mlp_pool_top_wsparse_rows_partial(Kp, N) floats in front of
+ * the row set.  pcops_mlp_gram_rows: gram = X^T diag(w) X, xsum = X^T w (partial as pcops_mlp_gram).
+ * pcops_mlp_pool_top_rows_supported is the ONE answer a caller asks for all four (S % 16 == 0, S <= 128, Kp = 64 / 128,
+ * N <= 256, the addend within the 32-bit offset of its bounds check).  Sums in a fixed order (deterministic). */
+int pcops_mlp_pool_top_rows_supported(int M, int Kp, int N, int S);
+unsigned long long pcops_mlp_pool_top_wsparse_rows_partial(int Kp, int N);
+int pcops_mlp_pool_top_addend_rows(int M, int Kp, int N, int S, const float *gout, const float *ysel,
+                                   const unsigned char *argmax, const float *pool_scale, const float *pool_shift,
+                                   const float *p, const float *Wt, float *addend, int *rowmap, const pcops_rows_t *rows,
+                                   pcops_stream_t stream);
+int pcops_mlp_gemm_dgrad_top_rows(int M, int Kp, const float *Yprev, const float *prev_scale, const float *prev_shift,
+                                  const float *Mq, const float *vconst, const float *addend, long long addend_rows,
+                                  const int *rowmap, float *Gprev, float *stats_partial, const pcops_rows_t *rows,
+                                  pcops_stream_t stream);
+int pcops_mlp_gram_rows(long long M, int Kp, const float *Yprev, int ldx, const float *a_scale, const float *a_shift,
+                        float *partial, float *gram, float *xsum, const pcops_rows_t *rows, pcops_stream_t stream);
+int pcops_mlp_pool_top_wsparse_rows(int M, int Kp, int N, int S, const float *gout, const float *ysel,
+                                    const unsigned char *argmax, const float *pool_scale, const float *pool_shift,
+                                    const float *p, const float *Yprev, const float *prev_scale, const float *prev_shift,
+                                    float *Ssp, float *cfsum, float *partial, const pcops_rows_t *rows,
+                                    pcops_stream_t stream);
 /* pcops_sa_gather_fwd / pcops_sa_scatter_bwd over compacted rows: Y, off4, G are (rows, c) / (rows, 4) in the
  * compacted order; idx stays the (b,m,s) tensor of the ball query */
 int pcops_sa_gather_fwd_rows(int b, int n, int m, int s, int c, const float *Q, const float *Ctr, const float *xyz,

@@ -61,6 +61,10 @@ SIGNATURES = {
     "pcops_mlp_gemm_dgrad_top": ([_I, _I] + [_P] * 6 + [_LL] + [_P] * 3, True),
     "pcops_mlp_gram": ([_LL, _I, _P, _I, _P, _P, _P, _P, _P], True),
     "pcops_mlp_pool_top_wsparse": ([_I, _I, _I, _I] + [_P] * 11, True),
+    "pcops_mlp_pool_top_addend_rows": ([_I, _I, _I, _I] + [_P] * 10, True),
+    "pcops_mlp_gemm_dgrad_top_rows": ([_I, _I] + [_P] * 6 + [_LL] + [_P] * 4, True),
+    "pcops_mlp_gram_rows": ([_LL, _I, _P, _I, _P, _P, _P, _P, _P, _P], True),
+    "pcops_mlp_pool_top_wsparse_rows": ([_I, _I, _I, _I] + [_P] * 13, True),
     "pcops_sa_gather_fwd": ([_I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P], True),
     "pcops_mlp_gemm_fwd_xyz": ([_I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P], True),
     "pcops_mlp_gemm_dgrad_xyz": ([_I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P], True),
@@ -158,6 +162,8 @@ PLAIN = {
     "pcops_scatter_rows_sorted_max_ndst": ([], _I),
     "pcops_scatter_rows_sorted_supported": ([_I, _I], _I),
     "pcops_mlp_pool_top_supported": ([_I, _I, _I, _I], _I),
+    "pcops_mlp_pool_top_rows_supported": ([_I, _I, _I, _I], _I),
+    "pcops_mlp_pool_top_wsparse_rows_partial": ([_I, _I], _U64),
     "pcops_knn_graph_path": ([_I, _I, _I, _I, _P], _I),
     "pcops_last_launch_pipe": ([], _I),
     "pcops_last_launch_plan": ([_P, _I], _I),

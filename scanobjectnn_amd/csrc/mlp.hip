@@ -1303,7 +1303,9 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void gemm_ws_kernel(GemmArgs
             const float4 epv = EM == E_FWD ? *reinterpret_cast<const float4 *>(&ecoef[2 * BN + ocq])
                                            : make_float4(0.f, 0.f, 0.f, 0.f);             // forward: the pivot
             float ew[2] = {1.f, 1.f};                        // compacted rows: statistics weight of rows 0 / 16
-            if (EM == E_FWD && compact) {
+            // (E_MASKA / E_PLAINA: the weight of the DENSE part  acc + vconst  of those rows -- the row stands for w equal rows
+            // of the uncompacted tensor, the arg-max row of a group is counted once: the addend carries no weight)
+            if ((EM == E_FWD || has_add(EM)) && compact) {
                 const int nblk = (M + kBlk - 1) / kBlk;
 #pragma unroll
                 for (int hb = 0; hb < 2; ++hb) {
@@ -1352,12 +1354,24 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void gemm_ws_kernel(GemmArgs
                         }
                     } else if (EM == E_PLAINA) {
                         const float4 vc = *reinterpret_cast<const float4 *>(&ecoef[2 * BN + ocq]);
+                        if (compact && j % (O4 / 4) == 0) {
+                            const float w = lane < O4 ? ew[j / (O4 / 4)] : 1.f;
+                            o.x = w * (o.x + vc.x) + pad[j].x; o.y = w * (o.y + vc.y) + pad[j].y;
+                            o.z = w * (o.z + vc.z) + pad[j].z; o.w = w * (o.w + vc.w) + pad[j].w;
+                        } else {
                         o.x += pad[j].x + vc.x; o.y += pad[j].y + vc.y; o.z += pad[j].z + vc.z; o.w += pad[j].w + vc.w;
+                        }
                     } else if (is_mask(EM)) {
                         const float4 yp = py[j];
                         if (EM == E_MASKA) {
                             const float4 vc = *reinterpret_cast<const float4 *>(&ecoef[2 * BN + ocq]);
+                            if (compact && j % (O4 / 4) == 0) {
+                                const float w = lane < O4 ? ew[j / (O4 / 4)] : 1.f;
+                                o.x = w * (o.x + vc.x) + pad[j].x; o.y = w * (o.y + vc.y) + pad[j].y;
+                                o.z = w * (o.z + vc.z) + pad[j].z; o.w = w * (o.w + vc.w) + pad[j].w;
+                            } else {
                             o.x += pad[j].x + vc.x; o.y += pad[j].y + vc.y; o.z += pad[j].z + vc.z; o.w += pad[j].w + vc.w;
+                            }
                         }
                         o.x = fmaf(yp.x, eb.x, em.x) > 0.f ? o.x : 0.f;
                         o.y = fmaf(yp.y, eb.y, em.y) > 0.f ? o.y : 0.f;
@@ -4114,6 +4128,9 @@ struct GramArgs {
     const float *X, *asc, *ash;      // X = raw input; asc == NULL: plain, else relu(X asc + ash)
     float *part;                     // [groups][K][K] partial Gram (upper 32 x 32 blocks written)
     float *xpart;                    // [groups][K] partial column sums
+    // compacted rows (gram_full_kernel<.., ROWS>): X^T diag(w) X and X^T w, w = the weight of a block's first row
+    const RowBlock *blocks;
+    const int *Mdev;
 };
 
 constexpr int gram_blocks(int nbk) { return nbk * (nbk + 1) / 2; }
@@ -4154,7 +4171,10 @@ __device__ __forceinline__ void gram_store(const AccT &acc, float *out, int K, i
     (one(std::integral_constant<int, B>{}), ...);
 }
 
-template <int NBK, bool BNRELU>
+// ROWS: compacted rows.  The first row of a 16-row block stands for w equal rows: it is staged as sqrt(w) x, so that both
+// operand sides of the symmetric product carry half of the weight (the two sides are ONE stripe in LDS) and the column
+// sums take sqrt(w) of the staged value, i.e. w x.  w = 1 leaves a row bit for bit what the uncompacted kernel stages.
+template <int NBK, bool BNRELU, bool ROWS = false>
 __global__ __launch_bounds__(512, 1) void gram_full_kernel(GramArgs a) {
     constexpr int KP = 32 * NBK, RS = 32, LD = KP + 4;
     constexpr int NU = gram_blocks(NBK), PER = (NU + 3) / 4;       // upper blocks, blocks per consumer wave
@@ -4163,7 +4183,7 @@ __global__ __launch_bounds__(512, 1) void gram_full_kernel(GramArgs a) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int K = a.K;
-    const long long M = a.M;
+    const long long M = ROWS ? (long long)__builtin_amdgcn_readfirstlane(*a.Mdev) : a.M;
     const int grp = blockIdx.x, ngrp = gridDim.x;
     float *coef = lds;                 // [2][KP]
     float *buf = coef + 2 * KP;        // [2][RS][LD]  | afterwards: column-sum scratch [256][4]
@@ -4194,6 +4214,16 @@ __global__ __launch_bounds__(512, 1) void gram_full_kernel(GramArgs a) {
         };
         auto stage = [&](long long stripe, float *dst) {
             const long long row0 = stripe * RS;
+            float sw[2] = {1.f, 1.f};                          // sqrt(weight) of rows 0 / 16 of the stripe
+            if (ROWS) {
+                const long long nblk = (M + kBlk - 1) / kBlk;
+#pragma unroll
+                for (int hb = 0; hb < 2; ++hb) {
+                    long long bi = stripe * 2 + hb;
+                    bi = bi < nblk ? bi : nblk - 1;
+                    sw[hb] = sqrtf(uniform_block(a.blocks, bi).w);
+                }
+            }
 #pragma unroll
             for (int j = 0; j < NV; ++j) {
                 const int e = pt + 256 * j, r = e / K4, c = (e % K4) * 4;
@@ -4205,7 +4235,14 @@ __global__ __launch_bounds__(512, 1) void gram_full_kernel(GramArgs a) {
                     x.z = fmaxf(fmaf(x.z, sc.z, sh.z), 0.f); x.w = fmaxf(fmaf(x.w, sc.w, sh.w), 0.f);
                     if (!(c < K && row0 + r < M)) x = make_float4(0.f, 0.f, 0.f, 0.f);   // (relu(shift) of a padded element)
                 }
+                if (ROWS && (r & (kBlk - 1)) == 0) {
+                    const float w = sw[r / kBlk];
+                    x.x *= w; x.y *= w; x.z *= w; x.w *= w;
+                    cs[j][0] = fmaf(w, x.x, cs[j][0]); cs[j][1] = fmaf(w, x.y, cs[j][1]);
+                    cs[j][2] = fmaf(w, x.z, cs[j][2]); cs[j][3] = fmaf(w, x.w, cs[j][3]);
+                } else {
                 cs[j][0] += x.x; cs[j][1] += x.y; cs[j][2] += x.z; cs[j][3] += x.w;
+                }
                 *reinterpret_cast<float4 *>(&dst[r * LD + c]) = x;
             }
         };
@@ -4907,6 +4944,149 @@ __global__ __launch_bounds__(256) void pool_top_wsparse_kernel(long long G, int 
         cfsum[c] = (red[0][64 * KR] + red[1][64 * KR]) + (red[2][64 * KR] + red[3][64 * KR]);
 }
 
+// ---- the two sparse halves over COMPACTED rows, for MANY SMALL groups (the grouped stacks: 32 768 groups of <= 64 rows at
+// the SSG config's second level).  The kernels above give a workgroup to a group / a channel and fetch a Kp-wide row of W^T /
+// of X per hit through L2 -- 4.3 GB of 512-byte gathers each at that shape.  Here the reused operand sits in LDS:
+//   pool_top_addend_rows_kernel   W^T [C][KP] resident (128 KB), persistent workgroups, four groups per round
+//   pool_top_wsparse_rows_kernel  group-major: a group's rows of X (contiguous in the compacted stack) staged once
+// The row of slot (g, a) is 16 block_start[g] + a; argmax is the row-in-group in compacted numbering.  Sums in a fixed order.
+//
+// addend: a quarter of the workgroup (256 threads = the C <= 256 channels) owns one group per round.  The channels that
+// picked row r are a C-bit mask in LDS (integer OR: the result does not depend on the order); KP / 4 lanes per row then add
+// cf[c] Wt[c][:] over the set bits in ascending channel order and write the row ONCE.  The addend is indexed by the
+// compacted row itself (slot = row), rowmap [row] = row or -1.
+template <int KP>
+__global__ __launch_bounds__(1024) void pool_top_addend_rows_kernel(int G, int C, const float *__restrict__ gout,
+                                                                    const float *__restrict__ ysel,
+                                                                    const unsigned char *__restrict__ arg,
+                                                                    const float *__restrict__ sc, const float *__restrict__ sh,
+                                                                    const float *__restrict__ p, const float *__restrict__ Wt,
+                                                                    const int *__restrict__ block_start,
+                                                                    float *__restrict__ addend, int *__restrict__ rowmap) {
+    constexpr int LPR = KP / 4, RPP = 256 / LPR;      // lanes per row (a float4 each), rows per pass of a quarter
+    constexpr int MAXR = 128, MW = 8;                 // rows per group, mask words per row (C <= 256)
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    float *Ws = lds;                                  // [C][KP]
+    float *cf = Ws + (size_t)C * KP;                  // [4][256]
+    unsigned *mask = reinterpret_cast<unsigned *>(cf + 4 * 256);      // [4][MAXR][MW]
+    const int tid = threadIdx.x, sub = tid >> 8, c = tid & 255;
+    for (int e = tid; e < C * (KP / 4); e += 1024)
+        reinterpret_cast<float4 *>(Ws)[e] = reinterpret_cast<const float4 *>(Wt)[e];
+    const float scc = c < C ? sc[c] : 0.f, shc = c < C ? sh[c] : 0.f, pc = c < C ? p[c] : 0.f;
+    float *mycf = cf + sub * 256;
+    unsigned *mymask = mask + sub * MAXR * MW;
+    const int q = c % LPR, rsub = c / LPR;
+    float v = 0.f;
+    int row = 0, base = 0, nrows = 0;
+    auto fetch = [&](long long g) {
+        v = 0.f; row = 0; base = 0; nrows = 0;
+        if (g < G) {
+            const int b0 = block_start[g];
+            base = kBlk * b0;
+            nrows = kBlk * (block_start[g + 1] - b0);
+            nrows = nrows < MAXR ? nrows : MAXR;
+            if (c < C) {
+                const long long e = g * C + c;
+                v = fmaf(ysel[e], scc, shc) > 0.f ? pc * gout[e] : 0.f;
+                row = arg[e];
+            }
+        }
+    };
+    fetch((long long)blockIdx.x * 4 + sub);
+    for (long long g0 = (long long)blockIdx.x * 4; g0 < G; g0 += (long long)gridDim.x * 4) {
+        const float cv = v;
+        const int crow = row, cbase = base, cnrows = nrows;
+        __syncthreads();                              // the previous round's rows are written (and Ws is there)
+        mycf[c] = cv;
+#pragma unroll
+        for (int i = 0; i < MAXR * MW / 256; ++i) mymask[c + 256 * i] = 0u;
+        __syncthreads();
+        if (cv != 0.f && crow < cnrows) atomicOr(&mymask[crow * MW + (c >> 5)], 1u << (c & 31));
+        __syncthreads();
+        fetch(g0 + (long long)gridDim.x * 4 + sub);  // the next round's coefficients fly under this round's rows
+        for (int r = rsub; r < cnrows; r += RPP) {
+            float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+            bool any = false;
+#pragma unroll
+            for (int w = 0; w < MW; ++w) {
+                unsigned mm = mymask[r * MW + w];
+                any = any || mm != 0u;
+                while (mm) {
+                    const int ch = 32 * w + __builtin_ctz(mm);
+                    mm &= mm - 1u;
+                    const float cw = mycf[ch];
+                    const float4 wt = *reinterpret_cast<const float4 *>(&Ws[ch * KP + 4 * q]);
+                    acc.x = fmaf(cw, wt.x, acc.x); acc.y = fmaf(cw, wt.y, acc.y);
+                    acc.z = fmaf(cw, wt.z, acc.z); acc.w = fmaf(cw, wt.w, acc.w);
+                }
+            }
+            const long long ri = (long long)cbase + r;
+            if (any) *reinterpret_cast<float4 *>(&addend[ri * KP + 4 * q]) = acc;
+            if (q == 0) rowmap[ri] = any ? (int)ri : -1;
+        }
+    }
+}
+
+// wsparse: thread = channel, KP accumulators in registers; a workgroup walks its share of the groups, stages the group's
+// rows of relu(bn(X)) (row stride KP + 1: the lanes of a wave read DIFFERENT rows at the same k -- conflict-free) and adds
+// cf[g][c] X_g[arg][:].  part [gridDim.x][KP][C], part2 [gridDim.x][C]: summed in a fixed order by sum_partials2_kernel.
+template <int KP>
+__global__ __launch_bounds__(256) void pool_top_wsparse_rows_kernel(int G, int C, int maxr, const float *__restrict__ gout,
+                                                                    const float *__restrict__ ysel,
+                                                                    const unsigned char *__restrict__ arg,
+                                                                    const float *__restrict__ sc, const float *__restrict__ sh,
+                                                                    const float *__restrict__ p,
+                                                                    const float *__restrict__ Yprev,
+                                                                    const float *__restrict__ psc, const float *__restrict__ psh,
+                                                                    const int *__restrict__ block_start,
+                                                                    float *__restrict__ part, float *__restrict__ part2) {
+    constexpr int LD = KP + 1, K4 = KP / 4;
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    float *Xs = lds;                                  // [maxr][LD]
+    const int tid = threadIdx.x, c = tid;             // C <= 256
+    const float scc = c < C ? sc[c] : 0.f, shc = c < C ? sh[c] : 0.f, pc = c < C ? p[c] : 0.f;
+    // a thread stages the column quad tid % K4 of the rows tid / K4, + 256 / K4, ...: its BN coefficients are fixed
+    const int k4 = tid % K4, r0 = tid / K4;
+    const float4 asc = *reinterpret_cast<const float4 *>(psc + 4 * k4), ash = *reinterpret_cast<const float4 *>(psh + 4 * k4);
+    float acc[KP];
+#pragma unroll
+    for (int k = 0; k < KP; ++k) acc[k] = 0.f;
+    float csum = 0.f;
+    for (int g = blockIdx.x; g < G; g += gridDim.x) {
+        const int b0 = block_start[g];
+        int nrows = kBlk * (block_start[g + 1] - b0);
+        nrows = nrows < maxr ? nrows : maxr;
+        const float *src = Yprev + (long long)kBlk * b0 * KP;
+        float cfv = 0.f;
+        int row = 0;
+        if (c < C) {
+            const long long e = (long long)g * C + c;
+            cfv = fmaf(ysel[e], scc, shc) > 0.f ? pc * gout[e] : 0.f;
+            row = arg[e];
+            if (row >= nrows) { row = 0; cfv = 0.f; }
+        }
+        __syncthreads();                              // the previous group's rows are consumed
+        for (int r = r0; r < nrows; r += 256 / K4) {
+            float4 x = *reinterpret_cast<const float4 *>(src + (long long)r * KP + 4 * k4);
+            x.x = fmaxf(fmaf(x.x, asc.x, ash.x), 0.f); x.y = fmaxf(fmaf(x.y, asc.y, ash.y), 0.f);
+            x.z = fmaxf(fmaf(x.z, asc.z, ash.z), 0.f); x.w = fmaxf(fmaf(x.w, asc.w, ash.w), 0.f);
+            float *d = &Xs[r * LD + 4 * k4];
+            d[0] = x.x; d[1] = x.y; d[2] = x.z; d[3] = x.w;
+        }
+        __syncthreads();
+        const float *xr = &Xs[row * LD];
+#pragma unroll
+        for (int k = 0; k < KP; ++k) acc[k] = fmaf(cfv, xr[k], acc[k]);
+        csum += cfv;
+    }
+    if (c < C) {
+        float *dst = part + (long long)blockIdx.x * KP * C + c;
+#pragma unroll
+        for (int k = 0; k < KP; ++k) dst[(long long)k * C] = acc[k];
+        part2[(long long)blockIdx.x * C + c] = csum;
+    }
+}
+
 // C [M][N] = A [M][K] B [K][N] for the SMALL products around the big kernels (weights x weights: K x K Gram algebra,
 // matrix-vector rows).  One 32 x 32 tile per workgroup so that even a 512 x 512 result fills the chip; the 4 waves split
 // K and add their accumulators through LDS in a fixed order.  (Eight waves over K for the long reductions -- the partial tiles
@@ -5024,6 +5204,7 @@ PCOPS_HIDDEN int wgrad_impl(WgradArgs &a, float *partial, float *dW, float *db, 
 PCOPS_HIDDEN int bwd_fused_launch(WgradArgs &a, bool xyz, int groups, float *partial, float *dW, float *db, hipStream_t st,
                                   bool side = false, const float *gw_bias = nullptr);
 PCOPS_HIDDEN int gram_full_launch(GramArgs &g, int nbk, bool bnrelu, int gg, size_t lds, hipStream_t st);
+PCOPS_HIDDEN int gram_full_rows_launch(GramArgs &g, int nbk, int gg, size_t lds, hipStream_t st);
 
 static int wgrad_legacy_splits(long long M, int K, int N) {
     const int kb = (K + 63) / 64, nb = (N + 127) / 128;
@@ -5324,6 +5505,17 @@ int gram_full_launch(GramArgs &g, int nbk, bool bnrelu, int gg, size_t lds, hipS
 #undef PCOPS_GRAM_LAUNCH
     return PCOPS_OK;
 }
+
+// compacted rows: the widths the pooled top layers of the grouped stacks have (Kp = 64, 128), BN + ReLU input
+int gram_full_rows_launch(GramArgs &g, int nbk, int gg, size_t lds, hipStream_t st) {
+    auto kern = nbk == 2 ? gram_full_kernel<2, true, true> : gram_full_kernel<4, true, true>;
+    if (nbk != 2 && nbk != 4) return PCOPS_ERR_UNSUPPORTED;
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) !=
+        hipSuccess)
+        return PCOPS_ERR_LAUNCH;
+    hipLaunchKernelGGL(kern, dim3(gg), dim3(512), lds, st, g);
+    return PCOPS_OK;
+}
 #endif
 
 #if PCOPS_PART(0)
@@ -5447,7 +5639,9 @@ int pcops_mlp_gemm_fwd_pool_rows(int M, int K, int N, const float *X, int ldx, c
                                  float *Y, float *stats_partial, const float *stat_pivot, float *ypart,
                                  unsigned char *ppart, const pcops_rows_t *rows, pcops_stream_t stream) {
     PCOPS_REQUIRE_SHAPE(M >= 1 && K >= 1 && N >= 1 && ldx >= K);
-    PCOPS_REQUIRE_PTR(X); PCOPS_REQUIRE_PTR(W); PCOPS_REQUIRE_PTR(Y); PCOPS_REQUIRE_PTR(pro_scale);
+    // Y == NULL: the activation is not stored (the stack takes the algebraic backward, or has none); every other output
+    // is what the storing call writes
+    PCOPS_REQUIRE_PTR(X); PCOPS_REQUIRE_PTR(W); PCOPS_REQUIRE_PTR(pro_scale);
     PCOPS_REQUIRE_PTR(pro_shift); PCOPS_REQUIRE_PTR(gamma); PCOPS_REQUIRE_PTR(ypart); PCOPS_REQUIRE_PTR(ppart);
     PCOPS_REQUIRE_PTR(rows);
     if (ldx != K || (reinterpret_cast<uintptr_t>(ypart) & 15) || (reinterpret_cast<uintptr_t>(ppart) & 3))
@@ -6122,23 +6316,8 @@ int pcops_mlp_pool_top_addend(int M, int Kp, int N, int S, const float *gout, co
 int pcops_mlp_gemm_dgrad_top(int M, int Kp, const float *Yprev, const float *prev_scale, const float *prev_shift,
                              const float *Mq, const float *vconst, const float *addend, long long addend_rows,
                              const int *rowmap, float *Gprev, float *stats_partial, pcops_stream_t stream) {
-    PCOPS_REQUIRE_SHAPE(M >= 1 && Kp >= 1);
-    PCOPS_REQUIRE_PTR(Yprev); PCOPS_REQUIRE_PTR(Mq);
-    PCOPS_REQUIRE_PTR(vconst); PCOPS_REQUIRE_PTR(addend); PCOPS_REQUIRE_PTR(rowmap); PCOPS_REQUIRE_PTR(Gprev);
-    PCOPS_REQUIRE_ARG((prev_scale == nullptr) == (prev_shift == nullptr));
-    WsPlan pl;
-    if (!dgrad_top_plan(M, Kp, &pl)) return PCOPS_ERR_UNSUPPORTED;
-    GemmArgs a = {};
-    a.M = M; a.K = Kp; a.N = Kp; a.X = Yprev; a.ldx = Kp; a.v0 = prev_scale; a.v1 = prev_shift;
-    a.W = Mq; a.Y = Gprev; a.ldy = Kp; a.Yprev = Yprev; a.msc = prev_scale; a.msh = prev_shift;
-    a.stats = stats_partial; a.addend = addend; a.rowmap = rowmap; a.add_ld = Kp; a.vconst = vconst;
-    a.add_bytes = addend_rows * Kp * 4;
-    if (addend_rows < 1 || a.add_bytes >= (long long)kOOB) return PCOPS_ERR_UNSUPPORTED;
-    if (!prev_scale) {      // X is the stack's raw input: plain dX, no mask, no statistics
-        a.stats = nullptr;
-        return launch_gemm_ws_only<A_PLAIN, E_PLAINA>(a, as_stream(stream));
-    }
-    return launch_gemm_ws_only<A_BNRELU, E_MASKA>(a, as_stream(stream));
+    return pcops_mlp_gemm_dgrad_top_rows(M, Kp, Yprev, prev_scale, prev_shift, Mq, vconst, addend, addend_rows, rowmap, Gprev,
+                                         stats_partial, nullptr, stream);
 }
 
 /* gram [Kp][Kp] = X^T X, xsum [Kp] = X^T 1 with X = relu(Yprev * a_scale + a_shift);  partial as pcops_mlp_wgrad
@@ -6187,6 +6366,143 @@ int pcops_mlp_pool_top_wsparse(int M, int Kp, int N, int S, const float *gout, c
     PCOPS_REQUIRE_PTR(Ssp); PCOPS_REQUIRE_PTR(cfsum);
     hipLaunchKernelGGL(pool_top_wsparse_kernel, dim3(N), dim3(256), 0, as_stream(stream), (long long)(M / S), S, N,
                        Kp, gout, ysel, argmax, pool_scale, pool_shift, p, Yprev, prev_scale, prev_shift, Ssp, cfsum);
+    return pcops_launch_status();
+}
+
+
+/* ---- the four algebraic entry points over COMPACTED rows (pcops.h): rows == NULL is the entry point without the suffix */
+static const int kTopRowsWs = 512;        // workgroups (= partial copies) of pool_top_wsparse_rows_kernel
+
+int pcops_mlp_pool_top_rows_supported(int M, int Kp, int N, int S) {
+    if (!pcops_mlp_pool_top_supported(M, Kp, N, S)) return 0;
+    if (M < 65536 || S % kBlk != 0 || S > 128 || (Kp != 64 && Kp != 128) || N > 256 || N % 32 != 0) return 0;
+    if (!gram_full_groups(M, Kp, Kp, nullptr)) return 0;
+    // the addend is indexed by the compacted row: at most M rows of Kp floats behind a 32-bit buffer offset
+    return (long long)M * Kp * 4 < (long long)kOOB ? 1 : 0;
+}
+
+unsigned long long pcops_mlp_pool_top_wsparse_rows_partial(int Kp, int N) {
+    return (unsigned long long)kTopRowsWs * ((unsigned long long)Kp * N + N);
+}
+
+int pcops_mlp_pool_top_addend_rows(int M, int Kp, int N, int S, const float *gout, const float *ysel,
+                                   const unsigned char *argmax, const float *pool_scale, const float *pool_shift,
+                                   const float *p, const float *Wt, float *addend, int *rowmap, const pcops_rows_t *rows,
+                                   pcops_stream_t stream) {
+    if (!rows) return pcops_mlp_pool_top_addend(M, Kp, N, S, gout, ysel, argmax, pool_scale, pool_shift, p, Wt, addend, rowmap, stream);
+    PCOPS_REQUIRE_SHAPE(M >= 1 && S >= 1 && M % S == 0);
+    PCOPS_REQUIRE_PTR(gout); PCOPS_REQUIRE_PTR(ysel); PCOPS_REQUIRE_PTR(argmax); PCOPS_REQUIRE_PTR(pool_scale);
+    PCOPS_REQUIRE_PTR(pool_shift); PCOPS_REQUIRE_PTR(p); PCOPS_REQUIRE_PTR(Wt); PCOPS_REQUIRE_PTR(addend);
+    PCOPS_REQUIRE_PTR(rowmap);
+    { const int rrc = rows_ok(rows); if (rrc) return rrc; }
+    if (!pcops_mlp_pool_top_rows_supported(M, Kp, N, S)) return PCOPS_ERR_UNSUPPORTED;
+    if (reinterpret_cast<uintptr_t>(Wt) & 15 || reinterpret_cast<uintptr_t>(addend) & 15) return PCOPS_ERR_UNSUPPORTED;
+    const int G = M / S;
+    const size_t lds = ((size_t)N * Kp + 4 * 256 + 4 * 128 * 8) * sizeof(float);
+    const int grid = (G + 3) / 4 < 256 ? (G + 3) / 4 : 256;
+    hipStream_t st = as_stream(stream);
+#define PCOPS_ADDR_LAUNCH(KP_)                                                                              \
+    do {                                                                                                    \
+        auto kern = pool_top_addend_rows_kernel<KP_>;                                                       \
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, \
+                                160 * 1024) != hipSuccess)                                                  \
+            return PCOPS_ERR_LAUNCH;                                                                        \
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(1024), lds, st, G, N, gout, ysel, argmax, pool_scale, pool_shift, p, \
+                           Wt, rows->block_start, addend, rowmap);                                          \
+    } while (0)
+    if (Kp == 64) PCOPS_ADDR_LAUNCH(64);
+    else PCOPS_ADDR_LAUNCH(128);
+#undef PCOPS_ADDR_LAUNCH
+    return pcops_launch_status();
+}
+
+int pcops_mlp_pool_top_wsparse_rows(int M, int Kp, int N, int S, const float *gout, const float *ysel,
+                                    const unsigned char *argmax, const float *pool_scale, const float *pool_shift,
+                                    const float *p, const float *Yprev, const float *prev_scale, const float *prev_shift,
+                                    float *Ssp, float *cfsum, float *partial, const pcops_rows_t *rows,
+                                    pcops_stream_t stream) {
+    if (!rows) return pcops_mlp_pool_top_wsparse(M, Kp, N, S, gout, ysel, argmax, pool_scale, pool_shift, p, Yprev, prev_scale, prev_shift, Ssp, cfsum, stream);
+    PCOPS_REQUIRE_SHAPE(M >= 1 && S >= 1 && M % S == 0);
+    PCOPS_REQUIRE_PTR(gout); PCOPS_REQUIRE_PTR(ysel); PCOPS_REQUIRE_PTR(argmax); PCOPS_REQUIRE_PTR(pool_scale);
+    PCOPS_REQUIRE_PTR(pool_shift); PCOPS_REQUIRE_PTR(p); PCOPS_REQUIRE_PTR(Yprev); PCOPS_REQUIRE_PTR(prev_scale);
+    PCOPS_REQUIRE_PTR(prev_shift); PCOPS_REQUIRE_PTR(Ssp); PCOPS_REQUIRE_PTR(cfsum); PCOPS_REQUIRE_PTR(partial);
+    { const int rrc = rows_ok(rows); if (rrc) return rrc; }
+    if (!pcops_mlp_pool_top_rows_supported(M, Kp, N, S)) return PCOPS_ERR_UNSUPPORTED;
+    if (reinterpret_cast<uintptr_t>(Yprev) & 15 || reinterpret_cast<uintptr_t>(prev_scale) & 15 ||
+        reinterpret_cast<uintptr_t>(prev_shift) & 15)
+        return PCOPS_ERR_UNSUPPORTED;
+    const int G = M / S;
+    const int grid = G < kTopRowsWs ? G : kTopRowsWs;
+    const size_t lds = (size_t)S * (Kp + 1) * sizeof(float);
+    float *part2 = partial + (long long)kTopRowsWs * Kp * N;
+    hipStream_t st = as_stream(stream);
+#define PCOPS_WSPR_LAUNCH(KP_)                                                                              \
+    do {                                                                                                    \
+        auto kern = pool_top_wsparse_rows_kernel<KP_>;                                                      \
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, \
+                                160 * 1024) != hipSuccess)                                                  \
+            return PCOPS_ERR_LAUNCH;                                                                        \
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, G, N, S, gout, ysel, argmax, pool_scale, pool_shift, p, \
+                           Yprev, prev_scale, prev_shift, rows->block_start, partial, part2);               \
+    } while (0)
+    if (Kp == 64) PCOPS_WSPR_LAUNCH(64);
+    else PCOPS_WSPR_LAUNCH(128);
+#undef PCOPS_WSPR_LAUNCH
+    int rc = pcops_launch_status();
+    if (rc) return rc;
+    const long long L = (long long)Kp * N;
+    hipLaunchKernelGGL(sum_partials2_kernel, dim3(cdiv(L, 64) + cdiv(N, 64)), dim3(1024), 0, st, grid, L, partial, Ssp,
+                       (long long)N, part2, cfsum);
+    return pcops_launch_status();
+}
+
+int pcops_mlp_gemm_dgrad_top_rows(int M, int Kp, const float *Yprev, const float *prev_scale, const float *prev_shift,
+                                  const float *Mq, const float *vconst, const float *addend, long long addend_rows,
+                                  const int *rowmap, float *Gprev, float *stats_partial, const pcops_rows_t *rows,
+                                  pcops_stream_t stream) {
+    PCOPS_REQUIRE_SHAPE(M >= 1 && Kp >= 1);
+    PCOPS_REQUIRE_PTR(Yprev); PCOPS_REQUIRE_PTR(Mq);
+    PCOPS_REQUIRE_PTR(vconst); PCOPS_REQUIRE_PTR(addend); PCOPS_REQUIRE_PTR(rowmap); PCOPS_REQUIRE_PTR(Gprev);
+    PCOPS_REQUIRE_ARG((prev_scale == nullptr) == (prev_shift == nullptr));
+    WsPlan pl;
+    if (!dgrad_top_plan(M, Kp, &pl)) return PCOPS_ERR_UNSUPPORTED;
+    GemmArgs a = {};
+    a.M = M; a.K = Kp; a.N = Kp; a.X = Yprev; a.ldx = Kp; a.v0 = prev_scale; a.v1 = prev_shift;
+    a.W = Mq; a.Y = Gprev; a.ldy = Kp; a.Yprev = Yprev; a.msc = prev_scale; a.msh = prev_shift;
+    a.stats = stats_partial; a.addend = addend; a.rowmap = rowmap; a.add_ld = Kp; a.vconst = vconst;
+    a.add_bytes = addend_rows * Kp * 4;
+    if (addend_rows < 1 || a.add_bytes >= (long long)kOOB) return PCOPS_ERR_UNSUPPORTED;
+    PCOPS_ROWS(a, rows);
+    if (!prev_scale) {      // X is the stack's raw input: plain dX, no mask, no statistics
+        a.stats = nullptr;
+        return launch_gemm_ws_only<A_PLAIN, E_PLAINA>(a, as_stream(stream));
+    }
+    return launch_gemm_ws_only<A_BNRELU, E_MASKA>(a, as_stream(stream));
+}
+
+int pcops_mlp_gram_rows(long long M, int Kp, const float *Yprev, int ldx, const float *a_scale, const float *a_shift,
+                        float *partial, float *gram, float *xsum, const pcops_rows_t *rows, pcops_stream_t stream) {
+    if (!rows) return pcops_mlp_gram(M, Kp, Yprev, ldx, a_scale, a_shift, partial, gram, xsum, stream);
+    PCOPS_REQUIRE_SHAPE(M >= 1 && Kp >= 1 && ldx >= Kp);
+    PCOPS_REQUIRE_PTR(Yprev); PCOPS_REQUIRE_PTR(partial); PCOPS_REQUIRE_PTR(gram); PCOPS_REQUIRE_PTR(a_scale);
+    PCOPS_REQUIRE_PTR(a_shift);
+    { const int rrc = rows_ok(rows); if (rrc) return rrc; }
+    const int gg = gram_full_groups(M, Kp, ldx, Yprev);
+    if (gg <= 0 || (Kp != 64 && Kp != 128)) return PCOPS_ERR_UNSUPPORTED;
+    pcops_note_pipe(0);
+    hipStream_t st = as_stream(stream);
+    GramArgs g = {M, Kp, ldx, Yprev, a_scale, a_shift, partial, partial + (long long)gg * Kp * Kp,
+                  static_cast<const RowBlock *>(rows->blocks), rows->rows};
+    const int nbk = Kp / 32;
+    const size_t lds = (size_t)(2 * 32 * nbk + 2 * 32 * (32 * nbk + 4)) * sizeof(float);
+    const int rcl = gram_full_rows_launch(g, nbk, gg, lds, st);
+    if (rcl) return rcl;
+    int rc = pcops_launch_status();
+    if (rc) return rc;
+    const long long L = (long long)Kp * Kp;
+    hipLaunchKernelGGL(sum_partials2_kernel, dim3(cdiv(L, 64) + (xsum ? cdiv(Kp, 64) : 0)), dim3(1024), 0, st, gg, L,
+                       partial, gram, (long long)Kp, g.xpart, xsum);
+    hipLaunchKernelGGL(mirror_lower_kernel, dim3(Kp), dim3(256), 0, st, Kp, gram);
     return pcops_launch_status();
 }
 

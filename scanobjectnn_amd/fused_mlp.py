@@ -164,20 +164,25 @@ class FusedMLPStack(torch.autograd.Function):
                 N = w.shape[-1]
                 W2 = w.detach().reshape(-1, N)
                 assert W2.shape[0] == K and W2.is_contiguous()
-                Y = _f32((R, N), dev)
+                pool_rows = (rows is not None and pool and li == L - 1 and sc_prev is not None and ld == K
+                             and not (li == 1 and virt) and FUSE_POOL_ROWS
+                             and bool(lib.pcops_mlp_gemm_fwd_pool_rows_supported(R, K, N)))
+                if pool_rows:
+                    # the algebraic backward over compacted rows never reads the activation: it is not stored (nor allocated)
+                    pool_top = need_grad and _pool_top_ok(lib, R, K, N, S, li, gather, K0, rows, False, b is not None)
+                Y = None if (pool_rows and pool_top) else _f32((R, N), dev)
                 P = lib.pcops_mlp_stats_rows(R)
                 part = _f32((P, 2, N), dev) if training else None
                 if li == 1 and virt:
                     _lib.call("pcops_mlp_gemm_fwd_xyz_rows", R, K, N, off4.data_ptr(), xyzw.data_ptr(), sc_prev.data_ptr(),
                               sh_prev.data_ptr(), W2.data_ptr(), b.data_ptr(), Y.data_ptr(), _p(part), piv, rref)
-                elif (rows is not None and pool and li == L - 1 and sc_prev is not None and ld == K and FUSE_POOL_ROWS
-                        and lib.pcops_mlp_gemm_fwd_pool_rows_supported(R, K, N)):
+                elif pool_rows:
                     # compacted rows: the epilogue emits the extremum of every 16-row block (a block lies inside one
                     # group), a small pass picks per group afterwards
                     nbk = rows.blocks.shape[0]
                     pooled_parts = (_f32((nbk, N), dev), torch.empty((nbk, N), dtype=torch.uint8, device=dev))
                     _lib.call("pcops_mlp_gemm_fwd_pool_rows", R, K, N, src.data_ptr(), ld, sc_prev.data_ptr(),
-                              sh_prev.data_ptr(), W2.data_ptr(), b.data_ptr(), gamma.data_ptr(), Y.data_ptr(),
+                              sh_prev.data_ptr(), W2.data_ptr(), b.data_ptr(), gamma.data_ptr(), _p(Y),
                               _p(part), piv, pooled_parts[0].data_ptr(), pooled_parts[1].data_ptr(), rref)
                 elif rows is not None:
                     # compacted rows without the fused epilogue: the max over the groups is its own pass below
@@ -408,7 +413,7 @@ class FusedMLPStack(torch.autograd.Function):
                 prev = (Ys[l - 1], scales[l - 1], shifts[l - 1]) if l > 0 else (a0, None, None)
                 Gm, part = _pool_top_backward(R, K, N, S, Ws[l], ctx.biases[l].detach(), p, q, t, grad_out, ysel,
                                               argmax, scales[l], shifts[l], prev[0], prev[1], prev[2], grads, l, dev,
-                                              l > 0 or ctx.needs_input_grad[0])
+                                              l > 0 or ctx.needs_input_grad[0], rows)
                 P = lib.pcops_mlp_stats_rows(R)
                 if l == 0:
                     d0 = Gm
@@ -530,16 +535,23 @@ class FusedMLPStack(torch.autograd.Function):
 
 def _pool_top_ok(lib, R, K, N, S, l, gather, K0, rows, xyz_prev, has_bias):
     """the pooled top layer l takes the algebraic backward (pcops.h): K x K products instead of K x N, no use of Y"""
-    return bool(POOL_TOP and rows is None and not xyz_prev and S >= 64 and N >= 2 * K
+    if rows is not None:        # compacted rows: the *_rows forms, one answer from the library (PCOPS_POOL_TOP_ROWS=0: never)
+        # (the narrow layers the one-pass backward takes stay there: it reads Y once for both gradients)
+        return bool(POOL_TOP and POOL_TOP_ROWS and not xyz_prev and S >= 64 and N >= 2 * K and l > 0 and has_bias
+                    and not (BWD_FUSED and lib.pcops_mlp_bwd_fused_groups(R, K, N, S, 1))
+                    and lib.pcops_mlp_pool_top_rows_supported(R, K, N, S))
+    return bool(POOL_TOP and not xyz_prev and S >= 64 and N >= 2 * K
                 and (l > 0 or (not gather and K0 == K)) and has_bias
                 and lib.pcops_mlp_pool_top_supported(R, K, N, S))
 
 
 def _pool_top_backward(R, K, N, S, W, b, p, q, t, grad_out, ysel, argmax, sc, sh, Yprev, psc, psh, grads, l, dev,
-                       need_dx=True):
+                       need_dx=True, rows=None):
     """dW, db (into grads) and the masked data gradient + its statistics of a pooled top layer, from the Kp x Kp
-    products of pcops.h's algebraic form.  Returns (Gprev, stats_partial)."""
+    products of pcops.h's algebraic form.  Returns (Gprev, stats_partial).  rows: the stack's compacted row set (R stays
+    the uncompacted count: it sizes the buffers and is the M of the closing sums)."""
     lib = _lib.load()
+    rref = rows.ref if rows is not None else None
     Wt = _f32((N, K), dev)
     if TAIL_FOLD:       # W^T, W diag(q) and q.b + t out of one launch
         Wq, u = _f32((K, N), dev), _f32(N, dev)
@@ -556,8 +568,12 @@ def _pool_top_backward(R, K, N, S, W, b, p, q, t, grad_out, ysel, argmax, sc, sh
     splits = lib.pcops_mlp_wgrad_splits(R, K, K)
     scratch = _f32(splits * (K * K + K), dev)
     gram, xsum = _f32((K, K), dev), _f32(K, dev)
-    _lib.call("pcops_mlp_gram", R, K, Yprev.data_ptr(), K, _p(psc), _p(psh), scratch.data_ptr(),
-              gram.data_ptr(), xsum.data_ptr())
+    if rows is not None:        # X^T diag(w) X and X^T w
+        _lib.call("pcops_mlp_gram_rows", R, K, Yprev.data_ptr(), K, _p(psc), _p(psh), scratch.data_ptr(),
+                  gram.data_ptr(), xsum.data_ptr(), rref)
+    else:
+        _lib.call("pcops_mlp_gram", R, K, Yprev.data_ptr(), K, _p(psc), _p(psh), scratch.data_ptr(),
+                  gram.data_ptr(), xsum.data_ptr())
     dW = _f32((K, N), dev)
     paired = TAIL_FOLD and need_dx
     if paired:
@@ -572,19 +588,34 @@ def _pool_top_backward(R, K, N, S, W, b, p, q, t, grad_out, ysel, argmax, sc, sh
             v = _f32(K, dev)
             _lib.call("pcops_small_gemm", 1, N, K, u.data_ptr(), N, Wt.data_ptr(), K, v.data_ptr(), K)
         G = R // S
-        addend = _f32((G * min(S, N), K), dev)
+        # (compacted rows: the addend is indexed by the compacted row itself)
+        addend = _f32((R if rows is not None else G * min(S, N), K), dev)
         rowmap = torch.empty(R, dtype=torch.int32, device=dev)
-        _lib.call("pcops_mlp_pool_top_addend", R, K, N, S, grad_out.data_ptr(), ysel.data_ptr(), argmax.data_ptr(),
-                  sc.data_ptr(), sh.data_ptr(), p.data_ptr(), Wt.data_ptr(), addend.data_ptr(), rowmap.data_ptr())
         Gprev = _f32((R, K), dev)
         part = _f32((lib.pcops_mlp_stats_rows(R), 2, K), dev) if psc is not None else None
-        _lib.call("pcops_mlp_gemm_dgrad_top", R, K, Yprev.data_ptr(), _p(psc), _p(psh), Mq.data_ptr(),
-                  v.data_ptr(), addend.data_ptr(), addend.shape[0], rowmap.data_ptr(), Gprev.data_ptr(), _p(part))
+        if rows is not None:
+            _lib.call("pcops_mlp_pool_top_addend_rows", R, K, N, S, grad_out.data_ptr(), ysel.data_ptr(),
+                      argmax.data_ptr(), sc.data_ptr(), sh.data_ptr(), p.data_ptr(), Wt.data_ptr(), addend.data_ptr(),
+                      rowmap.data_ptr(), rref)
+            _lib.call("pcops_mlp_gemm_dgrad_top_rows", R, K, Yprev.data_ptr(), _p(psc), _p(psh), Mq.data_ptr(),
+                      v.data_ptr(), addend.data_ptr(), addend.shape[0], rowmap.data_ptr(), Gprev.data_ptr(), _p(part),
+                      rref)
+        else:
+            _lib.call("pcops_mlp_pool_top_addend", R, K, N, S, grad_out.data_ptr(), ysel.data_ptr(), argmax.data_ptr(),
+                      sc.data_ptr(), sh.data_ptr(), p.data_ptr(), Wt.data_ptr(), addend.data_ptr(), rowmap.data_ptr())
+            _lib.call("pcops_mlp_gemm_dgrad_top", R, K, Yprev.data_ptr(), _p(psc), _p(psh), Mq.data_ptr(),
+                      v.data_ptr(), addend.data_ptr(), addend.shape[0], rowmap.data_ptr(), Gprev.data_ptr(), _p(part))
     # weight gradient
     Ssp, cfsum = _f32((K, N), dev), _f32(N, dev)
-    _lib.call("pcops_mlp_pool_top_wsparse", R, K, N, S, grad_out.data_ptr(), ysel.data_ptr(), argmax.data_ptr(),
-              sc.data_ptr(), sh.data_ptr(), p.data_ptr(), Yprev.data_ptr(), _p(psc), _p(psh),
-              Ssp.data_ptr(), cfsum.data_ptr())
+    if rows is not None:
+        wpart = _f32(int(lib.pcops_mlp_pool_top_wsparse_rows_partial(K, N)), dev)
+        _lib.call("pcops_mlp_pool_top_wsparse_rows", R, K, N, S, grad_out.data_ptr(), ysel.data_ptr(), argmax.data_ptr(),
+                  sc.data_ptr(), sh.data_ptr(), p.data_ptr(), Yprev.data_ptr(), _p(psc), _p(psh),
+                  Ssp.data_ptr(), cfsum.data_ptr(), wpart.data_ptr(), rref)
+    else:
+        _lib.call("pcops_mlp_pool_top_wsparse", R, K, N, S, grad_out.data_ptr(), ysel.data_ptr(), argmax.data_ptr(),
+                  sc.data_ptr(), sh.data_ptr(), p.data_ptr(), Yprev.data_ptr(), _p(psc), _p(psh),
+                  Ssp.data_ptr(), cfsum.data_ptr())
     if not paired:
         _lib.call("pcops_small_gemm", K, K, N, gram.data_ptr(), K, Wq.data_ptr(), N, dW.data_ptr(), N)
     if TAIL_FOLD:       # (dW + Ssp) + xsum u^T in place, db = (cfsum + q.(xsum^T W + R b)) + R t: one launch for eleven
@@ -1085,6 +1116,7 @@ CLOUD_POINT = os.environ.get("PCOPS_CLOUD_POINT", "1") != "0"   # dgcnn_bga's he
 EDGE_DIRECT = os.environ.get("PCOPS_EDGE_DIRECT", "1") != "0"   # first EdgeConv layer of a stack on an input without gradient
 EDGE_DIRECT_FUSED = os.environ.get("PCOPS_EDGE_DIRECT_FUSED", "1") != "0"   # ... its E^T Gm inside the one-pass backward above
 POOL_TOP = os.environ.get("PCOPS_POOL_TOP", "1") != "0"     # algebraic backward of pooled top layers (fused_mlp._pool_top_backward)
+POOL_TOP_ROWS = os.environ.get("PCOPS_POOL_TOP_ROWS", "1") != "0"    # ... of the stacks over compacted rows too (the *_rows forms)
 # the step's short generic launches folded into their neighbours (round 6): db out of the FC head's dW launch, the algebraic top
 # layer's operand / closing sums as one launch each, one concatenation for the gradient of a split weight (split_rows), the
 # whole-cloud group's index built once, the smoothed cross entropy as one launch per direction; "0": the torch forms (A/B, tests)

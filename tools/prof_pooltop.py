@@ -11,7 +11,9 @@ from scanobjectnn_amd import _lib, fused_mlp  # noqa: E402
 
 DEV = "cuda:0"
 SHAPES = [("SSG SA3", 256 * 128, 128, 256, [256, 512, 1024]), ("DGCNN agg", 256 * 2048, 256, 320, [1024]),
-          ("DGCNN tconv3", 256 * 2048, 256, 128, [1024])]
+          ("DGCNN tconv3", 256 * 2048, 256, 128, [1024]),
+          # SA2 without row compaction: 32 768 groups of 64 (the compacted stack runs the *_rows forms of the same launches)
+          ("SSG SA2", 256 * 128 * 64, 64, 132, [128, 128, 256])]
 
 
 def layers(k0, widths):
