@@ -74,8 +74,15 @@ int pcops_abi_version(void);
  *                                      (no Q, no Ctr, Y == NULL, moments and stats_partial wanted) takes its statistics from
  *                                      the nine offset moments instead of summing the b m s x c outputs it never stores
  *                                      (opt-in: the statistics agree with float64 to 3e-7, but not bit for bit with the summed form)
+ *   PCOPS_OPT_GRAM_SPLIT_BF16          0 fp32 MFMA / 1 (default): pcops_mlp_gram_rows over compacted rows at Kp == 128 on the bf16
+ *                                      matrix pipe with split operands (six products per block, the column sums stay the fp32
+ *                                      sums of the other form, bit for bit); Kp == 64 and rows == NULL keep the fp32 kernel
+ *   PCOPS_OPT_POOL_TOP_ROWS_PIPELINED  0 / 1 (default): pcops_mlp_pool_top_wsparse_rows over compacted rows software-pipelined (the
+ *                                      next group's rows and coefficients in flight under this group's sums, double-buffered LDS
+ *                                      image, 16-byte LDS reads); same sums in the same order.  pcops_mlp_pool_top_addend_rows
+ *                                      keeps its one form under either value
  * pcops_set_option returns the PREVIOUS value (>= 0) or PCOPS_ERR_BAD_ARGUMENT.  The environment variables of rounds 3-4
- * (PCOPS_GEMM_BF3, PCOPS_WGRAD_BF3, PCOPS_BWD_FUSED_DX3, PCOPS_KNN_F16; round 6: PCOPS_DGRAD_BF3, PCOPS_BWD_FUSED_GW) only seed the initial values (test overrides). */
+ * (PCOPS_GEMM_BF3, PCOPS_WGRAD_BF3, PCOPS_BWD_FUSED_DX3, PCOPS_KNN_F16; round 6: PCOPS_DGRAD_BF3, PCOPS_BWD_FUSED_GW; later: PCOPS_GRAM_BF3, PCOPS_POOL_TOP_ROWS_PIPE) only seed the initial values (test overrides). */
 typedef enum pcops_option {
     PCOPS_OPT_GEMM_SPLIT_BF16 = 1,
     PCOPS_OPT_WGRAD_SPLIT_BF16 = 2,
@@ -85,7 +92,9 @@ typedef enum pcops_option {
     PCOPS_OPT_BWD_FUSED_GRAM_WGRAD = 6,
     PCOPS_OPT_SCATTER_QFORM = 7,
     PCOPS_OPT_XYZ_STATS_MOMENTS = 8,
-    PCOPS_OPT_COUNT = 9
+    PCOPS_OPT_GRAM_SPLIT_BF16 = 9,
+    PCOPS_OPT_POOL_TOP_ROWS_PIPELINED = 10,
+    PCOPS_OPT_COUNT = 11
 } pcops_option;
 int pcops_set_option(int option, int value);
 int pcops_get_option(int option);

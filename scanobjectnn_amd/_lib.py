@@ -294,6 +294,8 @@ OPT_GEMM_SPLIT_BF16, OPT_WGRAD_SPLIT_BF16, OPT_BWD_FUSED_DX_SPLIT_BF16, OPT_KNN_
 OPT_DGRAD_SPLIT_BF16, OPT_BWD_FUSED_GRAM_WGRAD = 5, 6            # round 6
 OPT_SCATTER_QFORM = 7                                            # pcops_sa_scatter_bwd(_rows): Q form of the chunked walk
 OPT_XYZ_STATS_MOMENTS = 8                                        # pcops_sa_gather_fwd(_rows): arithmetic first layer's statistics
+OPT_GRAM_SPLIT_BF16 = 9                                          # pcops_mlp_gram_rows at Kp == 128: split operands on the bf16 pipe
+OPT_POOL_TOP_ROWS_PIPELINED = 10                                 # pcops_mlp_pool_top_wsparse_rows: software-pipelined kernel
 
 
 def set_option(option, value):

@@ -61,6 +61,8 @@ void options_init() {
         g_options[PCOPS_OPT_BWD_FUSED_GRAM_WGRAD].store(env_int("PCOPS_BWD_FUSED_GW", 0) != 0);
         g_options[PCOPS_OPT_SCATTER_QFORM].store(env_int("PCOPS_SCATTER_QFORM", 1) != 0);
         g_options[PCOPS_OPT_XYZ_STATS_MOMENTS].store(env_int("PCOPS_XYZ_STATS_MOMENTS", 0) != 0);
+        g_options[PCOPS_OPT_GRAM_SPLIT_BF16].store(env_int("PCOPS_GRAM_BF3", 1) != 0);
+        g_options[PCOPS_OPT_POOL_TOP_ROWS_PIPELINED].store(env_int("PCOPS_POOL_TOP_ROWS_PIPE", 1) != 0);
         g_options_init.store(1, std::memory_order_release);
     }
     busy.clear(std::memory_order_release);

@@ -4317,6 +4317,222 @@ __global__ __launch_bounds__(512, 1) void gram_full_kernel(GramArgs a) {
     }
 }
 
+// ---- the compacted-row Gram matrix on the bf16 matrix pipe with split operands (PCOPS_OPT_GRAM_SPLIT_BF16, KP = 128 only; KP = 64
+// keeps gram_full_kernel).  The producers of gram_full_kernel<4, true, true> -- same loads, same BN + ReLU, same sqrt(w) on a
+// block's first row, same fp32 column sums in the same order -- split every staged value into its three bf16 pieces (split3_pair)
+// and hand the stripe over TRANSPOSED, T[piece][slot][k]: both operand sides of X^T X are the same stripe with k = its rows, so
+// ONE image serves the A and the B fragments of v_mfma_f32_32x32x16_bf16 (one ds_read_b128 per piece, block and 16 rows).  The
+// fp32 stripe is gone.
+//   slot of column c   = 32 (c % 4) + c / 4: a producer lane's float4 goes to four slot BLOCKS at the same offset, so the 8-byte
+//                        stores of a 16-lane group fall on 8 distinct bank pairs (2-way; slot = column would be 8-way)
+//   k of stripe row r  = 4 (r % 8) + r / 8: a lane's four rows r0, r0 + 8, r0 + 16, r0 + 24 (the assignment the column sums'
+//                        order is tied to) are consecutive k, one 8-byte store per column and piece.  A sum over k does not
+//                        care which row carries which label as long as both sides agree -- and they are one image
+//   slot stride        = 40 bf16 (80 bytes = 5 sixteen-byte units, odd): the 16 lanes of a ds_read_b128 group hold 16 different
+//                        slots mod 16 and meet 16 different units of the 256-byte bank row
+// Slot block (i, j), i <= j, holds the products of columns = i mod 4 with columns = j mod 4; it is written to the partial copy
+// at (row, column) AND (column, row), so every element of the partial is defined and its upper triangle -- all that
+// mirror_lower_kernel reads -- is complete.  Per block and 16 rows the six products h h | h m, m h, h l, l h, m m, the large one in
+// the block's accumulator and the five small ones in a second one: 12 MFMAs of 32 cycles per block and
+// stripe where the fp32 kernel runs 16 of 64.  The ten blocks are dealt 3 / 3 / 2 / 2 over the four consumer waves so that a
+// wave reads at most three slot blocks (18 ds_read_b128 against 36 MFMAs per stripe).
+constexpr int gbf_nb(int w) { return w < 2 ? 3 : 2; }
+constexpr int gbf_i(int w, int b) { return w == 0 ? 0 : (w == 1 ? 1 : (w == 2 ? (b == 0 ? 0 : 3) : 2)); }
+constexpr int gbf_j(int w, int b) { return w == 0 ? b : (w == 1 ? 1 + b : (w == 2 ? 3 : 2 + b)); }
+constexpr bool gbf_used(int w, int blk) {
+    for (int b = 0; b < gbf_nb(w); ++b)
+        if (gbf_i(w, b) == blk || gbf_j(w, b) == blk) return true;
+    return false;
+}
+
+template <int KP>
+__global__ __launch_bounds__(512, 1) void gram_rows_bf3_kernel(GramArgs a) {
+    static_assert(KP == 128, "four slot blocks: the deal below");
+    constexpr int RS = 32, K4 = KP / 4, NV = RS * K4 / 256;
+    constexpr int RSP = 40, PSZ = KP * RSP, TBUF = 3 * PSZ;         // bf16 per slot / piece / stripe image
+    static_assert(NV == 4 && 256 % K4 == 0, "a producer lane holds rows r0 + 8 j of ONE column quad");
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    wave_prio_consumer(wave < 4);
+    const long long M = (long long)__builtin_amdgcn_readfirstlane(*a.Mdev);
+    const int grp = blockIdx.x, ngrp = gridDim.x;
+    float *coef = lds;                                              // [2][KP]
+    __bf16 *Tp = reinterpret_cast<__bf16 *>(coef + 2 * KP);         // [2][3][KP][RSP]  | afterwards: column-sum scratch [256 NV][4]
+    for (int e = tid; e < KP; e += 512) {
+        coef[e] = a.asc[e];
+        coef[KP + e] = a.ash[e];
+    }
+    __syncthreads();
+    const long long nstripes = (M + RS - 1) / RS;
+    const long long cnt = grp < nstripes ? (nstripes - grp + ngrp - 1) / ngrp : 0;
+
+    if (wave >= 4) {
+        // ------------------------------------------------------------------ producers: whole rows of X, two stripes in flight
+        const int pt = tid - 256;
+        const int c = (pt % K4) * 4, r0 = pt / K4;                  // column quad, first row of the lane (rows r0 + 8 j)
+        const float4 sc = *reinterpret_cast<const float4 *>(&coef[c]);
+        const float4 sh = *reinterpret_cast<const float4 *>(&coef[KP + c]);
+        float4 pxa[NV], pxb[NV];                                    // (named sets: an array of sets went to scratch elsewhere)
+        float cs[NV][4];
+#pragma unroll
+        for (int j = 0; j < NV; ++j) cs[j][0] = cs[j][1] = cs[j][2] = cs[j][3] = 0.f;
+        auto issue = [&](float4 (&px)[NV], long long stripe) {
+            const long long row0 = stripe * RS;
+            const __amdgpu_buffer_rsrc_t rx = make_rsrc(a.X + row0 * a.ldx, (M - row0) * a.ldx * 4);
+#pragma unroll
+            for (int j = 0; j < NV; ++j) px[j] = buf_load4(rx, (unsigned)((r0 + 8 * j) * a.ldx + c) * 4u, 0u);
+        };
+        auto stage = [&](const float4 (&px)[NV], long long stripe, __bf16 *dst) {
+            const long long row0 = stripe * RS;
+            float sw[2];                                            // sqrt(weight) of rows 0 / 16 of the stripe
+            const long long nblk = (M + kBlk - 1) / kBlk;
+#pragma unroll
+            for (int hb = 0; hb < 2; ++hb) {
+                long long bi = stripe * 2 + hb;
+                bi = bi < nblk ? bi : nblk - 1;
+                sw[hb] = sqrtf(uniform_block(a.blocks, bi).w);
+            }
+            float4 xt[NV];
+#pragma unroll
+            for (int j = 0; j < NV; ++j) {
+                const int r = r0 + 8 * j;
+                float4 x = px[j];
+                x.x = fmaxf(fmaf(x.x, sc.x, sh.x), 0.f); x.y = fmaxf(fmaf(x.y, sc.y, sh.y), 0.f);
+                x.z = fmaxf(fmaf(x.z, sc.z, sh.z), 0.f); x.w = fmaxf(fmaf(x.w, sc.w, sh.w), 0.f);
+                if (!(row0 + r < M)) x = make_float4(0.f, 0.f, 0.f, 0.f);   // (relu(shift) of a padded row)
+                if ((j & 1) == 0 && r0 == 0) {                      // rows 0 and 16 of the stripe open a block (j = 0, 2 of r0 = 0)
+                    const float w = sw[j >> 1];
+                    x.x *= w; x.y *= w; x.z *= w; x.w *= w;
+                    cs[j][0] = fmaf(w, x.x, cs[j][0]); cs[j][1] = fmaf(w, x.y, cs[j][1]);
+                    cs[j][2] = fmaf(w, x.z, cs[j][2]); cs[j][3] = fmaf(w, x.w, cs[j][3]);
+                } else {
+                    cs[j][0] += x.x; cs[j][1] += x.y; cs[j][2] += x.z; cs[j][3] += x.w;
+                }
+                xt[j] = x;
+            }
+            typedef __bf16 bf16x4_ __attribute__((ext_vector_type(4)));
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float v0 = e == 0 ? xt[0].x : (e == 1 ? xt[0].y : (e == 2 ? xt[0].z : xt[0].w));
+                const float v1 = e == 0 ? xt[1].x : (e == 1 ? xt[1].y : (e == 2 ? xt[1].z : xt[1].w));
+                const float v2 = e == 0 ? xt[2].x : (e == 1 ? xt[2].y : (e == 2 ? xt[2].z : xt[2].w));
+                const float v3 = e == 0 ? xt[3].x : (e == 1 ? xt[3].y : (e == 2 ? xt[3].z : xt[3].w));
+                bf16x2 h0, m0, l0, h1, m1, l1;
+                split3_pair(v0, v1, h0, m0, l0);
+                split3_pair(v2, v3, h1, m1, l1);
+                __bf16 *d = dst + (32 * e + (c >> 2)) * RSP + 4 * r0;
+                const bf16x4_ hv = {h0.x, h0.y, h1.x, h1.y}, mv = {m0.x, m0.y, m1.x, m1.y}, lv = {l0.x, l0.y, l1.x, l1.y};
+                *reinterpret_cast<bf16x4_ *>(d) = hv;
+                *reinterpret_cast<bf16x4_ *>(d + PSZ) = mv;
+                *reinterpret_cast<bf16x4_ *>(d + 2 * PSZ) = lv;
+            }
+        };
+        // a stripe beyond the last one gets a descriptor of zero records (make_rsrc): its loads fetch nothing and return
+        // zeros, so issue() is unconditional and the two sets always alternate -- the waits on a set are counted (vmcnt(4 ..)),
+        // which a branch on the set's parity inside the loop turned into waits for BOTH sets
+        issue(pxa, grp);
+        issue(pxb, grp + ngrp);
+        if (cnt > 0) stage(pxa, grp, Tp);
+        issue(pxa, grp + 2ll * ngrp);
+        __syncthreads();
+        // stripe i + 1 is staged out of its register set while the consumers work on stripe i; the set goes to stripe i + 3 at once.
+        // Two stripes per trip, both unconditional, and the last one or two stripes behind the loop: one barrier per stripe in all.
+        // Barriers of either branch of the workgroup: 1 (coefficients) + 1 (stripe 0 staged) + cnt (one per stripe: 2 per trip here,
+        // then 0, 1 or 2 behind the loop) + 2 (column sums); the consumers' run() counts the same 1 + 1 + cnt + 2
+        long long i = 0;
+        for (; i + 2 < cnt; i += 2) {
+            stage(pxb, grp + (i + 1) * ngrp, Tp + TBUF);
+            issue(pxb, grp + (i + 3) * ngrp);
+            __syncthreads();
+            stage(pxa, grp + (i + 2) * ngrp, Tp);
+            issue(pxa, grp + (i + 4) * ngrp);
+            __syncthreads();
+        }
+        if (i + 1 < cnt) {
+            stage(pxb, grp + (i + 1) * ngrp, Tp + TBUF);
+            __syncthreads();
+        }
+        if (cnt > 0) __syncthreads();
+        // column sums: as in gram_full_kernel (element idx = pt + 256 j of the [RS][K4] grid, one thread per column, fixed order)
+        float *scr = reinterpret_cast<float *>(Tp);                 // [256 NV][4]
+#pragma unroll
+        for (int j = 0; j < NV; ++j)
+            *reinterpret_cast<float4 *>(&scr[(pt + 256 * j) * 4]) = make_float4(cs[j][0], cs[j][1], cs[j][2], cs[j][3]);
+        __syncthreads();
+        for (int e = pt; e < KP; e += 256) {
+            float sum = 0.f;
+            for (int idx = e >> 2; idx < 256 * NV; idx += K4) sum += scr[idx * 4 + (e & 3)];
+            a.xpart[(long long)grp * KP + e] = sum;
+        }
+        __syncthreads();
+    } else {
+        // ------------------------------------------------------------------ consumers: the ten slot blocks, 3 / 3 / 2 / 2
+        const int half = lane >> 5, li = lane & 31;
+        auto run = [&](auto wv_) {
+            constexpr int WV = decltype(wv_)::value;
+            constexpr int NB_ = gbf_nb(WV);
+            f32x16 acc[NB_], sm[NB_];
+#pragma unroll
+            for (int b = 0; b < NB_; ++b)
+#pragma unroll
+                for (int v = 0; v < 16; ++v) acc[b][v] = sm[b][v] = 0.f;
+            __syncthreads();
+            for (long long i = 0; i < cnt; ++i) {
+                // fragment of (slot block, piece, 16-row step s): slot 32 blk + li, k = 16 s + 8 half .. + 7
+                const __bf16 *tb = Tp + (i & 1) * TBUF + li * RSP + 8 * half;
+                bf16x8 f[2][4][3];
+#pragma unroll
+                for (int s = 0; s < 2; ++s)
+#pragma unroll
+                    for (int blk = 0; blk < 4; ++blk)
+#pragma unroll
+                        for (int pc = 0; pc < 3; ++pc)
+                            if (gbf_used(WV, blk))
+                                f[s][blk][pc] = *reinterpret_cast<const bf16x8 *>(tb + pc * PSZ + 32 * blk * RSP + 16 * s);
+                __builtin_amdgcn_sched_barrier(0);
+                // one product at a time over the blocks: consecutive matrix instructions do not share an accumulator
+#define PCOPS_GMM(S_, A_, B_, C_)                                                                          \
+    _Pragma("unroll") for (int b = 0; b < NB_; ++b)                                                        \
+        C_[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f[S_][gbf_i(WV, b)][A_], f[S_][gbf_j(WV, b)][B_], C_[b], 0, 0, 0)
+#pragma unroll
+                for (int s = 0; s < 2; ++s) {
+                    PCOPS_GMM(s, 2, 0, sm);
+                    PCOPS_GMM(s, 0, 2, sm);
+                    PCOPS_GMM(s, 1, 1, sm);
+                    PCOPS_GMM(s, 1, 0, sm);
+                    PCOPS_GMM(s, 0, 1, sm);
+                    PCOPS_GMM(s, 0, 0, acc);
+                }
+#undef PCOPS_GMM
+                __builtin_amdgcn_sched_barrier(0);
+                __syncthreads();
+            }
+            // acc[b][v]: slot (v & 3) + 8 (v >> 2) + 4 half of block i (A side) x slot li of block j (B side); slot s of block e is
+            // column 4 s + e
+            float *out = a.part + (long long)grp * KP * KP;
+#pragma unroll
+            for (int b = 0; b < NB_; ++b) {
+                const int bi = gbf_i(WV, b), bj = gbf_j(WV, b);
+                const int cb = 4 * li + bj;
+#pragma unroll
+                for (int v = 0; v < 16; ++v) {
+                    const int ca = 4 * ((v & 3) + 8 * (v >> 2) + 4 * half) + bi;
+                    const float val = acc[b][v] + sm[b][v];
+                    out[ca * KP + cb] = val;
+                    if (bi != bj) out[cb * KP + ca] = val;
+                }
+            }
+            __syncthreads();               // the producers' two column-sum barriers
+            __syncthreads();
+        };
+        if (wave == 0) run(std::integral_constant<int, 0>{});
+        else if (wave == 1) run(std::integral_constant<int, 1>{});
+        else if (wave == 2) run(std::integral_constant<int, 2>{});
+        else run(std::integral_constant<int, 3>{});
+    }
+}
+
 // lower triangle of a symmetric K x K result from its upper one
 static __global__ __launch_bounds__(256) void mirror_lower_kernel(int K, float *__restrict__ g) {
     const int i = blockIdx.x, tid = threadIdx.x;
@@ -5087,6 +5303,97 @@ __global__ __launch_bounds__(256) void pool_top_wsparse_rows_kernel(int G, int C
     }
 }
 
+// wsparse, software-pipelined (PCOPS_OPT_POOL_TOP_ROWS_PIPELINED = 1): the same thread = channel walk, but the NEXT group's rows
+// (NR float4 per thread), its (gout, ysel, arg) triple and the block_start pair of the group after it are requested into
+// registers before this group's accumulation, the LDS image is double-buffered (ONE barrier per group: a buffer is rewritten two
+// groups later, behind the barrier that follows its last read), and a hit row is read with KP / 4 ds_read_b128 -- row stride
+// KP + 4 floats = an odd number of 16-byte units, so the lanes of a read group that hold different rows mod 16 meet different
+// units of the bank row (KP + 1 is the stride for ds_read_b32).  Same partition of the groups over the grid, same partial layout.
+template <int KP, int NR>
+__global__ __launch_bounds__(256) void pool_top_wsparse_rows_pipe_kernel(int G, int C, int maxr, const float *__restrict__ gout,
+                                                                         const float *__restrict__ ysel,
+                                                                         const unsigned char *__restrict__ arg,
+                                                                         const float *__restrict__ sc, const float *__restrict__ sh,
+                                                                         const float *__restrict__ p,
+                                                                         const float *__restrict__ Yprev,
+                                                                         const float *__restrict__ psc, const float *__restrict__ psh,
+                                                                         const int *__restrict__ block_start,
+                                                                         float *__restrict__ part, float *__restrict__ part2) {
+    constexpr int LD = KP + 4, K4 = KP / 4, RPP = 256 / K4;       // rows staged per pass of the workgroup
+    static_assert(NR * RPP == 64 || NR * RPP == 128, "the launcher sizes an LDS image at 64 or 128 rows (maxr <= NR RPP)");
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int tid = threadIdx.x, c = tid;                         // C <= 256
+    const float scc = c < C ? sc[c] : 0.f, shc = c < C ? sh[c] : 0.f, pc = c < C ? p[c] : 0.f;
+    const int k4 = tid % K4, r0 = tid / K4;
+    const float4 asc = *reinterpret_cast<const float4 *>(psc + 4 * k4), ash = *reinterpret_cast<const float4 *>(psh + 4 * k4);
+    float acc[KP];
+#pragma unroll
+    for (int k = 0; k < KP; ++k) acc[k] = 0.f;
+    float csum = 0.f;
+    const int grid = gridDim.x;
+    // the group in flight: its rows, its raw triple (the coefficient is formed at use, not behind the load) and its row count
+    float4 px[NR];
+    float fy = 0.f, fg = 0.f;
+    int fa = 0, fn = 0;
+    int nb0 = 0, nb1 = 0;                                         // block_start pair of the group fetch() takes next
+    auto pair = [&](int g) {
+        if (g < G) { nb0 = block_start[g]; nb1 = block_start[g + 1]; }
+    };
+    // every request is unconditional: rows beyond the group's (and every row of a group beyond the last) lie outside the
+    // buffer descriptor and read as zeros, the triple is read at a clamped index and dropped at use (fn == 0, c >= C)
+    auto fetch = [&](int g) {
+        const int n = g < G ? kBlk * (nb1 - nb0) : 0;
+        fn = n < maxr ? n : maxr;
+        const __amdgpu_buffer_rsrc_t rx = make_rsrc(Yprev + (long long)kBlk * (g < G ? nb0 : 0) * KP, (long long)fn * KP * 4);
+#pragma unroll
+        for (int j = 0; j < NR; ++j) px[j] = buf_load4(rx, (unsigned)((r0 + RPP * j) * KP + 4 * k4) * 4u, 0u);
+        const long long e = (long long)(g < G ? g : G - 1) * C + (c < C ? c : C - 1);
+        fy = ysel[e]; fg = gout[e]; fa = arg[e];
+    };
+    int g = blockIdx.x;
+    pair(g);
+    fetch(g);
+    pair(g + grid);
+    int buf = 0;
+    for (; g < G; g += grid) {
+        float *Xs = lds + buf * (NR * RPP * LD);                  // [NR RPP][LD]: a row beyond the group's arrives as zeros and is stored as relu(shift); never read (row < fn below)
+        int t0 = 0, t1 = 0;                                       // block_start pair of the group after the next (scalar loads: requested
+        if (g + 2 * grid < G) {                                   // here, so that the barrier below does not wait for them)
+            t0 = block_start[g + 2 * grid];
+            t1 = block_start[g + 2 * grid + 1];
+        }
+#pragma unroll
+        for (int j = 0; j < NR; ++j) {
+            const int r = r0 + RPP * j;
+            float4 x = px[j];
+            x.x = fmaxf(fmaf(x.x, asc.x, ash.x), 0.f); x.y = fmaxf(fmaf(x.y, asc.y, ash.y), 0.f);
+            x.z = fmaxf(fmaf(x.z, asc.z, ash.z), 0.f); x.w = fmaxf(fmaf(x.w, asc.w, ash.w), 0.f);
+            *reinterpret_cast<float4 *>(&Xs[r * LD + 4 * k4]) = x;
+        }
+        float cfv = fmaf(fy, scc, shc) > 0.f ? pc * fg : 0.f;
+        int row = fa;
+        if (row >= fn || c >= C) { row = 0; cfv = 0.f; }
+        fetch(g + grid);                                          // the next group flies under this group's accumulation
+        nb0 = t0; nb1 = t1;
+        __syncthreads();
+        const float *xr = &Xs[row * LD];
+#pragma unroll
+        for (int q = 0; q < K4; ++q) {
+            const float4 v = *reinterpret_cast<const float4 *>(xr + 4 * q);
+            acc[4 * q] = fmaf(cfv, v.x, acc[4 * q]); acc[4 * q + 1] = fmaf(cfv, v.y, acc[4 * q + 1]);
+            acc[4 * q + 2] = fmaf(cfv, v.z, acc[4 * q + 2]); acc[4 * q + 3] = fmaf(cfv, v.w, acc[4 * q + 3]);
+        }
+        csum += cfv;
+        buf ^= 1;
+    }
+    if (c < C) {
+        float *dst = part + (long long)blockIdx.x * KP * C + c;
+#pragma unroll
+        for (int k = 0; k < KP; ++k) dst[(long long)k * C] = acc[k];
+        part2[(long long)blockIdx.x * C + c] = csum;
+    }
+}
+
 // C [M][N] = A [M][K] B [K][N] for the SMALL products around the big kernels (weights x weights: K x K Gram algebra,
 // matrix-vector rows).  One 32 x 32 tile per workgroup so that even a 512 x 512 result fills the chip; the 4 waves split
 // K and add their accumulators through LDS in a fixed order.  (Eight waves over K for the long reductions -- the partial tiles
@@ -5205,6 +5512,7 @@ PCOPS_HIDDEN int bwd_fused_launch(WgradArgs &a, bool xyz, int groups, float *par
                                   bool side = false, const float *gw_bias = nullptr);
 PCOPS_HIDDEN int gram_full_launch(GramArgs &g, int nbk, bool bnrelu, int gg, size_t lds, hipStream_t st);
 PCOPS_HIDDEN int gram_full_rows_launch(GramArgs &g, int nbk, int gg, size_t lds, hipStream_t st);
+PCOPS_HIDDEN int gram_rows_bf3_launch(GramArgs &g, int gg, hipStream_t st);
 
 static int wgrad_legacy_splits(long long M, int K, int N) {
     const int kb = (K + 63) / 64, nb = (N + 127) / 128;
@@ -5510,6 +5818,17 @@ int gram_full_launch(GramArgs &g, int nbk, bool bnrelu, int gg, size_t lds, hipS
 int gram_full_rows_launch(GramArgs &g, int nbk, int gg, size_t lds, hipStream_t st) {
     auto kern = nbk == 2 ? gram_full_kernel<2, true, true> : gram_full_kernel<4, true, true>;
     if (nbk != 2 && nbk != 4) return PCOPS_ERR_UNSUPPORTED;
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) !=
+        hipSuccess)
+        return PCOPS_ERR_LAUNCH;
+    hipLaunchKernelGGL(kern, dim3(gg), dim3(512), lds, st, g);
+    return PCOPS_OK;
+}
+
+// ... on the bf16 matrix pipe with split operands (gram_rows_bf3_kernel: Kp = 128, ldx % 4 == 0 -- checked by the caller)
+int gram_rows_bf3_launch(GramArgs &g, int gg, hipStream_t st) {
+    const size_t lds = 2 * 128 * sizeof(float) + (size_t)2 * 3 * 128 * 40 * 2;
+    auto kern = gram_rows_bf3_kernel<128>;
     if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) !=
         hipSuccess)
         return PCOPS_ERR_LAUNCH;
@@ -6445,8 +6764,30 @@ int pcops_mlp_pool_top_wsparse_rows(int M, int Kp, int N, int S, const float *go
         hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, G, N, S, gout, ysel, argmax, pool_scale, pool_shift, p, \
                            Yprev, prev_scale, prev_shift, rows->block_start, partial, part2);               \
     } while (0)
-    if (Kp == 64) PCOPS_WSPR_LAUNCH(64);
+    // PCOPS_OPT_POOL_TOP_ROWS_PIPELINED = 1 (default): the software-pipelined kernel (both widths; NR = the float4 a thread
+    // holds of a group of S rows).  Same grid, so pcops_mlp_pool_top_wsparse_rows_partial covers both.
+    // two images of NR x (256 / (Kp / 4)) = 64 or 128 rows each: every row a group can have, because
+    // pcops_mlp_pool_top_rows_supported (checked above) caps S at 128
+    const int img_rows = S <= 64 ? 64 : 128;
+    if (S > img_rows) return PCOPS_ERR_UNSUPPORTED;
+    const size_t lds_pipe = (size_t)2 * img_rows * (Kp + 4) * sizeof(float);
+#define PCOPS_WSPP_LAUNCH(KP_, NR_)                                                                         \
+    do {                                                                                                    \
+        auto kern = pool_top_wsparse_rows_pipe_kernel<KP_, NR_>;                                            \
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, \
+                                160 * 1024) != hipSuccess)                                                  \
+            return PCOPS_ERR_LAUNCH;                                                                        \
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds_pipe, st, G, N, S, gout, ysel, argmax, pool_scale, pool_shift, p, \
+                           Yprev, prev_scale, prev_shift, rows->block_start, partial, part2);               \
+    } while (0)
+    if (pcops_get_option(PCOPS_OPT_POOL_TOP_ROWS_PIPELINED) != 0) {
+        if (Kp == 64 && S <= 64) PCOPS_WSPP_LAUNCH(64, 4);
+        else if (Kp == 64) PCOPS_WSPP_LAUNCH(64, 8);
+        else if (S <= 64) PCOPS_WSPP_LAUNCH(128, 8);
+        else PCOPS_WSPP_LAUNCH(128, 16);
+    } else if (Kp == 64) PCOPS_WSPR_LAUNCH(64);
     else PCOPS_WSPR_LAUNCH(128);
+#undef PCOPS_WSPP_LAUNCH
 #undef PCOPS_WSPR_LAUNCH
     int rc = pcops_launch_status();
     if (rc) return rc;
@@ -6495,8 +6836,12 @@ int pcops_mlp_gram_rows(long long M, int Kp, const float *Yprev, int ldx, const 
                   static_cast<const RowBlock *>(rows->blocks), rows->rows};
     const int nbk = Kp / 32;
     const size_t lds = (size_t)(2 * 32 * nbk + 2 * 32 * (32 * nbk + 4)) * sizeof(float);
-    const int rcl = gram_full_rows_launch(g, nbk, gg, lds, st);
+    // PCOPS_OPT_GRAM_SPLIT_BF16 = 1 (default): Kp = 128 on the bf16 matrix pipe with split operands (gram_rows_bf3_kernel); Kp = 64
+    // keeps the fp32 kernel under either value (two blocks a side: three upper blocks over four waves, nothing to deal better)
+    const bool bf3 = Kp == 128 && pcops_get_option(PCOPS_OPT_GRAM_SPLIT_BF16) != 0;
+    const int rcl = bf3 ? gram_rows_bf3_launch(g, gg, st) : gram_full_rows_launch(g, nbk, gg, lds, st);
     if (rcl) return rcl;
+    if (bf3) pcops_note_pipe(1);
     int rc = pcops_launch_status();
     if (rc) return rc;
     const long long L = (long long)Kp * Kp;

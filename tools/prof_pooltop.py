@@ -1,5 +1,7 @@
 """Per-call HIP-event timings of the algebraic top-layer backward (fused_mlp._pool_top_backward) against the plain
-dgrad + wgrad it replaces, at the benchmark shapes.  python tools/prof_pooltop.py"""
+dgrad + wgrad it replaces, at the benchmark shapes; then SA2's compacted case: pcops_mlp_gram_rows and
+pcops_mlp_pool_top_wsparse_rows alone, HIP events around the entry point, under both values of PCOPS_OPT_GRAM_SPLIT_BF16 /
+PCOPS_OPT_POOL_TOP_ROWS_PIPELINED.  python tools/prof_pooltop.py [--rows-only]"""
 import collections
 import os
 import sys
@@ -52,7 +54,63 @@ class Timer:
         print("    sum %.1f us" % tot)
 
 
-for name, R, S, k0, widths in SHAPES:
+def rows_case(reps=20):
+    """SSG SA2 over compacted rows: 32 768 groups of 24 .. 64 members in S = 64 slots, Kp = 128, N = 256"""
+    lib = _lib.load()
+    S, Kp, N, G = 64, 128, 256, 32768
+    g = torch.Generator().manual_seed(1)
+    cnt = torch.randint(24, 65, (G,), generator=g, dtype=torch.int32)
+    rows = _lib.Rows(cnt.view(256, 128).to(DEV), S)
+    R = G * S
+    print("SSG SA2, compacted: %d rows of %d, S %d, %d -> %d" % (rows.num_rows(), R, S, Kp, N))
+    Yprev = torch.randn(R, Kp, generator=g).to(DEV)
+    psc, psh = (0.5 + torch.rand(Kp, generator=g)).to(DEV), (0.3 * torch.randn(Kp, generator=g)).to(DEV)
+    splits = lib.pcops_mlp_wgrad_splits(R, Kp, Kp)
+    scratch, gram, xsum = (torch.empty(n, device=DEV) for n in (splits * (Kp * Kp + Kp), Kp * Kp, Kp))
+    gout, ysel = torch.randn(G, N, generator=g).to(DEV), torch.randn(G, N, generator=g).to(DEV)
+    nrow = 16 * ((cnt.long() + 15) // 16)
+    arg8 = (torch.rand(G, N, generator=g) * nrow.view(G, 1)).long().clamp_(max=255).to(torch.uint8).to(DEV)
+    sc, sh, p = ((0.5 + torch.rand(N, generator=g)).to(DEV), (0.2 * torch.randn(N, generator=g)).to(DEV),
+                 (0.5 + torch.rand(N, generator=g)).to(DEV))
+    Ssp, cfsum = torch.empty(Kp, N, device=DEV), torch.empty(N, device=DEV)
+    wpart = torch.empty(int(lib.pcops_mlp_pool_top_wsparse_rows_partial(Kp, N)), device=DEV)
+
+    def gram_call():
+        _lib.call("pcops_mlp_gram_rows", R, Kp, Yprev.data_ptr(), Kp, psc.data_ptr(), psh.data_ptr(), scratch.data_ptr(),
+                  gram.data_ptr(), xsum.data_ptr(), rows.ref)
+
+    def ws_call():
+        _lib.call("pcops_mlp_pool_top_wsparse_rows", R, Kp, N, S, gout.data_ptr(), ysel.data_ptr(), arg8.data_ptr(),
+                  sc.data_ptr(), sh.data_ptr(), p.data_ptr(), Yprev.data_ptr(), psc.data_ptr(), psh.data_ptr(),
+                  Ssp.data_ptr(), cfsum.data_ptr(), wpart.data_ptr(), rows.ref)
+
+    def timeit(f):
+        for _ in range(3):
+            f()
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(reps):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            f()
+            b.record()
+            torch.cuda.synchronize()
+            ts.append(a.elapsed_time(b) * 1e3)
+        ts.sort()
+        return ts[0], ts[len(ts) // 2], ts[-1]
+
+    for label, option, f in (("gram_rows (gram + partial sum + mirror)", _lib.OPT_GRAM_SPLIT_BF16, gram_call),
+                             ("wsparse_rows (walk + partial sum)", _lib.OPT_POOL_TOP_ROWS_PIPELINED, ws_call)):
+        prev = _lib.get_option(option)
+        try:
+            for value in (0, 1, 0, 1):
+                _lib.set_option(option, value)
+                print("    %-42s option %d: min %6.1f median %6.1f max %6.1f us" % ((label, value) + timeit(f)))
+        finally:
+            _lib.set_option(option, prev)
+
+
+for name, R, S, k0, widths in ([] if "--rows-only" in sys.argv else SHAPES):
     x = torch.randn(R, k0, device=DEV).requires_grad_(True)
     ls = layers(k0, widths)
     for mode in (True, False):
@@ -68,3 +126,5 @@ for name, R, S, k0, widths in SHAPES:
                 _lib._hooks.remove(tm)
                 print("%s rows %d S %d %d -> %s  %s" % (name, R, S, k0, widths, "algebraic" if mode else "plain"))
                 tm.report()
+
+rows_case()
