@@ -106,6 +106,19 @@ int pcops_last_launch_pipe(void);
  *              4 / 5 / 6 / 7 weight gradient: split-operand / producer-consumer / wave-stream / legacy split-K kernel,
  *              8 / 9 pcops_sa_scatter_bwd(_rows) over the inverse index: chunked walk with atomics ([1] = 1: its Q form,
  *              [2] sorted rows per chunk, [4] = 4 compacted rows) / owner walk (deterministic mode)
+ *              10..13 the EdgeConv family (csrc/edgeconv.hip and its launchers); their fields are their own:
+ *              10 pcops_edge_pool_fwd(_ld):  [1] kernel: 0 generic, 1 64-group chunks over L2 (ec_fwd_kernel<0>), 2 LDS-resident
+ *                 slice (ec_fwd_lds_kernel);  [2] rows of stats_partial written (0 without statistics);  [3] 1 for the instance
+ *                 of kernels 1 / 2 that sums groups of more than 20 neighbours in blocks of 16;  [4] 1 for the _ld form
+ *              11 pcops_edge_pool_bwd(_ld):  [1] 0 global atomics, 1 generic owner pair, 2 ordered owner pair (deterministic
+ *                 mode), 3 arg-row kernel + inverse index + owner walk of edgeconv.hip, 4 the one-walk kernel
+ *                 (PCOPS_EDGECONV_BWD_FUSED=1);  [2] the walk: 0 none of edgeconv.hip's, 1 lists read from global memory
+ *                 (ec_walk_kernel), 2 LDS-resident (ec_walk_lds_kernel);  [3] 1 when the inverse index was assembled in LDS as
+ *                 16-bit codes (ec_csr_build_kernel<true>);  [4] 1 for the _ld form
+ *              12 the Q + Ctr form of pcops_sa_gather_fwd with a stored Y (ec_fwd_kernel<1>): [2] rows of stats_partial,
+ *                 [4] 1 for pcops_sa_gather_fwd_ld
+ *              13 the Q + Ctr form of pcops_sa_scatter_bwd (ec_tnet_ctr_kernel + ec_walk_kernel<true>): [2], [3] as for 11,
+ *                 [4] 1 for pcops_sa_scatter_bwd_ld
  *   [1] split  1 when the operands are split into bf16 pieces (the one-pass backward: 1 its dX half, 2 both halves)
  *   [2] bn     output columns per block (64, 96, 128; the weight gradients: columns of their dW tile; 0 tiled)
  *   [3] wst    1 when the weights are streamed rather than resident in LDS

@@ -97,6 +97,9 @@ static thread_local int t_last_plan[5] = {0, 0, 0, 0, 0};
 void pcops_note_plan(int path, int split, int bn, int wst, int pool) {
     t_last_plan[0] = path; t_last_plan[1] = split; t_last_plan[2] = bn; t_last_plan[3] = wst; t_last_plan[4] = pool;
 }
+void pcops_note_plan_field(int field, int value) {
+    if (field >= 0 && field < 5) t_last_plan[field] = value;
+}
 extern "C" int pcops_last_launch_plan(int *out, int n) {
     if (!out || n < 0) return PCOPS_ERR_NULL_POINTER;
     for (int i = 0; i < n && i < 5; ++i) out[i] = t_last_plan[i];

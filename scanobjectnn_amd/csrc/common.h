@@ -33,6 +33,7 @@ extern "C" int pcops_get_option(int option);      // abi.hip: the arithmetic opt
 void pcops_note_pipe(int pipe);                   // abi.hip: what pcops_last_launch_pipe() reports (0 fp32, 1 split bf16, 2 both)
 // abi.hip: what pcops_last_launch_plan() reports -- the variant the last product launch took (codes in pcops.h)
 void pcops_note_plan(int path, int split, int bn, int wst, int pool);
+void pcops_note_plan_field(int field, int value);   // one field of the plan just noted (a sub-launcher's own decision)
 
 constexpr int kWave = 64;  // CDNA wavefront
 

@@ -14,10 +14,10 @@ int ec_edge_pool_stats_rows(int b, int n, int m);     // ... and what pcops_edge
 // pooled EdgeConv layer (pcops_edge_pool_fwd): SQ, qsel, arg, shifted moments
 int ec_edge_pool_fwd(int b, int n, int m, int s, int c, const float *Q, int ldq, const float *Ctr, int ldc, const int *idx,
                      const float *gamma, float *SQ, float *qsel, unsigned char *arg, float *stats, const float *pivot,
-                     hipStream_t st);
+                     bool ld_form, hipStream_t st);
 // stored first layer of a gather stack, Y = Q[idx] + Ctr (pcops_sa_gather_fwd_rows in its Q + Ctr form)
 int ec_gather_fwd(int b, int n, int m, int s, int c, const float *Q, int ldq, const float *Ctr, int ldc, const int *idx,
-                  float *Y, float *stats, const float *pivot, hipStream_t st);
+                  float *Y, float *stats, const float *pivot, bool ld_form, hipStream_t st);
 // inverse index of idx into `workspace` (order | start | perm | codes), then the owner walk over it
 int ec_csr_build(int b, int n, int m, int s, const int *idx, void *workspace, hipStream_t st);
 int ec_walk(int b, int n, int m, int s, int c, const float *Q, int ldq, const float *Ctr, int ldc, const float *G,

@@ -65,7 +65,10 @@ struct FwdArgs {
 // formulas of gather.hip edge_pool_fwd_kernel, kept so that the statistics are the same numbers), ex = max_s sg.q and the
 // FIRST s attaining it (sg = -1 where gamma < 0: BN + ReLU is then decreasing and the pooled row is the minimum).
 // MODE 1, per row: y = Ctr + q stored, d = y - pivot, s1 += d, s2 += d^2 (gather.hip sa_gather_fwd_kernel).
-template <int MODE, bool UP>
+// BLOCKED (MODE 0, groups of more than 20 neighbours; its own kernel instance, so that the k <= 20 instance keeps its
+// registers and its order of summation): the shifted sum is folded away every 16 terms.  Its partial sums grow as j |qz|,
+// and one sequential fp32 sum carried that into SQ -- relative RMS 1.2e-6 .. 1.4e-6 against float64 at s = 128, 5e-7 folded.
+template <int MODE, bool UP, bool BLOCKED>
 __device__ __forceinline__ void ec_fwd_groups(const FwdArgs &a, const unsigned *offs, long long g0, int set, int quad,
                                               unsigned tq, __amdgpu_buffer_rsrc_t rq, int ch, f2 (&s1)[2], f2 (&s2)[2]) {
     const int S = a.S, C = a.C;
@@ -129,6 +132,9 @@ __device__ __forceinline__ void ec_fwd_groups(const FwdArgs &a, const unsigned *
                 s2[1] = __builtin_elementwise_fma(db, db, s2[1]);
             }
         };
+        constexpr bool blocked = BLOCKED && MODE == 0;
+        f2 hq[2] = {{0.f, 0.f}, {0.f, 0.f}};
+        auto fold = [&]() { hq[0] += sq[0]; hq[1] += sq[1]; sq[0] = f2{0.f, 0.f}; sq[1] = f2{0.f, 0.f}; };
         int s = 0;
         if ((S & 3) == 0) {
             for (; s + 8 <= S; s += 8) {
@@ -138,6 +144,7 @@ __device__ __forceinline__ void ec_fwd_groups(const FwdArgs &a, const unsigned *
                              q6 = ec_load4(rq, o1.z + tq), q7 = ec_load4(rq, o1.w + tq);
                 take(q0, s); take(q1, s + 1); take(q2, s + 2); take(q3, s + 3);
                 take(q4, s + 4); take(q5, s + 5); take(q6, s + 6); take(q7, s + 7);
+                if (blocked && ((s + 8) & 15) == 0 && s + 8 < S) fold();
             }
             for (; s + 4 <= S; s += 4) {
                 const uint4 o0 = *reinterpret_cast<const uint4 *>(og + s);
@@ -146,8 +153,12 @@ __device__ __forceinline__ void ec_fwd_groups(const FwdArgs &a, const unsigned *
                 take(q0, s); take(q1, s + 1); take(q2, s + 2); take(q3, s + 3);
             }
         }
-        for (; s < S; ++s) take(ec_load4(rq, og[s] + tq), s);
+        for (; s < S; ++s) {
+            take(ec_load4(rq, og[s] + tq), s);
+            if (blocked && (s & 15) == 15 && s + 1 < S) fold();
+        }
         if (MODE == 0) {
+            if constexpr (blocked) { sq[0] += hq[0]; sq[1] += hq[1]; }
             *reinterpret_cast<float4 *>(a.SQ + g * C + ch) =
                 make_float4(fmaf(kf, qz[0].x, sq[0].x), fmaf(kf, qz[0].y, sq[0].y), fmaf(kf, qz[1].x, sq[1].x),
                             fmaf(kf, qz[1].y, sq[1].y));
@@ -171,7 +182,7 @@ __device__ __forceinline__ void ec_fwd_groups(const FwdArgs &a, const unsigned *
     (void)quad;
 }
 
-template <int MODE>
+template <int MODE, bool BLOCKED>
 __global__ __launch_bounds__(256) void ec_fwd_kernel(FwdArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned ec_sm[];      // offsets [64][S] | statistics [16][2][64]
     const int S = a.S, C = a.C;
@@ -198,8 +209,8 @@ __global__ __launch_bounds__(256) void ec_fwd_kernel(FwdArgs a) {
         up = !(ga.x < 0.f) && !(ga.y < 0.f) && !(ga.z < 0.f) && !(ga.w < 0.f);
         up = __all(up) != 0;                                               // wave-uniform: one loop body per wave
     }
-    if (up) ec_fwd_groups<MODE, true>(a, ec_sm, g0, set, quad, tq, rq, ch, s1, s2);
-    else ec_fwd_groups<MODE, false>(a, ec_sm, g0, set, quad, tq, rq, ch, s1, s2);
+    if (up) ec_fwd_groups<MODE, true, BLOCKED>(a, ec_sm, g0, set, quad, tq, rq, ch, s1, s2);
+    else ec_fwd_groups<MODE, false, BLOCKED>(a, ec_sm, g0, set, quad, tq, rq, ch, s1, s2);
     if (a.stats == nullptr) return;
     float *sm = reinterpret_cast<float *>(ec_sm + kGB * S);
     {
@@ -482,7 +493,8 @@ __global__ __launch_bounds__(256) void ec_tnet_ctr_kernel(CtrArgs a) {
 // is a ds_read_b128.  Four lanes per group / point (a float4 of channels each), 256 groups in flight.
 constexpr int kSliceCh = 16;
 
-template <bool UP, int NI>         // NI int4 index registers per group: S <= 4 NI in the prefetched form
+// BLOCKED: as in ec_fwd_groups (more than 20 neighbours, always the in-line form: NI = 1 there)
+template <bool UP, int NI, bool BLOCKED>         // NI int4 index registers per group: S <= 4 NI in the prefetched form
 __device__ __forceinline__ void ec_fwd_lds_groups(const FwdArgs &a, const float4 *qs, int b, int quad, int cl, int ch,
                                                   f2 (&s1)[2], f2 (&s2)[2]) {
     const int S = a.S, C = a.C, m = a.m;
@@ -558,7 +570,19 @@ __device__ __forceinline__ void ec_fwd_lds_groups(const FwdArgs &a, const float4
                 }
         } else {
             const int *ig = a.idx + g * S;
-            for (int s = 0; s < S; ++s) take(qs[ig[s] * 4 + cl], s);
+            if constexpr (BLOCKED) {
+                f2 hq[2] = {{0.f, 0.f}, {0.f, 0.f}};
+                for (int s = 0; s < S; ++s) {
+                    take(qs[ig[s] * 4 + cl], s);
+                    if ((s & 15) == 15 && s + 1 < S) {
+                        hq[0] += sq[0]; hq[1] += sq[1];
+                        sq[0] = f2{0.f, 0.f}; sq[1] = f2{0.f, 0.f};
+                    }
+                }
+                sq[0] += hq[0]; sq[1] += hq[1];
+            } else {
+                for (int s = 0; s < S; ++s) take(qs[ig[s] * 4 + cl], s);
+            }
         }
         *reinterpret_cast<float4 *>(a.SQ + g * C + ch) =
             make_float4(fmaf(kf, qz[0].x, sq[0].x), fmaf(kf, qz[0].y, sq[0].y), fmaf(kf, qz[1].x, sq[1].x),
@@ -585,6 +609,7 @@ __device__ __forceinline__ void ec_fwd_lds_groups(const FwdArgs &a, const float4
 }
 
 // statistics: ONE partial row per cloud, stats [b][2][C]
+template <bool BLOCKED>
 __global__ __launch_bounds__(1024) void ec_fwd_lds_kernel(FwdArgs a) {
     extern __shared__ __attribute__((aligned(16))) float4 ec_qs[];      // [n][4] | wave sums [16][2][16] floats
     const int C = a.C, n = a.n, NS = C / kSliceCh;
@@ -602,8 +627,8 @@ __global__ __launch_bounds__(1024) void ec_fwd_lds_kernel(FwdArgs a) {
     const bool up = __all(!(ga.x < 0.f) && !(ga.y < 0.f) && !(ga.z < 0.f) && !(ga.w < 0.f)) != 0;
     // (five index registers: k <= 20 neighbours take the prefetched form, larger groups read their indices in line;
     //  eight registers per buffer spilled at the 128 VGPRs a 1024-lane workgroup leaves per lane)
-    if (up) ec_fwd_lds_groups<true, 5>(a, ec_qs, b, quad, cl, ch, s1, s2);
-    else ec_fwd_lds_groups<false, 5>(a, ec_qs, b, quad, cl, ch, s1, s2);
+    if (up) ec_fwd_lds_groups<true, BLOCKED ? 1 : 5, BLOCKED>(a, ec_qs, b, quad, cl, ch, s1, s2);
+    else ec_fwd_lds_groups<false, BLOCKED ? 1 : 5, BLOCKED>(a, ec_qs, b, quad, cl, ch, s1, s2);
     if (a.stats == nullptr) return;
     float v[8] = {s1[0].x, s1[0].y, s1[1].x, s1[1].y, s2[0].x, s2[0].y, s2[1].x, s2[1].y};
 #pragma unroll
@@ -1250,30 +1275,37 @@ int ec_edge_pool_stats_rows(int b, int n, int m) {
 
 int ec_edge_pool_fwd(int b, int n, int m, int s, int c, const float *Q, int ldq, const float *Ctr, int ldc, const int *idx,
                      const float *gamma, float *SQ, float *qsel, unsigned char *arg, float *stats, const float *pivot,
-                     hipStream_t st) {
+                     bool ld_form, hipStream_t st) {
     FwdArgs a = {b, n, m, s, c, ldq, ldc, Q, Ctr, idx, gamma, SQ, qsel, arg, nullptr, stats, pivot};
+    const bool blocked = s > 20;          // the instances that fold the group's shifted sum every 16 terms (ec_fwd_groups)
     if (ec_lds_on() && ec_lds_fwd_ok(n)) {
         const size_t lds = (size_t)n * 64 + 16 * 2 * kSliceCh * sizeof(float);
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(ec_fwd_lds_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)kLdsMax) != hipSuccess)
+        const void *fn = blocked ? reinterpret_cast<const void *>(ec_fwd_lds_kernel<true>)
+                                 : reinterpret_cast<const void *>(ec_fwd_lds_kernel<false>);
+        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax) != hipSuccess)
             return PCOPS_ERR_LAUNCH;
-        hipLaunchKernelGGL(ec_fwd_lds_kernel, dim3((unsigned)b * (c / kSliceCh)), dim3(1024), lds, st, a);
+        pcops_note_plan(10, 2, stats ? b : 0, blocked ? 1 : 0, ld_form ? 1 : 0);
+        if (blocked) hipLaunchKernelGGL(ec_fwd_lds_kernel<true>, dim3((unsigned)b * (c / kSliceCh)), dim3(1024), lds, st, a);
+        else hipLaunchKernelGGL(ec_fwd_lds_kernel<false>, dim3((unsigned)b * (c / kSliceCh)), dim3(1024), lds, st, a);
         return pcops_launch_status();
     }
     const unsigned grid = (unsigned)((long long)b * (c / 64) * (m / kGB));
     const size_t lds = ((size_t)kGB * s + kSets * 128) * sizeof(float);
-    hipLaunchKernelGGL(ec_fwd_kernel<0>, dim3(grid), dim3(256), lds, st, a);
+    pcops_note_plan(10, 1, stats ? ec_stats_rows((long long)b * m) : 0, blocked ? 1 : 0, ld_form ? 1 : 0);
+    if (blocked) hipLaunchKernelGGL((ec_fwd_kernel<0, true>), dim3(grid), dim3(256), lds, st, a);
+    else hipLaunchKernelGGL((ec_fwd_kernel<0, false>), dim3(grid), dim3(256), lds, st, a);
     return pcops_launch_status();
 }
 
 int ec_gather_fwd(int b, int n, int m, int s, int c, const float *Q, int ldq, const float *Ctr, int ldc, const int *idx,
-                  float *Y, float *stats, const float *pivot, hipStream_t st) {
+                  float *Y, float *stats, const float *pivot, bool ld_form, hipStream_t st) {
     static const bool nt_on = [] { const char *e = getenv("PCOPS_NT_STORE"); return !(e && e[0] == '0'); }();   // kernel A/B only
     FwdArgs a = {b, n, m, s, c, ldq, ldc, Q, Ctr, idx, nullptr, nullptr, nullptr, nullptr, Y, stats, pivot,
                  (nt_on && (long long)b * m * s * c * 4 >= (256ll << 20)) ? 1 : 0};
     const unsigned grid = (unsigned)((long long)b * (c / 64) * (m / kGB));
     const size_t lds = ((size_t)kGB * s + kSets * 128) * sizeof(float);
-    hipLaunchKernelGGL(ec_fwd_kernel<1>, dim3(grid), dim3(256), lds, st, a);
+    pcops_note_plan(12, 0, stats ? ec_stats_rows((long long)b * m) : 0, 0, ld_form ? 1 : 0);
+    hipLaunchKernelGGL((ec_fwd_kernel<1, false>), dim3(grid), dim3(256), lds, st, a);
     return pcops_launch_status();
 }
 
@@ -1295,12 +1327,14 @@ int ec_csr_build(int b, int n, int m, int s, const int *idx, void *workspace, hi
         if (hipFuncSetAttribute(reinterpret_cast<const void *>(ec_csr_build_kernel<true>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
             return PCOPS_ERR_LAUNCH;
+        pcops_note_plan_field(3, 1);
         hipLaunchKernelGGL(ec_csr_build_kernel<true>, dim3(b), dim3(1024), lds + (size_t)m * s * 2, st, n, m, s, sbits, idx, order,
                            start, perm, codes);
     } else {
         if (hipFuncSetAttribute(reinterpret_cast<const void *>(ec_csr_build_kernel<false>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
             return PCOPS_ERR_LAUNCH;
+        pcops_note_plan_field(3, 0);
         hipLaunchKernelGGL(ec_csr_build_kernel<false>, dim3(b), dim3(1024), lds, st, n, m, s, sbits, idx, order, start, perm,
                            codes);
     }
@@ -1319,10 +1353,12 @@ int ec_walk(int b, int n, int m, int s, int c, const float *Q, int ldq, const fl
         const int *perm = start + (size_t)b * (n + 1);
         const unsigned short *codes = reinterpret_cast<const unsigned short *>(perm + (size_t)b * n);
         WalkLdsArgs wa = {a, perm, codes, ec_sbits(s)};
+        pcops_note_plan_field(2, 2);
         hipLaunchKernelGGL(ec_walk_lds_kernel, dim3((unsigned)b * (c / kWalkCh)), dim3(1024), ec_lds_walk_bytes(n, m, s), st, wa);
         return pcops_launch_status();
     }
     const unsigned grid = (unsigned)((long long)b * (c / 64) * ((n + kGB - 1) / kGB));
+    pcops_note_plan_field(2, 1);
     if (G) hipLaunchKernelGGL(ec_walk_kernel<true>, dim3(grid), dim3(256), 0, st, a);
     else hipLaunchKernelGGL(ec_walk_kernel<false>, dim3(grid), dim3(256), 0, st, a);
     return pcops_launch_status();

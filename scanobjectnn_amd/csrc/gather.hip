@@ -1454,7 +1454,8 @@ __global__ __launch_bounds__(256) void edge_pool_fwd_kernel(long long G, int n, 
             const long long b = g / m;
             const float4 ct = *reinterpret_cast<const float4 *>(Ctr + g * C + cq);
             float sq[4] = {0.f, 0.f, 0.f, 0.f}, sq2[4] = {0.f, 0.f, 0.f, 0.f};
-            float ex[4];
+            float hq[4] = {0.f, 0.f, 0.f, 0.f};                   // groups of more than 20: sq folded away every 20 terms (its
+            float ex[4];                                          // partial sums grow as j |qz|: edgeconv.hip ec_fwd_groups)
             int ea[4] = {0, 0, 0, 0};
 #pragma unroll
             for (int e = 0; e < 4; ++e) ex[e] = up[e] ? -INFINITY : INFINITY;
@@ -1485,6 +1486,10 @@ __global__ __launch_bounds__(256) void edge_pool_fwd_kernel(long long G, int n, 
                 for (int u = 0; u < UF; ++u) qu[u] = *reinterpret_cast<const float4 *>(Qb + iu[u] * (long long)C);
 #pragma unroll
                 for (int u = 0; u < UF; ++u) take(qu[u], s + u);
+                if ((s + UF) % 20 == 0 && s + UF < S) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) { hq[e] += sq[e]; sq[e] = 0.f; }
+                }
             }
             for (; s + 4 <= S; s += 4) {
                 const int i0 = ig[s], i1 = ig[s + 1], i2 = ig[s + 2], i3 = ig[s + 3];
@@ -1495,6 +1500,8 @@ __global__ __launch_bounds__(256) void edge_pool_fwd_kernel(long long G, int n, 
                 take(q0v, s); take(q1v, s + 1); take(q2v, s + 2); take(q3v, s + 3);
             }
             for (; s < S; ++s) take(*reinterpret_cast<const float4 *>(Qb + ig[s] * (long long)C), s);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) sq[e] += hq[e];
             const float kf = (float)S;
             *reinterpret_cast<float4 *>(SQ + g * C + cq) =                       // the backward reads SQ = sum_s q
                 make_float4(fmaf(kf, qz[0], sq[0]), fmaf(kf, qz[1], sq[1]), fmaf(kf, qz[2], sq[2]), fmaf(kf, qz[3], sq[3]));
@@ -1998,7 +2005,7 @@ int pcops_sa_gather_fwd_rows(int b, int n, int m, int s, int c, const float *Q, 
                          moments != nullptr, rows != nullptr) && Y != nullptr) {
         // (writes pcops_sa_gather_fwd_stats_rows(...) rows of partial statistics -- fewer than the shape-less upper bound
         // pcops_sa_gather_stats_rows(G): ABI version 4, pcops.h)
-        return ec_gather_fwd(b, n, m, s, c, Q, c, Ctr, c, idx, Y, stats_partial, stat_pivot, as_stream(stream));
+        return ec_gather_fwd(b, n, m, s, c, Q, c, Ctr, c, idx, Y, stats_partial, stat_pivot, false, as_stream(stream));
     }
     if (!Y && !Q && !Ctr && Wxyz && moments && stats_partial && pcops_get_option(PCOPS_OPT_XYZ_STATS_MOMENTS) != 0) {
         // arithmetic first layer, statistics only: its two sums per channel follow from the nine offset moments
@@ -2077,6 +2084,7 @@ int pcops_sa_scatter_bwd_rows(int b, int n, int m, int s, int c, const float *G,
         !pcops_get_deterministic() && ec_bwd_supported(b, n, m, s, c)) {
         // round 5 (edgeconv.hip), the Q + Ctr form:  sum over the rows of a point of  q Y  is  q (cnt Q[i] + sum Ctr[g]),
         // so Y is not read at all and G is read twice (streamed per group for dCtr, gathered per point for dQ)
+        pcops_note_plan(13, 0, 0, 0, 0);
         int rc = ec_csr_build(b, n, m, s, idx, workspace, st);
         if (rc) return rc;
         rc = ec_tnet_ctr(b, n, m, s, c, fwd_Q, c, fwd_Ctr, c, G, idx, p, q, t, dCtr, c, st);
@@ -2284,9 +2292,10 @@ int pcops_edge_pool_fwd(int b, int n, int m, int s, int c, const float *Q, const
     // b m / 64 = pcops_edge_pool_stats_rows(G) rows of partial statistics
     if (ec_fwd_supported(b, n, m, s, c) && s <= 256) {
         // (writes pcops_edge_pool_fwd_stats_rows(...) rows, not the shape-less upper bound: ABI version 4, pcops.h)
-        return ec_edge_pool_fwd(b, n, m, s, c, Q, c, Ctr, c, idx, gamma, SQ, qsel, arg, stats_partial, stat_pivot, as_stream(stream));
+        return ec_edge_pool_fwd(b, n, m, s, c, Q, c, Ctr, c, idx, gamma, SQ, qsel, arg, stats_partial, stat_pivot, false, as_stream(stream));
     }
     const int gl = 256 / (c / 4);
+    pcops_note_plan(10, 0, stats_partial ? pcops_edge_pool_stats_rows(G) : 0, 0, 0);
     hipLaunchKernelGGL(edge_pool_fwd_kernel, dim3(pcops_edge_pool_stats_rows(G)), dim3(256),
                        (size_t)gl * 2 * c * sizeof(float), as_stream(stream), G, n, m, s, c, Q, Ctr, idx, gamma, SQ, qsel,
                        arg, stats_partial, stat_pivot, 64);
@@ -2327,6 +2336,7 @@ int pcops_edge_pool_bwd(int b, int n, int m, int s, int c, const float *Q, const
     PCOPS_REQUIRE_PTR(q); PCOPS_REQUIRE_PTR(t); PCOPS_REQUIRE_PTR(dCtr); PCOPS_REQUIRE_PTR(workspace);
     if (use_owner && !det && ec_bwd_supported(b, n, m, s, c) && ec_bwd_fused_ok(n, m, s, c)) {
         // round 5, second half: both terms and dCtr in ONE owner walk (edgeconv.hip ec_bwd_lds_kernel)
+        pcops_note_plan(11, 4, 0, 0, 0);
         int rc = ec_csr_build(b, n, m, s, idx, workspace, st);
         if (rc) return rc;
         return ec_bwd_fused(b, n, m, s, c, Q, c, Ctr, c, gpool, ysel, SQ, arg, scale, shift, p, q, t, workspace, dQ, c, dCtr, c, st);
@@ -2337,6 +2347,7 @@ int pcops_edge_pool_bwd(int b, int n, int m, int s, int c, const float *Q, const
         if (hipFuncSetAttribute(reinterpret_cast<const void *>(edge_pool_bwd_sparse_kernel<false>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
             return PCOPS_ERR_LAUNCH;
+        pcops_note_plan(11, 3, 0, 0, 0);
         hipLaunchKernelGGL(edge_pool_bwd_sparse_kernel<false>, dim3(b * (c / kEdgeSlice)), dim3(1024), slice_lds, st, n, m, s, c,
                            gpool, ysel, SQ, Ctr, arg, idx, scale, shift, p, q, t, dCtr, dQ);
         int rc = ec_csr_build(b, n, m, s, idx, workspace, st);
@@ -2363,6 +2374,7 @@ int pcops_edge_pool_bwd(int b, int n, int m, int s, int c, const float *Q, const
     hipLaunchKernelGGL((edge_pool_bwd_dense_kernel<LPR_, DET_>), dim3(dgrid), dim3(256), 0, st, b, n, m, s, c, Q, Ctr, q, t, \
                        DET_ ? sorted : order, start, dQ, sp)
         if (det) {
+            pcops_note_plan(11, 2, 0, 0, 0);
             hipLaunchKernelGGL(edge_pool_bwd_sparse_kernel<true>, dim3(b * (c / kEdgeSlice)), dim3(1024), 0, st, n, m, s, c,
                                gpool, ysel, SQ, Ctr, arg, idx, scale, shift, p, q, t, dCtr, dQ);
             switch (lpr) {
@@ -2376,6 +2388,7 @@ int pcops_edge_pool_bwd(int b, int n, int m, int s, int c, const float *Q, const
         if (hipFuncSetAttribute(reinterpret_cast<const void *>(edge_pool_bwd_sparse_kernel<false>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
             return PCOPS_ERR_LAUNCH;
+        pcops_note_plan(11, 1, 0, 0, 0);
         hipLaunchKernelGGL(edge_pool_bwd_sparse_kernel<false>, dim3(b * (c / kEdgeSlice)), dim3(1024), slice_lds, st, n, m, s, c,
                            gpool, ysel, SQ, Ctr, arg, idx, scale, shift, p, q, t, dCtr, dQ);
         switch (lpr) {
@@ -2389,6 +2402,7 @@ int pcops_edge_pool_bwd(int b, int n, int m, int s, int c, const float *Q, const
     }
     const long long total = G * c;
     const unsigned grid = cdiv(total, 256) < 16384u ? cdiv(total, 256) : 16384u;
+    pcops_note_plan(11, 0, 0, 0, 0);
     hipLaunchKernelGGL(edge_pool_bwd_ctr_kernel, dim3(grid), dim3(256), 0, st, total, n, m, s, c, gpool, ysel, SQ, Ctr,
                        arg, idx, scale, shift, p, q, t, dCtr, dQ);
     switch (lpr) {
@@ -2421,7 +2435,7 @@ int pcops_edge_pool_fwd_ld(int b, int n, int m, int s, int c, const float *Q, in
     PCOPS_REQUIRE_PTR(Q); PCOPS_REQUIRE_PTR(Ctr); PCOPS_REQUIRE_PTR(idx); PCOPS_REQUIRE_PTR(gamma);
     PCOPS_REQUIRE_PTR(SQ); PCOPS_REQUIRE_PTR(qsel); PCOPS_REQUIRE_PTR(arg);
     if (!edge_ld_shape_ok(b, n, m, s, c) || (long long)b * n * ldq * 4 >= (1ll << 32)) return PCOPS_ERR_UNSUPPORTED;
-    return ec_edge_pool_fwd(b, n, m, s, c, Q, ldq, Ctr, ldc, idx, gamma, SQ, qsel, arg, stats_partial, stat_pivot,
+    return ec_edge_pool_fwd(b, n, m, s, c, Q, ldq, Ctr, ldc, idx, gamma, SQ, qsel, arg, stats_partial, stat_pivot, true,
                             as_stream(stream));
 }
 
@@ -2477,11 +2491,13 @@ int pcops_edge_pool_bwd_ld(int b, int n, int m, int s, int c, const float *Q, in
     if (!edge_ld_shape_ok(b, n, m, s, c) || (long long)b * n * ldq * 4 >= (1ll << 32)) return PCOPS_ERR_UNSUPPORTED;
     hipStream_t st = as_stream(stream);
     if (ec_bwd_fused_ok(n, m, s, c)) {
+        pcops_note_plan(11, 4, 0, 0, 1);
         int rc0 = ec_csr_build(b, n, m, s, idx, workspace, st);
         if (rc0) return rc0;
         return ec_bwd_fused(b, n, m, s, c, Q, ldq, Ctr, ldc, gpool, ysel, SQ, arg, scale, shift, p, q, t, workspace, dQ, lddq,
                             dCtr, lddc, st);
     }
+    pcops_note_plan(11, 3, 0, 0, 1);
     int rc = ec_sparse(b, n, m, s, c, gpool, ysel, SQ, Ctr, ldc, arg, idx, scale, shift, p, q, t, dCtr, lddc, dQ, lddq, st);
     if (rc) return rc;
     rc = ec_csr_build(b, n, m, s, idx, workspace, st);
@@ -2494,7 +2510,7 @@ int pcops_sa_gather_fwd_ld(int b, int n, int m, int s, int c, const float *Q, in
     PCOPS_REQUIRE_SHAPE(b >= 1 && n >= 1 && m >= 1 && s >= 1 && c >= 4 && ldq >= c && ldc >= c && ldq % 4 == 0 && ldc % 4 == 0);
     PCOPS_REQUIRE_PTR(Q); PCOPS_REQUIRE_PTR(Ctr); PCOPS_REQUIRE_PTR(idx); PCOPS_REQUIRE_PTR(Y);
     if (!edge_ld_shape_ok(b, n, m, s, c) || (long long)b * n * ldq * 4 >= (1ll << 32)) return PCOPS_ERR_UNSUPPORTED;
-    return ec_gather_fwd(b, n, m, s, c, Q, ldq, Ctr, ldc, idx, Y, stats_partial, stat_pivot, as_stream(stream));
+    return ec_gather_fwd(b, n, m, s, c, Q, ldq, Ctr, ldc, idx, Y, stats_partial, stat_pivot, true, as_stream(stream));
 }
 
 int pcops_sa_scatter_bwd_ld(int b, int n, int m, int s, int c, const float *G, const float *p, const float *q, const float *t,
@@ -2506,6 +2522,7 @@ int pcops_sa_scatter_bwd_ld(int b, int n, int m, int s, int c, const float *G, c
     PCOPS_REQUIRE_PTR(Q); PCOPS_REQUIRE_PTR(Ctr); PCOPS_REQUIRE_PTR(dQ); PCOPS_REQUIRE_PTR(dCtr); PCOPS_REQUIRE_PTR(workspace);
     if (!edge_ld_shape_ok(b, n, m, s, c) || (long long)b * n * ldq * 4 >= (1ll << 32)) return PCOPS_ERR_UNSUPPORTED;
     hipStream_t st = as_stream(stream);
+    pcops_note_plan(13, 0, 0, 0, 1);
     int rc = ec_csr_build(b, n, m, s, idx, workspace, st);
     if (rc) return rc;
     rc = ec_tnet_ctr(b, n, m, s, c, Q, ldq, Ctr, ldc, G, idx, p, q, t, dCtr, lddc, st);

@@ -405,8 +405,11 @@ def test_adam_step_is_the_reference_update():
 @pytest.mark.parametrize("b,n,k,C,ld", [(3, 2048, 20, 64, False), (2, 2048, 20, 128, True), (2, 1024, 20, 64, True),
                                         (2, 1088, 16, 64, False), (1, 1984, 20, 256, False)])
 def test_edge_pool_bwd_against_float64(b, n, k, C, ld):
-    """pcops_edge_pool_bwd / _ld (csrc/edgeconv.hip ec_bwd_lds_kernel: inverse index, then ONE walk that adds the Ctr rows
-    AND the arg-row values of every list entry) against the definition in float64:
+    """pcops_edge_pool_bwd / _ld at model-sized clouds against the definition in float64.  All five shapes take one branch:
+    the arg-row kernel (gather.hip edge_pool_bwd_sparse_kernel<false>, or edgeconv.hip ec_sparse_kernel for the _ld form), the
+    inverse index assembled in LDS (ec_csr_build_kernel<true>) and the LDS-resident owner walk (ec_walk_lds_kernel).  The
+    one-walk ec_bwd_lds_kernel is off unless PCOPS_EDGECONV_BWD_FUSED=1; it and every other branch are held element by element
+    in tests/test_edge_paths_gpu.py.
       a[g,c] = p gpool [scale ysel + shift > 0],  dCtr[g] = q (SQ + k Ctr) + k t + a,
       dQ[i] = q (cnt_i Q[i] + sum_{(g,s) -> i} Ctr[g]) + cnt_i t + sum_{(g,s) -> i, arg[g,c] == s} a[g,c]"""
     from scanobjectnn_amd.dgcnn import tf_util
