@@ -105,7 +105,9 @@ int pcops_last_launch_pipe(void);
  *   [0] path   0 none yet, 1 tiled fp32 kernel, 2 wave-stream kernel, 3 one-pass backward (pcops_mlp_bwd_fused*),
  *              4 / 5 / 6 / 7 weight gradient: split-operand / producer-consumer / wave-stream / legacy split-K kernel,
  *              8 / 9 pcops_sa_scatter_bwd(_rows) over the inverse index: chunked walk with atomics ([1] = 1: its Q form,
- *              [2] sorted rows per chunk, [4] = 4 compacted rows) / owner walk (deterministic mode)
+ *              [2] sorted rows per chunk, [4] = 4 compacted rows) / owner walk (deterministic mode);  [3] of both: the slice
+ *              width (64 / 32 / 16 / 8 channels) of the LDS streaming pass that ran first for the per-group outputs or the
+ *              pooled form (sa_scatter_lds_kernel), 0 when none ran
  *              10..13 the EdgeConv family (csrc/edgeconv.hip and its launchers); their fields are their own:
  *              10 pcops_edge_pool_fwd(_ld):  [1] kernel: 0 generic, 1 64-group chunks over L2 (ec_fwd_kernel<0>), 2 LDS-resident
  *                 slice (ec_fwd_lds_kernel);  [2] rows of stats_partial written (0 without statistics);  [3] 1 for the instance
@@ -119,6 +121,14 @@ int pcops_last_launch_pipe(void);
  *                 [4] 1 for pcops_sa_gather_fwd_ld
  *              13 the Q + Ctr form of pcops_sa_scatter_bwd (ec_tnet_ctr_kernel + ec_walk_kernel<true>): [2], [3] as for 11,
  *                 [4] 1 for pcops_sa_scatter_bwd_ld
+ *              14..16 the rest of the set-abstraction launchers (csrc/gather.hip); their fields are their own:
+ *              14 pcops_sa_scatter_bwd(_rows) on the LDS-accumulating kernel alone (sa_scatter_lds_kernel):  [1] slice width in
+ *                 channels (64 / 32 / 16 / 8);  [2] 1 pooled single-layer form;  [3] 1 when Y is rebuilt from the forward's
+ *                 Wxyz / bias rather than read;  [4] workgroups a cloud's groups are dealt to (gsplit; 1 with a feature gradient)
+ *              15 pcops_sa_scatter_bwd(_rows) on the global-atomics fallback (sa_scatter_bwd_kernel):  [2] 1 pooled
+ *              16 pcops_sa_gather_fwd(_rows) on the generic kernel (sa_gather_fwd_kernel):  [1] groups per workgroup (1 or 8);
+ *                 [2] rows of stats_partial written (0 without statistics);  [3] 1 for the statistics-from-moments route
+ *                 (sa_gather_offsets_kernel + xyz_stats_from_moments_kernel);  [4] 4 compacted rows
  *   [1] split  1 when the operands are split into bf16 pieces (the one-pass backward: 1 its dX half, 2 both halves)
  *   [2] bn     output columns per block (64, 96, 128; the weight gradients: columns of their dW tile; 0 tiled)
  *   [3] wst    1 when the weights are streamed rather than resident in LDS

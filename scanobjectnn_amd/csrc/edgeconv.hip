@@ -406,6 +406,8 @@ __global__ __launch_bounds__(256) void ec_walk_kernel(WalkArgs a) {
         if (HAS_G) {
             d.x = fmaf(cp.x, ag[0].x, d.x); d.y = fmaf(cp.y, ag[0].y, d.y);
             d.z = fmaf(cp.z, ag[1].x, d.z); d.w = fmaf(cp.w, ag[1].y, d.w);
+            // a point no row names: 0 q + 0 t is -0 where q and t are negative; the other scatter forms write +0 there
+            d.x += 0.f; d.y += 0.f; d.z += 0.f; d.w += 0.f;
         } else {
             const float4 o = *dst;
             d.x += o.x; d.y += o.y; d.z += o.z; d.w += o.w;

@@ -253,9 +253,11 @@ __global__ __launch_bounds__(256) void sa_gather_fwd_kernel(long long G, int n, 
         for (int k = 0; k < 9; ++k) mm[k * 256 + threadIdx.x] = mo[k];
         __syncthreads();
         if (threadIdx.x < 9) {
-            float t = 0.f;
-            for (int j = 0; j < 256; ++j) t += mm[threadIdx.x * 256 + j];
-            moments[(long long)blockIdx.x * 9 + threadIdx.x] = t;
+            // 256 lane sums in one chain: in double (nine threads, once per workgroup) -- an fp32 chain of that length cost
+            // the partial rows a relative RMS of 1.2e-6 against float64 (tests/test_sa_paths_gpu.py)
+            double t = 0.0;
+            for (int j = 0; j < 256; ++j) t += (double)mm[threadIdx.x * 256 + j];
+            moments[(long long)blockIdx.x * 9 + threadIdx.x] = (float)t;
         }
         __syncthreads();
     }
@@ -322,9 +324,9 @@ __global__ __launch_bounds__(256) void sa_gather_offsets_kernel(long long G, int
     for (int k = 0; k < 9; ++k) mm[k * 256 + threadIdx.x] = mo[k];
     __syncthreads();
     if (threadIdx.x < 9) {
-        float t = 0.f;
-        for (int j = 0; j < 256; ++j) t += mm[threadIdx.x * 256 + j];
-        moments[(long long)blockIdx.x * 9 + threadIdx.x] = t;
+        double t = 0.0;                       // as in sa_gather_fwd_kernel: the partial rows stay bit-identical to its
+        for (int j = 0; j < 256; ++j) t += (double)mm[threadIdx.x * 256 + j];
+        moments[(long long)blockIdx.x * 9 + threadIdx.x] = (float)t;
     }
 }
 
@@ -2011,6 +2013,7 @@ int pcops_sa_gather_fwd_rows(int b, int n, int m, int s, int c, const float *Q, 
         // arithmetic first layer, statistics only: its two sums per channel follow from the nine offset moments
         const int P = pcops_sa_gather_stats_rows(G);
         hipStream_t st = as_stream(stream);
+        pcops_note_plan(16, gather_groups_per_block(G), P, 1, rows ? 4 : 0);
         hipLaunchKernelGGL(sa_gather_offsets_kernel, dim3(P), dim3(256), 0, st, G, n, m, s, xyz, new_xyz, idx, off4, moments,
                            gather_groups_per_block(G), rows ? static_cast<const RowBlock *>(rows->blocks) : nullptr,
                            rows ? rows->block_start : nullptr);
@@ -2023,6 +2026,7 @@ int pcops_sa_gather_fwd_rows(int b, int n, int m, int s, int c, const float *Q, 
     static const bool nt_on = [] { const char *e = getenv("PCOPS_NT_STORE"); return !(e && e[0] == '0'); }();   // kernel A/B only
     const size_t staged = (size_t)(s >= 1024 ? s : 1024) * 4;      // floats: (dx, dy, dz, index) per staged row
     if (((size_t)rl * 2 * c + staged) * sizeof(float) > 64 * 1024) return PCOPS_ERR_UNSUPPORTED;
+    pcops_note_plan(16, gather_groups_per_block(G), stats_partial ? pcops_sa_gather_stats_rows(G) : 0, 0, rows ? 4 : 0);
     hipLaunchKernelGGL(sa_gather_fwd_kernel, dim3(pcops_sa_gather_stats_rows(G)), dim3(256),
                        ((size_t)rl * 2 * c + staged) * sizeof(float), as_stream(stream), G, n, m, s, c, Q, Ctr, xyz, new_xyz,
                        Wxyz, bias, idx, Y, off4, stats_partial, stat_pivot, moments, gather_groups_per_block(G),
@@ -2103,9 +2107,10 @@ int pcops_sa_scatter_bwd_rows(int b, int n, int m, int s, int c, const float *G,
         const bool split = dCtr || gpool;        // per-group outputs / pooled form: streaming pass first
         const bool owner = !gpool && (det || scatter_owner_enabled());
         if (!owner && hipMemsetAsync(dQ, 0, sizeof(float) * (size_t)b * n * c, st) != hipSuccess) return PCOPS_ERR_LAUNCH;
+        int cs0 = 0;                             // slice width of the streaming pass (plan field [3]; 0: none ran)
         if (split) {
             size_t lb = 0;
-            const int cs0 = scatter_lds_slice(n, c, false, xyz != nullptr, &lb);
+            cs0 = scatter_lds_slice(n, c, false, xyz != nullptr, &lb);
             if (!cs0) return PCOPS_ERR_UNSUPPORTED;
             const int nsl = c / cs0;
             int gsplit = kCsrGrid / ((b + 7) / 8 * 8 * nsl);        // enough workgroups to fill the chip
@@ -2141,7 +2146,7 @@ int pcops_sa_scatter_bwd_rows(int b, int n, int m, int s, int c, const float *G,
         CsrArgs a = {b, n, m, s, c, G, Y, p, q, t, xyz, new_xyz, sorted ? sorted : order, dQ, wp2, rblocks, rbstart, start,
                      fwd_Q, fwd_Wxyz, fwd_bias};
         if (owner) {
-            pcops_note_plan(9, 0, 0, 0, rows ? 4 : 0);
+            pcops_note_plan(9, 0, 0, cs0, rows ? 4 : 0);
             switch (lpr) {
                 case 8: hipLaunchKernelGGL(sa_scatter_owner_kernel<8>, dim3(kCsrGrid), dim3(256), 0, st, a); break;
                 case 16: hipLaunchKernelGGL(sa_scatter_owner_kernel<16>, dim3(kCsrGrid), dim3(256), 0, st, a); break;
@@ -2164,7 +2169,7 @@ int pcops_sa_scatter_bwd_rows(int b, int n, int m, int s, int c, const float *G,
         const bool qform = G && !split && fwd_Q && !fwd_Ctr && pcops_get_option(PCOPS_OPT_SCATTER_QFORM) != 0 &&
                            (long long)m * s * c * 4 < (1ll << 31) && (long long)n * c * 4 < (1ll << 31) &&
                            (long long)b * m * (s > 12 ? s : 12) < (1ll << 31);
-        pcops_note_plan(8, qform ? 1 : 0, small ? 16 : 64, 0, rows ? 4 : 0);
+        pcops_note_plan(8, qform ? 1 : 0, small ? 16 : 64, cs0, rows ? 4 : 0);
         if (qform) {
 #define PCOPS_CSRQ_CASE(LPR_)                                                                                          \
     case LPR_:                                                                                                         \
@@ -2223,6 +2228,7 @@ int pcops_sa_scatter_bwd_rows(int b, int n, int m, int s, int c, const float *G,
         }
         ScatterArgs a = {b, n, m, s, c, c / cs, gsplit, G, Y, p, q, t, gpool, argmax, pool_scale, pool_shift, idx,
                          xyz, new_xyz, dQ, dCtr, wp, nullptr, fwd_Q, fwd_Ctr, fwd_Wxyz, fwd_bias};
+        pcops_note_plan(14, cs, gpool ? 1 : 0, ((fwd_Wxyz || fwd_bias) && !fwd_Q && !fwd_Ctr) ? 1 : 0, gsplit);
         int rc;
 #define PCOPS_SCATTER_CASE(CS_)                                                                   \
     case CS_:                                                                                     \
@@ -2252,6 +2258,7 @@ int pcops_sa_scatter_bwd_rows(int b, int n, int m, int s, int c, const float *G,
     const size_t lds = (size_t)rl * 6 * c * sizeof(float);
     const int gpb = 16;
     const unsigned grid = (unsigned)((Gn + 15) / 16);
+    pcops_note_plan(15, 0, gpool ? 1 : 0, 0, 0);
     if (gpool) {
         PCOPS_REQUIRE_PTR(argmax); PCOPS_REQUIRE_PTR(pool_scale); PCOPS_REQUIRE_PTR(pool_shift);
         PCOPS_REQUIRE_SHAPE(s <= 256);
