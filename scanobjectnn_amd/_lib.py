@@ -6,6 +6,7 @@ test infrastructure and is never imported from here).
 """
 import ctypes as C
 import os
+import re
 import weakref
 
 import torch
@@ -16,165 +17,73 @@ LIB_PATH = os.environ.get("PCOPS_LIB") or os.path.join(_HERE, "libpcops.so")    
 _I, _F, _P, _U64, _LL = C.c_int, C.c_float, C.c_void_p, C.c_ulonglong, C.c_longlong
 ABI_VERSION = 4      # pcops_abi_version() of the library this binding matches (include/pcops.h), checked in load()
 
-# name -> (argtypes without the trailing stream, has_stream)
-SIGNATURES = {
-    "pcops_farthest_point_sample": ([_I, _I, _I, _P, _P, _P], True),
-    "pcops_prob_sample": ([_I, _I, _I, _P, _P, _P, _P], True),
-    "pcops_gather_point": ([_I, _I, _I, _P, _P, _P], True),
-    "pcops_gather_point_grad": ([_I, _I, _I, _P, _P, _P], True),
-    "pcops_query_ball_point": ([_I, _I, _I, _F, _I, _P, _P, _P, _P], True),
-    "pcops_query_ball_point_multi": ([_I, _I, _I, _I, _P, _P, _P, _P, _P, _P], True),
-    "pcops_group_point": ([_I, _I, _I, _I, _I, _P, _P, _P], True),
-    "pcops_group_point_grad": ([_I, _I, _I, _I, _I, _P, _P, _P], True),
-    "pcops_selection_sort": ([_I, _I, _I, _I, _P, _P, _P], True),
-    "pcops_three_nn": ([_I, _I, _I, _P, _P, _P, _P], True),
-    "pcops_three_interpolate": ([_I, _I, _I, _I, _P, _P, _P, _P], True),
-    "pcops_three_interpolate_grad": ([_I, _I, _I, _I, _P, _P, _P, _P], True),
-    "pcops_pairwise_distance": ([_I, _I, _I, _P, _P], True),
-    "pcops_knn_topk": ([_I, _I, _I, _P, _P], True),
-    "pcops_knn_graph": ([_I, _I, _I, _I, _P, _P], True),
-    "pcops_knn_graph_seeded": ([_I, _I, _I, _I, _P, _P, _P], True),
-    "pcops_edge_feature": ([_I, _I, _I, _I, _P, _P, _P], True),
-    "pcops_edge_feature_grad": ([_I, _I, _I, _I, _P, _P, _P], True),
-    "pcops_mlp_gemm_fwd": ([_I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P], True),
-    "pcops_mlp_bn_finalize": ([_I, _I, _LL, _P, _P, _P, _P, _P, _F, _F, _I, _P, _P, _P, _P, _P, _P], True),
-    "pcops_mlp_bn_eval_coeffs": ([_I, _P, _P, _P, _P, _F, _P, _P], True),
-    "pcops_mlp_bn_relu_maxpool": ([_LL, _I, _I, _P, _P, _P, _P, _P, _P], True),
-    "pcops_mlp_gemm_fwd_pool": ([_I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P], True),
-    "pcops_mlp_pool_select": ([_LL, _I, _P, _P, _P, _P], True),
-    "pcops_mlp_bn_relu_apply": ([_LL, _I, _P, _P, _P, _P], True),
-    "pcops_mlp_relu_mask_stats": ([_LL, _I, _P, _P, _P, _P, _P, _P], True),
-    "pcops_mlp_pool_bwd_stats": ([_LL, _I, _P, _P, _P, _P, _P, _P], True),
-    "pcops_mlp_pool_bwd_stats_sum": ([_LL, _I, _P, _LL, _P, _LL, _P, _P, _P, _P, _P], True),
-    "pcops_mlp_bn_bwd_coeffs": ([_I, _I, _LL, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P], True),
-    "pcops_mlp_gemm_dgrad": ([_I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P], True),
-    "pcops_mlp_wgrad": ([_LL, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P], True),
-    "pcops_mlp_transpose": ([_I, _I, _P, _P], True),
-    "pcops_small_gemm": ([_I, _I, _I, _P, _I, _P, _I, _P, _I], True),
-    "pcops_small_gemm_ex": ([_I, _I, _I, _P, _I, _I, _P, _I, _I, _P, _P, _I], True),
-    "pcops_mlp_dy_apply": ([_LL, _I] + [_P] * 6, True),
-    "pcops_small_gemm_colsum": ([_I, _I, _I, _P, _I, _I, _P, _I, _I, _P, _P, _I, _P], True),
-    "pcops_small_gemm_pair": ([_P], True),
-    "pcops_mlp_pool_top_prep": ([_I, _I] + [_P] * 8, True),
-    "pcops_mlp_pool_top_finish": ([_I, _I, _LL] + [_P] * 10, True),
-    "pcops_mlp_pool_top_addend": ([_I, _I, _I, _I] + [_P] * 9, True),
-    "pcops_mlp_gemm_dgrad_top": ([_I, _I] + [_P] * 6 + [_LL] + [_P] * 3, True),
-    "pcops_mlp_gram": ([_LL, _I, _P, _I, _P, _P, _P, _P, _P], True),
-    "pcops_mlp_pool_top_wsparse": ([_I, _I, _I, _I] + [_P] * 11, True),
-    "pcops_mlp_pool_top_addend_rows": ([_I, _I, _I, _I] + [_P] * 10, True),
-    "pcops_mlp_gemm_dgrad_top_rows": ([_I, _I] + [_P] * 6 + [_LL] + [_P] * 4, True),
-    "pcops_mlp_gram_rows": ([_LL, _I, _P, _I, _P, _P, _P, _P, _P, _P], True),
-    "pcops_mlp_pool_top_wsparse_rows": ([_I, _I, _I, _I] + [_P] * 13, True),
-    "pcops_sa_gather_fwd": ([_I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P], True),
-    "pcops_mlp_gemm_fwd_xyz": ([_I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P], True),
-    "pcops_mlp_gemm_dgrad_xyz": ([_I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P], True),
-    "pcops_mlp_wgrad_xyz": ([_LL, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P], True),
-    "pcops_edge_pool_fwd": ([_I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P], True),
-    "pcops_edge_pool_out": ([_LL, _I, _P, _P, _P, _P, _P, _P], True),
-    "pcops_edge_pool_bwd": ([_I, _I, _I, _I, _I] + [_P] * 15, True),
-    "pcops_xyz_first_layer_grads": ([_I, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _LL, _P, _P], True),
-    "pcops_cloud_bias_fwd": ([_LL, _I, _I, _P, _P, _P, _P, _P], True),
-    "pcops_cloud_bias_bwd": ([_LL, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P], True),
-    "pcops_edge_first_moments": ([_I, _I, _I, _I, _P, _P, _P, _P], True),
-    "pcops_mlp_bwd_fused_edge": ([_LL, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P], True),
-    "pcops_edge_first_wgrad": ([_I, _I, _I, _I, _I, _P, _P, _P, _P], True),
-    "pcops_edge_first_layer_grads": ([_I, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _LL, _P, _P], True),
-    "pcops_sa_scatter_bwd": ([_I, _I, _I, _I, _I] + [_P] * 22, True),
-    # ---- compacted rows (pcops.h "compacted rows"): the suffix-less signature + a pcops_rows_t* before the stream
-    "pcops_rows_plan": ([_I, _I, _I, _P, _P, _P, _P], True),
-    "pcops_mlp_gemm_fwd_rows": ([_I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P], True),
-    "pcops_mlp_gemm_fwd_xyz_rows": ([_I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P], True),
-    "pcops_mlp_gemm_dgrad_rows": ([_I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P], True),
-    "pcops_mlp_gemm_dgrad_xyz_rows": ([_I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P], True),
-    "pcops_mlp_bwd_fused": ([_LL, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P], True),
-    "pcops_mlp_bwd_fused_rows": ([_LL, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P], True),
-    "pcops_adam_step": ([_LL, _P, _P, _P, _P, _F, _F, _F, _F], True),
-    # round 6: the one-pass backward of a pooled layer with the weight gradient in its Gram form (+ bias)
-    "pcops_mlp_bwd_fused_gw": ([_LL, _I, _I] + [_P] * 9 + [_I] + [_P] * 7, True),
-    "pcops_mlp_bwd_fused_edge_gw": ([_LL, _I, _I] + [_P] * 9 + [_I] + [_P] * 8, True),
-    "pcops_mlp_bwd_fused_xyz_rows": ([_LL, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P], True),
-    "pcops_mlp_wgrad_rows": ([_LL, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P], True),
-    "pcops_mlp_wgrad_xyz_rows": ([_LL, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P], True),
-    "pcops_mlp_bn_relu_maxpool_rows": ([_LL, _I, _P, _P, _P, _P, _P, _P, _P], True),
-    "pcops_mlp_gemm_fwd_pool_rows": ([_I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P], True),
-    "pcops_mlp_pool_combine_rows": ([_LL, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P], True),
-    "pcops_sa_gather_fwd_rows": ([_I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P], True),
-    "pcops_sa_scatter_bwd_rows": ([_I, _I, _I, _I, _I] + [_P] * 23, True),
-    "pcops_knn_point": ([_I, _I, _I, _I, _I, _P, _P, _P, _P], True),
-    "pcops_knn_point_dist": ([_I, _I, _I, _I, _P, _P, _P], True),
-    "pcops_scatter_rows_sorted": ([_I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P], True),
-    "pcops_edge_feature_grad_central": ([_I, _I, _I, _I, _P, _P], True),
-    "pcops_edge_pool_fwd_ld": ([_I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P], True),
-    "pcops_edge_pool_out_ld": ([_LL, _I, _P, _P, _I, _P, _P, _P, _P], True),
-    "pcops_edge_pool_out_ld2": ([_LL, _I, _P, _P, _I, _P, _P, _P, _P, _P, _I], True),
-    "pcops_edge_pool_bwd_ld": ([_I, _I, _I, _I, _I, _P, _I, _P, _I] + [_P] * 10 + [_P, _I, _P, _I, _P], True),
-    "pcops_sa_gather_fwd_ld": ([_I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _P, _P, _P], True),
-    "pcops_sa_scatter_bwd_ld": ([_I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _I, _P, _I, _P, _I, _P], True),
-    "pcops_edge_weights_fwd": ([_I, _I, _I, _P, _P, _P, _P], True),
-    "pcops_edge_weights_bwd": ([_I, _I, _P, _P, _P, _P], True),
-    "pcops_transform3_fwd": ([_I, _I, _P, _P, _P], True),
-    "pcops_transform3_bwd": ([_I, _I, _P, _P, _P, _P, _P], True),
-    "pcops_fc_bn_fwd": ([_I, _I, _P, _P, _P, _P, _P, _I, _F, _F, _I, _I, _P, _P, _P], True),
-    "pcops_fc_bn_bwd": ([_I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P], True),
-    "pcops_softmax_ce": ([_I, _I, _P, _P, _F, _P, _P], True),
-    "pcops_three_nn_weights": ([_I, _I, _P, _P], True),
-    # SpiderConv (csrc/spider.hip)
-    "pcops_spider_taylor_fwd": ([_LL, _I, _P, _P, _P, _P], True),
-    "pcops_spider_taylor_bwd": ([_LL, _I, _P, _P, _P, _P, _P], True),
-    "pcops_spider_conv_fwd": ([_I] * 6 + [_P] * 6, True),
-    "pcops_spider_conv_wgrad": ([_I] * 6 + [_P] * 7, True),
-    "pcops_spider_conv_dgrad": ([_I] * 6 + [_P] * 7, True),
-    "pcops_group_norm_relu_fwd": ([_I, _I, _I, _I, _F] + [_P] * 6, True),
-    "pcops_group_norm_relu_bwd": ([_I, _I, _I, _I] + [_P] * 10, True),
-}
-PLAIN = {
-    "pcops_strerror": ([_I], C.c_char_p),
-    "pcops_abi_version": ([], _I),
-    "pcops_softmax_ce_blocks": ([_I], _I),
-    "pcops_farthest_point_sample_workspace_bytes": ([_I, _I], _U64),
-    "pcops_mlp_stats_rows": ([_I], _I),
-    "pcops_mlp_reduce_workspace_bytes": ([_I], _U64),
-    "pcops_mlp_gemm_fwd_pool_supported": ([_I, _I, _I, _I], _I),
-    "pcops_mlp_xyz_supported": ([_I, _I, _I], _I),
-    "pcops_mlp_bwd_stats_rows": ([_LL], _I),
-    "pcops_mlp_bwd_pool_stats_rows": ([_LL], _I),
-    "pcops_mlp_wgrad_splits": ([_LL, _I, _I], _I),
-    "pcops_mlp_bwd_fused_groups": ([_LL, _I, _I, _I, _I], _I),
-    "pcops_mlp_bwd_fused_gw_groups": ([_LL, _I, _I, _I], _I),
-    "pcops_mlp_bwd_fused_edge_groups": ([_LL, _I, _I, _I, _I], _I),
-    "pcops_gather_stack_rows_supported": ([_I, _I, _I, _I, _I, _I, _P], _I),
-    "pcops_sa_scatter_rows_supported": ([_I, _I, _I, _I], _I),
-    "pcops_sa_gather_stats_rows": ([_LL], _I),
-    "pcops_sa_gather_fwd_stats_rows": ([_I] * 9, _I),
-    "pcops_sa_scatter_rows": ([_I, _I], _I),
-    "pcops_edge_pool_stats_rows": ([_LL], _I),
-    "pcops_edge_pool_fwd_stats_rows": ([_I] * 5, _I),
-    "pcops_edge_ld_supported": ([_I] * 5, _I),
-    "pcops_edge_first_rows": ([], _I),
-    "pcops_cloud_bias_supported": ([_LL, _I, _I], _I),
-    "pcops_cloud_bias_rows": ([_LL], _I),
-    "pcops_edge_first_supported": ([_I] * 5, _I),
-    "pcops_sa_scatter_workspace_bytes": ([_I, _I, _I, _I], _U64),
-    "pcops_rows_max_blocks": ([_I, _I, _I], _U64),
-    "pcops_mlp_gemm_fwd_pool_rows_supported": ([_I, _I, _I], _I),
-    "pcops_scatter_rows_workspace_bytes": ([_I, _I, _I], _U64),
-    "pcops_knn_point_supported": ([_I], _I),
-    "pcops_scatter_rows_sorted_max_ndst": ([], _I),
-    "pcops_scatter_rows_sorted_supported": ([_I, _I], _I),
-    "pcops_mlp_pool_top_supported": ([_I, _I, _I, _I], _I),
-    "pcops_mlp_pool_top_rows_supported": ([_I, _I, _I, _I], _I),
-    "pcops_mlp_pool_top_wsparse_rows_partial": ([_I, _I], _U64),
-    "pcops_knn_graph_path": ([_I, _I, _I, _I, _P], _I),
-    "pcops_last_launch_pipe": ([], _I),
-    "pcops_last_launch_plan": ([_P, _I], _I),
-    "pcops_set_option": ([_I, _I], _I),
-    "pcops_get_option": ([_I], _I),
-    "pcops_set_deterministic": ([_I], None),
-    "pcops_get_deterministic": ([], _I),
-    "pcops_spider_taylor_bwd_workspace_bytes": ([_LL, _I], _U64),
-    "pcops_spider_conv_wgrad_workspace_bytes": ([_I] * 6, _U64),
-    "pcops_group_norm_relu_workspace_bytes": ([_I, _I], _U64),
-}
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "pcops.h")
+
+
+class PcopsError(RuntimeError):
+    pass
+
+
+_SCALARS = {"int": _I, "float": _F, "long long": _LL, "unsigned long long": _U64}
+
+
+def _ctype(decl, fn):
+    """ctypes type of one parameter or return type of include/pcops.h: any pointer is a c_void_p, a scalar is looked
+    up with and then without a trailing parameter name; anything else is refused (a guessed width would pass the wrong
+    arguments silently)"""
+    if "*" in decl:
+        return _P
+    words = [w for w in decl.split() if w != "const"]
+    for ws in (words, words[:-1]):
+        if " ".join(ws) in _SCALARS:
+            return _SCALARS[" ".join(ws)]
+    raise PcopsError("include/pcops.h: no ctypes mapping for '%s' in the declaration of %s" % (decl, fn))
+
+
+def parse_header(text):
+    """(SIGNATURES, PLAIN) from the text of include/pcops.h: every `ret pcops_name(args);` outside comments,
+    preprocessor lines and typedefs.  SIGNATURES: name -> (argtypes without the trailing stream, True) for the entry
+    points whose last parameter is a pcops_stream_t (they return a status); PLAIN: name -> (argtypes, restype)."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", " ", text)
+    text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)
+    text = re.sub(r'extern\s+"C"\s*\{', " ", text)
+    text = re.sub(r"\btypedef\b[^;{]*\{[^}]*\}[^;]*;", " ", text)      # struct / enum bodies
+    text = re.sub(r"\btypedef\b[^;{]*;", " ", text)
+    signatures, plain = {}, {}
+    for stmt in text.split(";"):
+        stmt = " ".join(stmt.split()).lstrip("} ")                      # (the closing brace of extern "C")
+        if not stmt:
+            continue
+        m = re.fullmatch(r"(.*?)\b(pcops_\w+) ?\((.*)\)", stmt)
+        if not m:
+            raise PcopsError("include/pcops.h: cannot read the declaration '%s'" % stmt)
+        ret, name, params = m.group(1).strip(), m.group(2), [a.strip() for a in m.group(3).split(",")]
+        if params == ["void"] or params == [""]:
+            params = []
+        has_stream = bool(params) and params[-1].split()[0] == "pcops_stream_t"
+        argtypes = [_ctype(a, name) for a in (params[:-1] if has_stream else params)]
+        if ret == "void":
+            restype = None
+        elif ret.replace(" ", "") == "constchar*":
+            restype = C.c_char_p
+        elif "*" in ret:
+            raise PcopsError("include/pcops.h: no ctypes mapping for the return type '%s' of %s" % (ret, name))
+        else:
+            restype = _ctype(ret, name)
+        if has_stream:
+            if restype is not _I:
+                raise PcopsError("include/pcops.h: %s takes a stream but does not return a status" % name)
+            signatures[name] = (argtypes, True)
+        else:
+            plain[name] = (argtypes, restype)
+    return signatures, plain
+
+
+# name -> (argtypes without the trailing stream, has_stream)  /  name -> (argtypes, restype): read from the header, the
+# one place an entry point's signature is written down
+with open(HEADER_PATH) as _f:
+    SIGNATURES, PLAIN = parse_header(_f.read())
 
 
 class GemmProblem(C.Structure):
@@ -236,10 +145,6 @@ class Rows:
 _lib = None
 
 
-class PcopsError(RuntimeError):
-    pass
-
-
 def load():
     """dlopen libpcops.so; raises if it has not been built (python __graft_entry__.py)."""
     global _lib
@@ -260,8 +165,8 @@ def load():
         fn.restype = restype
     got = int(lib.pcops_abi_version())
     if got != ABI_VERSION:
-        # the signatures above are positional: a stale or newer library would take the wrong arguments SILENTLY (round 3
-        # inserted stat_pivot mid-signature in five entry points) -- refuse it instead
+        # the signatures are the header's, not the library's: a stale or newer library would take the wrong arguments
+        # SILENTLY (round 3 inserted stat_pivot mid-signature in five entry points) -- refuse it instead
         raise PcopsError("%s reports ABI version %d, this binding is written for %d: rebuild it "
                          "(make -C scanobjectnn_amd/csrc)" % (LIB_PATH, got, ABI_VERSION))
     _lib = lib

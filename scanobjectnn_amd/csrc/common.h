@@ -28,6 +28,27 @@ static inline hipStream_t as_stream(pcops_stream_t s) { return reinterpret_cast<
 
 static inline unsigned cdiv(long long a, long long b) { return (unsigned)((a + b - 1) / b); }
 
+// A kernel whose dynamic LDS may pass the 64 KB default: raise its ceiling to max_lds, launch it, and return the launch's
+// status.  The attribute is set at every call; a refused attribute is PCOPS_ERR_LAUNCH.
+template <typename... Params, typename... Args>
+static inline int pcops_launch_lds(void (*kern)(Params...), dim3 grid, dim3 block, size_t lds, int max_lds, hipStream_t st,
+                                   Args... args) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds) !=
+        hipSuccess)
+        return PCOPS_ERR_LAUNCH;
+    hipLaunchKernelGGL(kern, grid, block, lds, st, args...);
+    return pcops_launch_status();
+}
+
+// A run-time value as a template argument: f(std::integral_constant<int, V>{}) for the V of Vs... that equals v, and its
+// result; `otherwise` when none does.
+template <int... Vs, typename F>
+static inline int pcops_dispatch(int v, int otherwise, F &&f) {
+    int rc = otherwise;
+    (void)((v == Vs && ((rc = f(std::integral_constant<int, Vs>{})), true)) || ...);
+    return rc;
+}
+
 extern "C" int pcops_get_deterministic(void);     // abi.hip: bit-reproducible backward passes requested
 extern "C" int pcops_get_option(int option);      // abi.hip: the arithmetic options of pcops.h (read at every call)
 void pcops_note_pipe(int pipe);                   // abi.hip: what pcops_last_launch_pipe() reports (0 fp32, 1 split bf16, 2 both)

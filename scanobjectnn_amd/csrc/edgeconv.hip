@@ -1210,11 +1210,8 @@ int ec_bwd_fused(int b, int n, int m, int s, int c, const float *Q, int ldq, con
     const unsigned short *codes = reinterpret_cast<const unsigned short *>(perm + (size_t)b * n);
     BwdLdsArgs a = {n, m, s, c, ec_sbits(s), ldq, ldc, lddq, lddc, Q, Ctr, gpool, ysel, SQ, arg, scale, shift, p, q, t,
                     start, perm, codes, dQ, dCtr};
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(ec_bwd_lds_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)kLdsMax) != hipSuccess)
-        return PCOPS_ERR_LAUNCH;
-    hipLaunchKernelGGL(ec_bwd_lds_kernel, dim3((unsigned)b * (c / kBwdCh)), dim3(1024), ec_bwd_lds_bytes(m, s), st, a);
-    return pcops_launch_status();
+    return pcops_launch_lds(ec_bwd_lds_kernel, dim3((unsigned)b * (c / kBwdCh)), dim3(1024), ec_bwd_lds_bytes(m, s),
+                            (int)kLdsMax, st, a);
 }
 
 
@@ -1282,14 +1279,10 @@ int ec_edge_pool_fwd(int b, int n, int m, int s, int c, const float *Q, int ldq,
     const bool blocked = s > 20;          // the instances that fold the group's shifted sum every 16 terms (ec_fwd_groups)
     if (ec_lds_on() && ec_lds_fwd_ok(n)) {
         const size_t lds = (size_t)n * 64 + 16 * 2 * kSliceCh * sizeof(float);
-        const void *fn = blocked ? reinterpret_cast<const void *>(ec_fwd_lds_kernel<true>)
-                                 : reinterpret_cast<const void *>(ec_fwd_lds_kernel<false>);
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax) != hipSuccess)
-            return PCOPS_ERR_LAUNCH;
-        pcops_note_plan(10, 2, stats ? b : 0, blocked ? 1 : 0, ld_form ? 1 : 0);
-        if (blocked) hipLaunchKernelGGL(ec_fwd_lds_kernel<true>, dim3((unsigned)b * (c / kSliceCh)), dim3(1024), lds, st, a);
-        else hipLaunchKernelGGL(ec_fwd_lds_kernel<false>, dim3((unsigned)b * (c / kSliceCh)), dim3(1024), lds, st, a);
-        return pcops_launch_status();
+        const int rc = pcops_launch_lds(blocked ? ec_fwd_lds_kernel<true> : ec_fwd_lds_kernel<false>,
+                                        dim3((unsigned)b * (c / kSliceCh)), dim3(1024), lds, (int)kLdsMax, st, a);
+        if (!rc) pcops_note_plan(10, 2, stats ? b : 0, blocked ? 1 : 0, ld_form ? 1 : 0);
+        return rc;
     }
     const unsigned grid = (unsigned)((long long)b * (c / 64) * (m / kGB));
     const size_t lds = ((size_t)kGB * s + kSets * 128) * sizeof(float);
@@ -1324,23 +1317,12 @@ int ec_csr_build(int b, int n, int m, int s, const int *idx, void *workspace, hi
     unsigned short *codes = reinterpret_cast<unsigned short *>(perm + (size_t)b * n);
     const size_t lds = ((size_t)n + 2048) * sizeof(int);
     const int sbits = ec_sbits(s);
-    const bool stage = ec_codes16_ok(m, s) && lds + (size_t)m * s * 2 <= 160 * 1024;
-    if (stage) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(ec_csr_build_kernel<true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-            return PCOPS_ERR_LAUNCH;
-        pcops_note_plan_field(3, 1);
-        hipLaunchKernelGGL(ec_csr_build_kernel<true>, dim3(b), dim3(1024), lds + (size_t)m * s * 2, st, n, m, s, sbits, idx, order,
-                           start, perm, codes);
-    } else {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(ec_csr_build_kernel<false>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-            return PCOPS_ERR_LAUNCH;
-        pcops_note_plan_field(3, 0);
-        hipLaunchKernelGGL(ec_csr_build_kernel<false>, dim3(b), dim3(1024), lds, st, n, m, s, sbits, idx, order, start, perm,
-                           codes);
-    }
-    return pcops_launch_status();
+    const bool stage = ec_codes16_ok(m, s) && lds + (size_t)m * s * 2 <= 160 * 1024;     // the codes staged in LDS as well
+    const int rc = pcops_launch_lds(stage ? ec_csr_build_kernel<true> : ec_csr_build_kernel<false>, dim3(b), dim3(1024),
+                                    lds + (stage ? (size_t)m * s * 2 : 0), 160 * 1024, st, n, m, s, sbits, idx, order, start, perm,
+                                    codes);
+    if (!rc) pcops_note_plan_field(3, stage ? 1 : 0);
+    return rc;
 }
 
 int ec_walk(int b, int n, int m, int s, int c, const float *Q, int ldq, const float *Ctr, int ldc, const float *G,
@@ -1349,15 +1331,13 @@ int ec_walk(int b, int n, int m, int s, int c, const float *Q, int ldq, const fl
     const int *start = reinterpret_cast<const int *>(order + (size_t)b * m * s);
     WalkArgs a = {b, n, m, s, c, ldq, ldc, lddq, Q, Ctr, G, p, q, t, order, start, dQ};
     if (!G && ec_lds_on() && ec_lds_walk_ok(n, m, s) && c % kWalkCh == 0) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(ec_walk_lds_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)kLdsMax) != hipSuccess)
-            return PCOPS_ERR_LAUNCH;
         const int *perm = start + (size_t)b * (n + 1);
         const unsigned short *codes = reinterpret_cast<const unsigned short *>(perm + (size_t)b * n);
         WalkLdsArgs wa = {a, perm, codes, ec_sbits(s)};
-        pcops_note_plan_field(2, 2);
-        hipLaunchKernelGGL(ec_walk_lds_kernel, dim3((unsigned)b * (c / kWalkCh)), dim3(1024), ec_lds_walk_bytes(n, m, s), st, wa);
-        return pcops_launch_status();
+        const int rc = pcops_launch_lds(ec_walk_lds_kernel, dim3((unsigned)b * (c / kWalkCh)), dim3(1024),
+                                        ec_lds_walk_bytes(n, m, s), (int)kLdsMax, st, wa);
+        if (!rc) pcops_note_plan_field(2, 2);
+        return rc;
     }
     const unsigned grid = (unsigned)((long long)b * (c / 64) * ((n + kGB - 1) / kGB));
     pcops_note_plan_field(2, 1);
@@ -1380,12 +1360,8 @@ int ec_sparse(int b, int n, int m, int s, int c, const float *gpool, const float
               int ldc, const unsigned char *arg, const int *idx, const float *scale, const float *shift, const float *p,
               const float *q, const float *t, float *dCtr, int lddc, float *dQ, int lddq, hipStream_t st) {
     SparseArgs a = {n, m, s, c, ldc, lddq, lddc, gpool, ysel, SQ, Ctr, arg, idx, scale, shift, p, q, t, dCtr, dQ};
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(ec_sparse_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)kLdsMax) != hipSuccess)
-        return PCOPS_ERR_LAUNCH;
-    hipLaunchKernelGGL(ec_sparse_kernel, dim3((unsigned)b * (c / kSparseSlice)), dim3(1024), (size_t)n * kSparseSlice * sizeof(float),
-                       st, a);
-    return pcops_launch_status();
+    return pcops_launch_lds(ec_sparse_kernel, dim3((unsigned)b * (c / kSparseSlice)), dim3(1024),
+                            (size_t)n * kSparseSlice * sizeof(float), (int)kLdsMax, st, a);
 }
 
 // ---- the concatenated EdgeConv weight ---------------------------------------------------------------------------------

@@ -662,20 +662,6 @@ __global__ __launch_bounds__(1024) void sa_scatter_lds_kernel(ScatterArgs a) {
     }
 }
 
-template <bool POOLED, int CS>
-static int launch_scatter_lds(const ScatterArgs &a, size_t lds, hipStream_t st) {
-    // rebuilding Y pays when it costs arithmetic only (coordinate term + bias); a Q / Ctr row gathered per grouped
-    // row is slower than streaming the stored Y
-    const bool rc = (a.fW || a.fbias) && !a.fQ && !a.fCtr;
-    auto kern = rc ? sa_scatter_lds_kernel<POOLED, CS, true> : sa_scatter_lds_kernel<POOLED, CS, false>;
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            160 * 1024) != hipSuccess)
-        return PCOPS_ERR_LAUNCH;
-    const unsigned grid = (unsigned)((a.b + 7) / 8 * 8 * a.nsl * a.gsplit);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(1024), lds, st, a);
-    return pcops_launch_status();
-}
-
 // slice width: the widest of 64/32/16/8 that divides C and whose LDS footprint fits; 0 = none (fallback kernel)
 static int scatter_lds_slice(int n, int C, bool has_dq, bool has_xyz, size_t *lds) {
     for (int cs = 64; cs >= 8; cs >>= 1) {
@@ -1849,30 +1835,52 @@ __global__ __launch_bounds__(256) void sum_rows_kernel(int P, int L, const float
 
 }  // namespace
 
+// an on/off switch of the environment (its caller reads it once): "0" switches off what is on by default, "1" switches on
+// what is off
+static bool env_switch(const char *name, bool dflt) {
+    const char *e = getenv(name);
+    return dflt ? !(e && e[0] == '0') : (e && e[0] == '1');
+}
+
 static bool scatter_csr_enabled() {
-    static const bool on = [] {
-        const char *e = getenv("PCOPS_SCATTER_CSR");
-        return !(e && e[0] == '0');
-    }();
+    static const bool on = env_switch("PCOPS_SCATTER_CSR", true);
     return on;
 }
 
 // owner walk outside deterministic mode: measured 2569 us against 592 us of the chunked form on the SA2 scatter of the
 // headline step (a few low-index points own lists hundreds of rows long and serialise their waves) -- off by default
 static bool scatter_owner_enabled() {
-    static const bool on = [] {
-        const char *e = getenv("PCOPS_SCATTER_OWNER");
-        return e && e[0] == '1';
-    }();
+    static const bool on = env_switch("PCOPS_SCATTER_OWNER", false);
     return on;
 }
 
 static bool scatter_lds_enabled() {
-    static const bool on = [] {
-        const char *e = getenv("PCOPS_SCATTER_LDS");
-        return !(e && e[0] == '0');
-    }();
+    static const bool on = env_switch("PCOPS_SCATTER_LDS", true);
     return on;
+}
+
+// ---- the inverse index of a cloud's rows (sa_csr_build_kernel) in the caller's workspace:
+//   order (b x rows int2) | start (b (n + 1) int32, padded to an even count) | the lists again in ascending row order
+// The size the queries report and the carving the launchers use are the one layout written here.
+static unsigned long long csr_workspace_bytes(int b, long long rows, int n) {
+    return sizeof(int) * (4ull * b * rows + (unsigned long long)b * (n + 1) + 2);
+}
+struct CsrLists { int2 *order; int *start; int2 *sorted; };      // sorted: NULL unless the ordered lists were asked for
+static int csr_build(int b, int n, int m, int s, int rows, const int *idx, void *workspace, const RowBlock *blocks,
+                     const int *bstart, bool ordered, hipStream_t st, CsrLists *out) {
+    out->order = static_cast<int2 *>(workspace);
+    out->start = reinterpret_cast<int *>(out->order + (size_t)b * rows);
+    out->sorted = ordered ? reinterpret_cast<int2 *>(out->start + (((size_t)b * (n + 1) + 1) & ~(size_t)1)) : nullptr;
+    return pcops_launch_lds(sa_csr_build_kernel, dim3(b), dim3(1024), (2 * (size_t)n + 1024) * sizeof(int), 160 * 1024, st, n,
+                            rows, idx, out->order, out->start, m, s, blocks, bstart, out->sorted);
+}
+
+// wpartial is [rows][4][c]: dWxyz (3, c) is the sum of its first three planes over the rows, dbias (c) of the fourth
+static int reduce_wpartial(const float *wp, int rows, int c, float *dWxyz, float *dbias, hipStream_t st) {
+    if (!wp) return PCOPS_OK;
+    if (dWxyz) hipLaunchKernelGGL(sum_rows_kernel, dim3(3 * c), dim3(256), 0, st, rows, 4 * c, wp, dWxyz);
+    if (dbias) hipLaunchKernelGGL(sum_rows_kernel, dim3(c), dim3(256), 0, st, rows, 4 * c, wp + 3 * c, dbias);
+    return pcops_launch_status();
 }
 
 extern "C" {
@@ -1890,12 +1898,11 @@ int pcops_sa_scatter_rows(int b, int m) {
 }
 
 unsigned long long pcops_sa_scatter_workspace_bytes(int b, int n, int m, int s) {
-    // order | start | order rewritten in ascending row order (deterministic mode)
-    return sizeof(int) * (4ull * b * m * s + (unsigned long long)b * (n + 1) + 2);
+    return csr_workspace_bytes(b, (long long)m * s, n);
 }
 
 unsigned long long pcops_scatter_rows_workspace_bytes(int b, int rows, int ndst) {
-    return sizeof(int) * (4ull * b * rows + (unsigned long long)b * (ndst + 1) + 2);
+    return csr_workspace_bytes(b, rows, ndst);
 }
 
 // the per-cloud counting sort keeps two ndst-sized tables (+ 1024 ints of scan scratch) in the 160 KB of LDS
@@ -1912,21 +1919,14 @@ int pcops_scatter_rows_sorted(int b, int rows, int ndst, int c, int div, int ld_
     PCOPS_REQUIRE_PTR(out); PCOPS_REQUIRE_PTR(workspace);
     if (rows > 0) { PCOPS_REQUIRE_PTR(idx); PCOPS_REQUIRE_PTR(src); }
     if (reinterpret_cast<uintptr_t>(workspace) & 7) return PCOPS_ERR_UNSUPPORTED;
-    const size_t blds = (2 * (size_t)ndst + 1024) * sizeof(int);
     if (!pcops_scatter_rows_sorted_supported(rows, ndst)) return PCOPS_ERR_UNSUPPORTED;
     hipStream_t st = as_stream(stream);
-    int2 *order = static_cast<int2 *>(workspace);
-    int *start = reinterpret_cast<int *>(order + (size_t)b * rows);
-    int2 *sorted = reinterpret_cast<int2 *>(start + (((size_t)b * (ndst + 1) + 1) & ~(size_t)1));
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(sa_csr_build_kernel),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-        return PCOPS_ERR_LAUNCH;
-    hipLaunchKernelGGL(sa_csr_build_kernel, dim3(b), dim3(1024), blds, st, ndst, rows, idx, order, start, 1, rows > 0 ? rows : 1,
-                       (const RowBlock *)nullptr, (const int *)nullptr, sorted);
+    CsrLists l;
+    if (const int rc = csr_build(b, ndst, 1, rows > 0 ? rows : 1, rows, idx, workspace, nullptr, nullptr, true, st, &l)) return rc;
     const long long total = (long long)b * ndst * c;
     const unsigned grid = cdiv(total, 256) < 32768u ? cdiv(total, 256) : 32768u;
     hipLaunchKernelGGL(scatter_rows_sorted_kernel, dim3(grid), dim3(256), 0, st, total, rows, ndst, c, div, ld_src, w, src,
-                       sorted, start, out, accumulate);
+                       l.sorted, l.start, out, accumulate);
     return pcops_launch_status();
 }
 
@@ -1955,9 +1955,10 @@ static bool scatter_csr_shape(int n, int m, int s, int c) {
     return (c == 32 || c == 64 || c == 128 || (c > 0 && c % 256 == 0)) && n <= 16384 && (long long)m * s < (1ll << 30) &&
            2 * (size_t)n * 4 + 4096 <= 160 * 1024;
 }
+static bool scatter_csr_ok(int n, int m, int s, int c) { return scatter_csr_enabled() && scatter_csr_shape(n, m, s, c); }
 
 int pcops_sa_scatter_rows_supported(int n, int m, int s, int c) {
-    return (scatter_csr_enabled() && s % kBlk == 0 && scatter_csr_shape(n, m, s, c)) ? 1 : 0;
+    return (s % kBlk == 0 && scatter_csr_ok(n, m, s, c)) ? 1 : 0;
 }
 
 static int gather_rows_ok(const pcops_rows_t *rows, int s) {
@@ -1967,15 +1968,34 @@ static int gather_rows_ok(const pcops_rows_t *rows, int s) {
     return PCOPS_OK;
 }
 
-// the Q + Ctr form with a stored Y (the T-Net's first layer, dgcnn/models/transform_nets.py:18) runs on edgeconv.hip's
-// forward kernel, which writes one row of partial statistics per 64 groups
-static bool gather_fwd_is_ec(int b, int n, int m, int s, int c, bool has_q, bool has_ctr, bool other_terms, bool compacted) {
-    return has_q && has_ctr && !other_terms && !compacted && ec_fwd_supported(b, n, m, s, c);
+// ---- pcops_sa_gather_fwd(_rows): the plan.  `stats_rows` is what the path writes when it is handed a statistics buffer
+// (and what pcops_sa_gather_fwd_stats_rows tells the caller to allocate: the plan answers for any shape, valid or not).
+struct GatherFwdPlan {
+    enum Kind { kEc, kMoments, kKernel } kind;
+    int stats_rows, gpb;      // gpb: groups per workgroup (kMoments, kKernel)
+};
+struct GatherFwdCall {        // the shape, and which optional operands the call was handed
+    int b, n, m, s, c;
+    bool has_q, has_ctr, other_terms, compacted, has_y, moments_only;
+};
+static GatherFwdPlan gather_fwd_plan(const GatherFwdCall &k) {
+    const long long G = (long long)k.b * k.m;
+    GatherFwdPlan pl = {GatherFwdPlan::kKernel, pcops_sa_gather_stats_rows(G), gather_groups_per_block(G)};
+    // the Q + Ctr form with a stored Y (the T-Net's first layer, dgcnn/models/transform_nets.py:18) runs on edgeconv.hip's
+    // forward kernel, which writes one row of partial statistics per 64 groups
+    if (k.has_q && k.has_ctr && !k.other_terms && !k.compacted && ec_fwd_supported(k.b, k.n, k.m, k.s, k.c) && k.has_y) {
+        pl.kind = GatherFwdPlan::kEc;
+        pl.stats_rows = ec_stats_rows(G);
+        return pl;
+    }
+    // arithmetic first layer, statistics only: its two sums per channel follow from the nine offset moments
+    if (k.moments_only && pcops_get_option(PCOPS_OPT_XYZ_STATS_MOMENTS) != 0) pl.kind = GatherFwdPlan::kMoments;
+    return pl;
 }
+
+// (the query cannot see whether Y is stored: it answers for a stored Y, pcops.h)
 int pcops_sa_gather_fwd_stats_rows(int b, int n, int m, int s, int c, int has_q, int has_ctr, int other_terms, int compacted) {
-    if (gather_fwd_is_ec(b, n, m, s, c, has_q != 0, has_ctr != 0, other_terms != 0, compacted != 0))
-        return ec_stats_rows((long long)b * m);
-    return pcops_sa_gather_stats_rows((long long)b * m);
+    return gather_fwd_plan({b, n, m, s, c, has_q != 0, has_ctr != 0, other_terms != 0, compacted != 0, true, false}).stats_rows;
 }
 
 int pcops_sa_gather_fwd(int b, int n, int m, int s, int c, const float *Q, const float *Ctr, const float *xyz,
@@ -2003,36 +2023,134 @@ int pcops_sa_gather_fwd_rows(int b, int n, int m, int s, int c, const float *Q, 
     PCOPS_REQUIRE_ARG(Q != nullptr || Wxyz != nullptr);
     if (off4 || moments) PCOPS_REQUIRE_PTR(Wxyz);
     if (Wxyz) { PCOPS_REQUIRE_PTR(xyz); PCOPS_REQUIRE_PTR(new_xyz); }
-    if (gather_fwd_is_ec(b, n, m, s, c, Q != nullptr, Ctr != nullptr, Wxyz != nullptr || bias != nullptr || off4 != nullptr ||
-                         moments != nullptr, rows != nullptr) && Y != nullptr) {
-        // (writes pcops_sa_gather_fwd_stats_rows(...) rows of partial statistics -- fewer than the shape-less upper bound
-        // pcops_sa_gather_stats_rows(G): ABI version 4, pcops.h)
-        return ec_gather_fwd(b, n, m, s, c, Q, c, Ctr, c, idx, Y, stats_partial, stat_pivot, false, as_stream(stream));
-    }
-    if (!Y && !Q && !Ctr && Wxyz && moments && stats_partial && pcops_get_option(PCOPS_OPT_XYZ_STATS_MOMENTS) != 0) {
-        // arithmetic first layer, statistics only: its two sums per channel follow from the nine offset moments
-        const int P = pcops_sa_gather_stats_rows(G);
-        hipStream_t st = as_stream(stream);
-        pcops_note_plan(16, gather_groups_per_block(G), P, 1, rows ? 4 : 0);
-        hipLaunchKernelGGL(sa_gather_offsets_kernel, dim3(P), dim3(256), 0, st, G, n, m, s, xyz, new_xyz, idx, off4, moments,
-                           gather_groups_per_block(G), rows ? static_cast<const RowBlock *>(rows->blocks) : nullptr,
-                           rows ? rows->block_start : nullptr);
-        const unsigned zg = cdiv((long long)(P - 1) * 2 * c, 256 * 8);
-        hipLaunchKernelGGL(xyz_stats_from_moments_kernel, dim3(zg < 1u ? 1u : (zg > 1024u ? 1024u : zg)), dim3(256), 0, st, P, c,
-                           (double)G * s, moments, Wxyz, bias, stat_pivot, stats_partial);
-        return pcops_launch_status();
+    const GatherFwdPlan pl = gather_fwd_plan({b, n, m, s, c, Q != nullptr, Ctr != nullptr,
+                                              Wxyz != nullptr || bias != nullptr || off4 != nullptr || moments != nullptr,
+                                              rows != nullptr, Y != nullptr,
+                                              !Y && !Q && !Ctr && Wxyz && moments && stats_partial});
+    hipStream_t st = as_stream(stream);
+    const RowBlock *rblocks = rows ? static_cast<const RowBlock *>(rows->blocks) : nullptr;
+    const int *rbstart = rows ? rows->block_start : nullptr;
+    switch (pl.kind) {
+        case GatherFwdPlan::kEc:
+            return ec_gather_fwd(b, n, m, s, c, Q, c, Ctr, c, idx, Y, stats_partial, stat_pivot, false, st);
+        case GatherFwdPlan::kMoments: {
+            const int P = pl.stats_rows;
+            pcops_note_plan(16, pl.gpb, P, 1, rows ? 4 : 0);
+            hipLaunchKernelGGL(sa_gather_offsets_kernel, dim3(P), dim3(256), 0, st, G, n, m, s, xyz, new_xyz, idx, off4, moments,
+                               pl.gpb, rblocks, rbstart);
+            const unsigned zg = cdiv((long long)(P - 1) * 2 * c, 256 * 8);
+            hipLaunchKernelGGL(xyz_stats_from_moments_kernel, dim3(zg < 1u ? 1u : (zg > 1024u ? 1024u : zg)), dim3(256), 0, st, P, c,
+                               (double)G * s, moments, Wxyz, bias, stat_pivot, stats_partial);
+            return pcops_launch_status();
+        }
+        case GatherFwdPlan::kKernel: break;
     }
     const int rl = 256 / (c / 4);
-    static const bool nt_on = [] { const char *e = getenv("PCOPS_NT_STORE"); return !(e && e[0] == '0'); }();   // kernel A/B only
+    static const bool nt_on = env_switch("PCOPS_NT_STORE", true);   // kernel A/B only
     const size_t staged = (size_t)(s >= 1024 ? s : 1024) * 4;      // floats: (dx, dy, dz, index) per staged row
-    if (((size_t)rl * 2 * c + staged) * sizeof(float) > 64 * 1024) return PCOPS_ERR_UNSUPPORTED;
-    pcops_note_plan(16, gather_groups_per_block(G), stats_partial ? pcops_sa_gather_stats_rows(G) : 0, 0, rows ? 4 : 0);
-    hipLaunchKernelGGL(sa_gather_fwd_kernel, dim3(pcops_sa_gather_stats_rows(G)), dim3(256),
-                       ((size_t)rl * 2 * c + staged) * sizeof(float), as_stream(stream), G, n, m, s, c, Q, Ctr, xyz, new_xyz,
-                       Wxyz, bias, idx, Y, off4, stats_partial, stat_pivot, moments, gather_groups_per_block(G),
-                       rows ? static_cast<const RowBlock *>(rows->blocks) : nullptr, rows ? rows->block_start : nullptr,
+    const size_t lds = ((size_t)rl * 2 * c + staged) * sizeof(float);
+    if (lds > 64 * 1024) return PCOPS_ERR_UNSUPPORTED;
+    pcops_note_plan(16, pl.gpb, stats_partial ? pl.stats_rows : 0, 0, rows ? 4 : 0);
+    hipLaunchKernelGGL(sa_gather_fwd_kernel, dim3(pl.stats_rows), dim3(256), lds, st, G, n, m, s, c, Q, Ctr, xyz, new_xyz,
+                       Wxyz, bias, idx, Y, off4, stats_partial, stat_pivot, moments, pl.gpb, rblocks, rbstart,
                        (nt_on && Y && G * s * c * 4 >= (256ll << 20)) ? 1 : 0);
     return pcops_launch_status();
+}
+
+// ---- pcops_sa_scatter_bwd(_rows): the plan.  Every condition of the entry point below is taken here, once, from the
+// shape, which operands are present, deterministic mode and the switches; `status` refuses the call.
+struct ScatterCall {
+    int b, n, m, s, c;
+    bool rows, G, Y, gpool, xyz, dQ, dCtr, wp, fQ, fCtr, fW, fbias, workspace;
+};
+struct ScatterPlan {
+    int status;
+    int path;                 // the code pcops_last_launch_plan reports: 13, 8, 9, 14, 15
+    // 8 / 9, the gather (CSR) formulation of the feature gradient
+    int lpr;                  // lanes per row
+    bool ordered;             // lists in ascending row order (deterministic mode)
+    bool split;               // per-group outputs / pooled form: a streaming pass of the LDS kernel first
+    bool qform, small;        // 8: Y rebuilt from Q; fewer 64-row chunks than waves
+    // 14, and the streaming pass of 8 / 9 (cs == 0: none): the LDS-slice kernel
+    int cs, gsplit;
+    size_t lds;
+};
+// workgroups per cloud of a pure streaming pass: enough to fill the chip
+static int scatter_gsplit(int b, int m, int nsl) {
+    int gsplit = kCsrGrid / ((b + 7) / 8 * 8 * nsl);
+    if (gsplit > (m + 15) / 16) gsplit = (m + 15) / 16;
+    return gsplit < 1 ? 1 : gsplit;
+}
+static ScatterPlan scatter_plan(const ScatterCall &k) {
+    ScatterPlan pl = {PCOPS_OK, 15, k.c <= 256 ? k.c / 4 : 64, false, false, false, false, 0, 1, 0};
+    const bool det = pcops_get_deterministic() != 0;
+    // round 5 (edgeconv.hip), the Q + Ctr form:  sum over the rows of a point of  q Y  is  q (cnt Q[i] + sum Ctr[g]),
+    // so Y is not read at all and G is read twice (streamed per group for dCtr, gathered per point for dQ)
+    if (!k.rows && !k.gpool && k.G && k.dQ && k.dCtr && k.fQ && k.fCtr && !k.fW && !k.fbias && !k.wp && k.workspace && !det &&
+        ec_bwd_supported(k.b, k.n, k.m, k.s, k.c)) {
+        pl.path = 13;
+        return pl;
+    }
+    const bool csr_ok = scatter_csr_ok(k.n, k.m, k.s, k.c);
+    // compacted rows: only the gather formulation walks them.  Deterministic mode: only its owner walk adds a feature
+    // gradient in a fixed order (the pooled single-layer form adds its arg-row term with atomics: no ordered variant)
+    if ((k.rows && !csr_ok) || (det && k.dQ && !(csr_ok && k.workspace && !k.gpool))) {
+        pl.status = PCOPS_ERR_UNSUPPORTED;
+        return pl;
+    }
+    // gather formulation: feature gradient wanted, G materialised, no per-group output
+    if (csr_ok && k.workspace && k.dQ) {
+        pl.split = k.dCtr || k.gpool;
+        pl.ordered = det;
+        pl.path = (!k.gpool && (det || scatter_owner_enabled())) ? 9 : 8;
+        if (pl.split) {
+            pl.cs = scatter_lds_slice(k.n, k.c, false, k.xyz, &pl.lds);
+            if (!pl.cs) pl.status = PCOPS_ERR_UNSUPPORTED;
+            else pl.gsplit = scatter_gsplit(k.b, k.m, k.c / pl.cs);
+        }
+        pl.small = (long long)k.b * ((k.m * k.s + 63) / 64) < 4 * kCsrGrid;
+        // Q form (sa_scatter_csr_q_kernel): Y = Q[idx] + offsets Wxyz + bias is a function of what the call was handed
+        // (its lane offsets are 32-bit: a cloud's rows of G and its Q stay below 2^31 bytes)
+        pl.qform = pl.path == 8 && k.G && !pl.split && k.fQ && !k.fCtr && pcops_get_option(PCOPS_OPT_SCATTER_QFORM) != 0 &&
+                   (long long)k.m * k.s * k.c * 4 < (1ll << 31) && (long long)k.n * k.c * 4 < (1ll << 31) &&
+                   (long long)k.b * k.m * (k.s > 12 ? k.s : 12) < (1ll << 31);
+        return pl;
+    }
+    pl.cs = scatter_lds_enabled() ? scatter_lds_slice(k.n, k.c, k.dQ, k.xyz, &pl.lds) : 0;
+    if (pl.cs) {
+        pl.path = 14;
+        if (!k.dQ) pl.gsplit = scatter_gsplit(k.b, k.m, k.c / pl.cs);      // pure streaming: several workgroups per cloud
+        return pl;
+    }
+    // fallback: global atomics (clouds too large for an LDS-resident slice); reads the stored Y
+    if (!k.Y) pl.status = PCOPS_ERR_NULL_POINTER;
+    return pl;
+}
+
+// the LDS-slice kernel: path 14, and the streaming pass of the gather formulation
+static int launch_scatter_lds(const ScatterPlan &pl, const ScatterArgs &a, hipStream_t st) {
+    // rebuilding Y pays when it costs arithmetic only (coordinate term + bias); a Q / Ctr row gathered per grouped
+    // row is slower than streaming the stored Y
+    const bool rc = (a.fW || a.fbias) && !a.fQ && !a.fCtr;
+    const unsigned grid = (unsigned)((a.b + 7) / 8 * 8 * a.nsl * a.gsplit);
+    return pcops_dispatch<64, 32, 16, 8>(pl.cs, PCOPS_ERR_UNSUPPORTED, [&](auto CS) {
+        constexpr int S = decltype(CS)::value;
+        auto kern = a.gpool ? (rc ? sa_scatter_lds_kernel<true, S, true> : sa_scatter_lds_kernel<true, S, false>)
+                            : (rc ? sa_scatter_lds_kernel<false, S, true> : sa_scatter_lds_kernel<false, S, false>);
+        return pcops_launch_lds(kern, dim3(grid), dim3(1024), pl.lds, 160 * 1024, st, a);
+    });
+}
+
+// the Q + Ctr form on edgeconv.hip's kernels (path 13): dense tensors, or the column halves of one product (ld_form)
+static int scatter_qctr(int b, int n, int m, int s, int c, const float *G, const float *p, const float *q, const float *t,
+                        const int *idx, const float *Q, int ldq, const float *Ctr, int ldc, float *dQ, int lddq, float *dCtr,
+                        int lddc, void *workspace, bool ld_form, hipStream_t st) {
+    pcops_note_plan(13, 0, 0, 0, ld_form ? 1 : 0);
+    int rc = ec_csr_build(b, n, m, s, idx, workspace, st);
+    if (rc) return rc;
+    rc = ec_tnet_ctr(b, n, m, s, c, Q, ldq, Ctr, ldc, G, idx, p, q, t, dCtr, lddc, st);
+    if (rc) return rc;
+    return ec_walk(b, n, m, s, c, Q, ldq, Ctr, ldc, G, p, q, t, workspace, dQ, lddq, st);
 }
 
 int pcops_sa_scatter_bwd(int b, int n, int m, int s, int c, const float *G, const float *Y, const float *p,
@@ -2068,8 +2186,9 @@ int pcops_sa_scatter_bwd_rows(int b, int n, int m, int s, int c, const float *G,
     PCOPS_REQUIRE_SHAPE(c <= 1024 && (c >= 256 || 256 % c == 0));
     const long long Gn = (long long)b * m;
     hipStream_t st = as_stream(stream);
+    const size_t dq_bytes = sizeof(float) * (size_t)b * n * c;
     if (Gn == 0) {
-        if (dQ && hipMemsetAsync(dQ, 0, sizeof(float) * (size_t)b * n * c, st) != hipSuccess) return PCOPS_ERR_LAUNCH;
+        if (dQ && hipMemsetAsync(dQ, 0, dq_bytes, st) != hipSuccess) return PCOPS_ERR_LAUNCH;
         return PCOPS_OK;
     }
     if (!rc_fwd) PCOPS_REQUIRE_PTR(Y);
@@ -2084,207 +2203,79 @@ int pcops_sa_scatter_bwd_rows(int b, int n, int m, int s, int c, const float *G,
     } else {
         PCOPS_REQUIRE_PTR(G);
     }
-    if (!rows && !gpool && G && dQ && dCtr && fwd_Q && fwd_Ctr && !fwd_Wxyz && !fwd_bias && !wp && workspace &&
-        !pcops_get_deterministic() && ec_bwd_supported(b, n, m, s, c)) {
-        // round 5 (edgeconv.hip), the Q + Ctr form:  sum over the rows of a point of  q Y  is  q (cnt Q[i] + sum Ctr[g]),
-        // so Y is not read at all and G is read twice (streamed per group for dCtr, gathered per point for dQ)
-        pcops_note_plan(13, 0, 0, 0, 0);
-        int rc = ec_csr_build(b, n, m, s, idx, workspace, st);
-        if (rc) return rc;
-        rc = ec_tnet_ctr(b, n, m, s, c, fwd_Q, c, fwd_Ctr, c, G, idx, p, q, t, dCtr, c, st);
-        if (rc) return rc;
-        return ec_walk(b, n, m, s, c, fwd_Q, c, fwd_Ctr, c, G, p, q, t, workspace, dQ, c, st);
-    }
-    // gather formulation: feature gradient wanted, G materialised, no per-group output
-    const int lpr = c <= 256 ? c / 4 : 64;
-    const bool csr_shape = scatter_csr_shape(n, m, s, c);
-    if (rows && !(scatter_csr_enabled() && csr_shape)) return PCOPS_ERR_UNSUPPORTED;
-    const bool det = pcops_get_deterministic() != 0;
-    // deterministic mode: only the owner walk below adds a feature gradient in a fixed order
-    // (the pooled single-layer form adds its arg-row term with atomics: no ordered variant)
-    if (det && dQ && !(scatter_csr_enabled() && workspace && csr_shape && !gpool)) return PCOPS_ERR_UNSUPPORTED;
-    if (scatter_csr_enabled() && workspace && dQ && csr_shape) {
-        const bool split = dCtr || gpool;        // per-group outputs / pooled form: streaming pass first
-        const bool owner = !gpool && (det || scatter_owner_enabled());
-        if (!owner && hipMemsetAsync(dQ, 0, sizeof(float) * (size_t)b * n * c, st) != hipSuccess) return PCOPS_ERR_LAUNCH;
-        int cs0 = 0;                             // slice width of the streaming pass (plan field [3]; 0: none ran)
-        if (split) {
-            size_t lb = 0;
-            cs0 = scatter_lds_slice(n, c, false, xyz != nullptr, &lb);
-            if (!cs0) return PCOPS_ERR_UNSUPPORTED;
-            const int nsl = c / cs0;
-            int gsplit = kCsrGrid / ((b + 7) / 8 * 8 * nsl);        // enough workgroups to fill the chip
-            if (gsplit > (m + 15) / 16) gsplit = (m + 15) / 16;
-            if (gsplit < 1) gsplit = 1;
-            ScatterArgs sa = {b, n, m, s, c, nsl, gsplit, G, Y, p, q, t, gpool, argmax, pool_scale, pool_shift, idx,
-                              xyz, new_xyz, nullptr, dCtr, wp, gpool ? dQ : nullptr, fwd_Q, fwd_Ctr, fwd_Wxyz,
-                              fwd_bias};
-            int rc0 = PCOPS_ERR_UNSUPPORTED;
-            switch (cs0) {
-                case 64: rc0 = gpool ? launch_scatter_lds<true, 64>(sa, lb, st) : launch_scatter_lds<false, 64>(sa, lb, st); break;
-                case 32: rc0 = gpool ? launch_scatter_lds<true, 32>(sa, lb, st) : launch_scatter_lds<false, 32>(sa, lb, st); break;
-                case 16: rc0 = gpool ? launch_scatter_lds<true, 16>(sa, lb, st) : launch_scatter_lds<false, 16>(sa, lb, st); break;
-                case 8: rc0 = gpool ? launch_scatter_lds<true, 8>(sa, lb, st) : launch_scatter_lds<false, 8>(sa, lb, st); break;
+    const ScatterPlan pl = scatter_plan({b, n, m, s, c, rows != nullptr, G != nullptr, Y != nullptr, gpool != nullptr,
+                                         xyz != nullptr, dQ != nullptr, dCtr != nullptr, wp != nullptr, fwd_Q != nullptr,
+                                         fwd_Ctr != nullptr, fwd_Wxyz != nullptr, fwd_bias != nullptr, workspace != nullptr});
+    if (pl.status) return pl.status;
+    switch (pl.path) {
+        case 13:
+            return scatter_qctr(b, n, m, s, c, G, p, q, t, idx, fwd_Q, c, fwd_Ctr, c, dQ, c, dCtr, c, workspace, false, st);
+        case 8:
+        case 9: {
+            if (pl.path == 8 && hipMemsetAsync(dQ, 0, dq_bytes, st) != hipSuccess) return PCOPS_ERR_LAUNCH;
+            if (pl.split) {
+                const ScatterArgs sa = {b, n, m, s, c, c / pl.cs, pl.gsplit, G, Y, p, q, t, gpool, argmax, pool_scale,
+                                        pool_shift, idx, xyz, new_xyz, nullptr, dCtr, wp, gpool ? dQ : nullptr, fwd_Q,
+                                        fwd_Ctr, fwd_Wxyz, fwd_bias};
+                int rc = launch_scatter_lds(pl, sa, st);
+                if (!rc) rc = reduce_wpartial(wp, b * pl.gsplit, c, dWxyz, dbias, st);
+                if (rc) return rc;
             }
-            if (rc0) return rc0;
-            if (wp) {
-                const int rows = b * gsplit;
-                if (dWxyz) hipLaunchKernelGGL(sum_rows_kernel, dim3(3 * c), dim3(256), 0, st, rows, 4 * c, wp, dWxyz);
-                if (dbias) hipLaunchKernelGGL(sum_rows_kernel, dim3(c), dim3(256), 0, st, rows, 4 * c, wp + 3 * c, dbias);
-            }
-        }
-        int2 *order = static_cast<int2 *>(workspace);
-        int *start = reinterpret_cast<int *>(order + (size_t)b * m * s);
-        const size_t blds = (2 * (size_t)n + 1024) * sizeof(int);
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(sa_csr_build_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-            return PCOPS_ERR_LAUNCH;
-        int2 *sorted = det ? reinterpret_cast<int2 *>(start + (((size_t)b * (n + 1) + 1) & ~(size_t)1)) : nullptr;
-        hipLaunchKernelGGL(sa_csr_build_kernel, dim3(b), dim3(1024), blds, st, n, m * s, idx, order, start, m, s, rblocks,
-                           rbstart, sorted);
-        float *wp2 = split ? nullptr : wp;
-        CsrArgs a = {b, n, m, s, c, G, Y, p, q, t, xyz, new_xyz, sorted ? sorted : order, dQ, wp2, rblocks, rbstart, start,
-                     fwd_Q, fwd_Wxyz, fwd_bias};
-        if (owner) {
-            pcops_note_plan(9, 0, 0, cs0, rows ? 4 : 0);
-            switch (lpr) {
-                case 8: hipLaunchKernelGGL(sa_scatter_owner_kernel<8>, dim3(kCsrGrid), dim3(256), 0, st, a); break;
-                case 16: hipLaunchKernelGGL(sa_scatter_owner_kernel<16>, dim3(kCsrGrid), dim3(256), 0, st, a); break;
-                case 32: hipLaunchKernelGGL(sa_scatter_owner_kernel<32>, dim3(kCsrGrid), dim3(256), 0, st, a); break;
-                case 64: hipLaunchKernelGGL(sa_scatter_owner_kernel<64>, dim3(kCsrGrid), dim3(256), 0, st, a); break;
-                default: return PCOPS_ERR_UNSUPPORTED;
-            }
-            int rc = pcops_launch_status();
+            CsrLists l;
+            int rc = csr_build(b, n, m, s, m * s, idx, workspace, rblocks, rbstart, pl.ordered, st, &l);
             if (rc) return rc;
-            if (wp2) {
-                if (dWxyz) hipLaunchKernelGGL(sum_rows_kernel, dim3(3 * c), dim3(256), 0, st, kCsrGrid, 4 * c, wp2, dWxyz);
-                if (dbias) hipLaunchKernelGGL(sum_rows_kernel, dim3(c), dim3(256), 0, st, kCsrGrid, 4 * c, wp2 + 3 * c, dbias);
-                rc = pcops_launch_status();
-            }
-            return rc;
+            float *wp2 = pl.split ? nullptr : wp;
+            const CsrArgs a = {b, n, m, s, c, G, Y, p, q, t, xyz, new_xyz, l.sorted ? l.sorted : l.order, dQ, wp2, rblocks,
+                               rbstart, l.start, fwd_Q, fwd_Wxyz, fwd_bias};
+            const int grid = pl.qform ? kCsrQGrid : kCsrGrid;
+            if (pl.path == 9) pcops_note_plan(9, 0, 0, pl.cs, rows ? 4 : 0);
+            else pcops_note_plan(8, pl.qform ? 1 : 0, pl.small ? 16 : 64, pl.cs, rows ? 4 : 0);
+            rc = pcops_dispatch<8, 16, 32, 64>(pl.lpr, PCOPS_ERR_UNSUPPORTED, [&](auto LPR) {
+                constexpr int L = decltype(LPR)::value;
+                void (*kern)(CsrArgs) = sa_scatter_owner_kernel<L>;
+                if (pl.path == 8 && pl.qform) kern = pl.small ? sa_scatter_csr_q_kernel<L, 16> : sa_scatter_csr_q_kernel<L, 64>;
+                else if (pl.path == 8 && gpool) kern = pl.small ? sa_scatter_csr_kernel<L, true, 16> : sa_scatter_csr_kernel<L, true, 64>;
+                else if (pl.path == 8) kern = pl.small ? sa_scatter_csr_kernel<L, false, 16> : sa_scatter_csr_kernel<L, false, 64>;
+                hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, st, a);
+                return pcops_launch_status();
+            });
+            return rc ? rc : reduce_wpartial(wp2, grid, c, dWxyz, dbias, st);
         }
-        const bool small = (long long)b * ((m * s + 63) / 64) < 4 * kCsrGrid;   // fewer 64-row chunks than waves
-        // Q form (sa_scatter_csr_q_kernel): Y = Q[idx] + offsets Wxyz + bias is a function of what the call was handed
-        // (its lane offsets are 32-bit: a cloud's rows of G and its Q stay below 2^31 bytes)
-        const bool qform = G && !split && fwd_Q && !fwd_Ctr && pcops_get_option(PCOPS_OPT_SCATTER_QFORM) != 0 &&
-                           (long long)m * s * c * 4 < (1ll << 31) && (long long)n * c * 4 < (1ll << 31) &&
-                           (long long)b * m * (s > 12 ? s : 12) < (1ll << 31);
-        pcops_note_plan(8, qform ? 1 : 0, small ? 16 : 64, cs0, rows ? 4 : 0);
-        if (qform) {
-#define PCOPS_CSRQ_CASE(LPR_)                                                                                          \
-    case LPR_:                                                                                                         \
-        if (small) hipLaunchKernelGGL((sa_scatter_csr_q_kernel<LPR_, 16>), dim3(kCsrQGrid), dim3(256), 0, st, a);       \
-        else hipLaunchKernelGGL((sa_scatter_csr_q_kernel<LPR_, 64>), dim3(kCsrQGrid), dim3(256), 0, st, a);            \
-        break;
-            switch (lpr) {
-                PCOPS_CSRQ_CASE(8)
-                PCOPS_CSRQ_CASE(16)
-                PCOPS_CSRQ_CASE(32)
-                PCOPS_CSRQ_CASE(64)
-                default: return PCOPS_ERR_UNSUPPORTED;
-            }
-#undef PCOPS_CSRQ_CASE
-        } else {
-#define PCOPS_CSR_LAUNCH(LPR_, Y_, CH_)                                                                            \
-    hipLaunchKernelGGL((sa_scatter_csr_kernel<LPR_, Y_, CH_>), dim3(kCsrGrid), dim3(256), 0, st, a)
-#define PCOPS_CSR_CASE(LPR_)                                             \
-    case LPR_:                                                           \
-        if (gpool) {                                                     \
-            if (small) PCOPS_CSR_LAUNCH(LPR_, true, 16);                 \
-            else PCOPS_CSR_LAUNCH(LPR_, true, 64);                       \
-        } else {                                                         \
-            if (small) PCOPS_CSR_LAUNCH(LPR_, false, 16);                \
-            else PCOPS_CSR_LAUNCH(LPR_, false, 64);                      \
-        }                                                                \
-        break;
-        switch (lpr) {
-            PCOPS_CSR_CASE(8)
-            PCOPS_CSR_CASE(16)
-            PCOPS_CSR_CASE(32)
-            PCOPS_CSR_CASE(64)
-            default: return PCOPS_ERR_UNSUPPORTED;
+        case 14: {
+            const ScatterArgs a = {b, n, m, s, c, c / pl.cs, pl.gsplit, G, Y, p, q, t, gpool, argmax, pool_scale, pool_shift,
+                                   idx, xyz, new_xyz, dQ, dCtr, wp, nullptr, fwd_Q, fwd_Ctr, fwd_Wxyz, fwd_bias};
+            pcops_note_plan(14, pl.cs, gpool ? 1 : 0, ((fwd_Wxyz || fwd_bias) && !fwd_Q && !fwd_Ctr) ? 1 : 0, pl.gsplit);
+            const int rc = launch_scatter_lds(pl, a, st);
+            return rc ? rc : reduce_wpartial(wp, b * pl.gsplit, c, dWxyz, dbias, st);
         }
-#undef PCOPS_CSR_LAUNCH
-#undef PCOPS_CSR_CASE
+        case 15: {      // global atomics
+            if (dQ && hipMemsetAsync(dQ, 0, dq_bytes, st) != hipSuccess) return PCOPS_ERR_LAUNCH;
+            const int rl = c >= 256 ? 1 : 256 / c;
+            const size_t lds = (size_t)rl * 6 * c * sizeof(float);
+            const int gpb = 16;
+            const unsigned grid = (unsigned)((Gn + 15) / 16);
+            pcops_note_plan(15, 0, gpool ? 1 : 0, 0, 0);
+            hipLaunchKernelGGL(gpool ? sa_scatter_bwd_kernel<true> : sa_scatter_bwd_kernel<false>, dim3(grid), dim3(256), lds, st,
+                               Gn, n, m, s, c, G, Y, p, q, t, gpool, argmax, pool_scale, pool_shift, idx, xyz, new_xyz, dQ, dCtr,
+                               wp, gpb);
+            const int rc = pcops_launch_status();
+            // wpartial rows are [block][4][c]: one per workgroup
+            return rc ? rc : reduce_wpartial(wp, (int)grid, c, dWxyz, dbias, st);
         }
-        int rc = pcops_launch_status();
-        if (rc) return rc;
-        if (wp2) {
-            const int wrows = qform ? kCsrQGrid : kCsrGrid;
-            if (dWxyz) hipLaunchKernelGGL(sum_rows_kernel, dim3(3 * c), dim3(256), 0, st, wrows, 4 * c, wp2, dWxyz);
-            if (dbias) hipLaunchKernelGGL(sum_rows_kernel, dim3(c), dim3(256), 0, st, wrows, 4 * c, wp2 + 3 * c, dbias);
-            rc = pcops_launch_status();
-        }
-        return rc;
     }
-    size_t lds_bytes = 0;
-    const int cs = scatter_lds_enabled() ? scatter_lds_slice(n, c, dQ != nullptr, xyz != nullptr, &lds_bytes) : 0;
-    if (cs) {
-        int gsplit = 1;
-        if (!dQ) {                               // pure streaming: deal a cloud's groups to several workgroups
-            gsplit = kCsrGrid / ((b + 7) / 8 * 8 * (c / cs));
-            if (gsplit > (m + 15) / 16) gsplit = (m + 15) / 16;
-            if (gsplit < 1) gsplit = 1;
-        }
-        ScatterArgs a = {b, n, m, s, c, c / cs, gsplit, G, Y, p, q, t, gpool, argmax, pool_scale, pool_shift, idx,
-                         xyz, new_xyz, dQ, dCtr, wp, nullptr, fwd_Q, fwd_Ctr, fwd_Wxyz, fwd_bias};
-        pcops_note_plan(14, cs, gpool ? 1 : 0, ((fwd_Wxyz || fwd_bias) && !fwd_Q && !fwd_Ctr) ? 1 : 0, gsplit);
-        int rc;
-#define PCOPS_SCATTER_CASE(CS_)                                                                   \
-    case CS_:                                                                                     \
-        rc = gpool ? launch_scatter_lds<true, CS_>(a, lds_bytes, st) : launch_scatter_lds<false, CS_>(a, lds_bytes, st); \
-        break;
-        switch (cs) {
-            PCOPS_SCATTER_CASE(64)
-            PCOPS_SCATTER_CASE(32)
-            PCOPS_SCATTER_CASE(16)
-            PCOPS_SCATTER_CASE(8)
-            default: rc = PCOPS_ERR_UNSUPPORTED;
-        }
-#undef PCOPS_SCATTER_CASE
-        if (rc) return rc;
-        if (wp) {
-            const int rows = b * gsplit;
-            if (dWxyz) hipLaunchKernelGGL(sum_rows_kernel, dim3(3 * c), dim3(256), 0, st, rows, 4 * c, wp, dWxyz);
-            if (dbias) hipLaunchKernelGGL(sum_rows_kernel, dim3(c), dim3(256), 0, st, rows, 4 * c, wp + 3 * c, dbias);
-            rc = pcops_launch_status();
-        }
-        return rc;
-    }
-    // fallback: global atomics (clouds too large for an LDS-resident slice); reads the stored Y
-    PCOPS_REQUIRE_PTR(Y);
-    if (dQ && hipMemsetAsync(dQ, 0, sizeof(float) * (size_t)b * n * c, st) != hipSuccess) return PCOPS_ERR_LAUNCH;
-    const int rl = c >= 256 ? 1 : 256 / c;
-    const size_t lds = (size_t)rl * 6 * c * sizeof(float);
-    const int gpb = 16;
-    const unsigned grid = (unsigned)((Gn + 15) / 16);
-    pcops_note_plan(15, 0, gpool ? 1 : 0, 0, 0);
-    if (gpool) {
-        PCOPS_REQUIRE_PTR(argmax); PCOPS_REQUIRE_PTR(pool_scale); PCOPS_REQUIRE_PTR(pool_shift);
-        PCOPS_REQUIRE_SHAPE(s <= 256);
-        hipLaunchKernelGGL((sa_scatter_bwd_kernel<true>), dim3(grid), dim3(256), lds, st, Gn, n, m, s, c, G, Y, p, q,
-                           t, gpool, argmax, pool_scale, pool_shift, idx, xyz, new_xyz, dQ, dCtr, wp, gpb);
-    } else {
-        PCOPS_REQUIRE_PTR(G);
-        hipLaunchKernelGGL((sa_scatter_bwd_kernel<false>), dim3(grid), dim3(256), lds, st, Gn, n, m, s, c, G, Y, p, q,
-                           t, gpool, argmax, pool_scale, pool_shift, idx, xyz, new_xyz, dQ, dCtr, wp, gpb);
-    }
-    int rc = pcops_launch_status();
-    if (rc) return rc;
-    if (wp) {
-        // wpartial rows are [block][4][c]: element e*c + col -> strided view: sum over blocks
-        if (dWxyz) hipLaunchKernelGGL(sum_rows_kernel, dim3(3 * c), dim3(256), 0, st, (int)grid, 4 * c, wp, dWxyz);
-        if (dbias) hipLaunchKernelGGL(sum_rows_kernel, dim3(c), dim3(256), 0, st, (int)grid, 4 * c, wp + 3 * c, dbias);
-        rc = pcops_launch_status();
-    }
-    return rc;
+    return PCOPS_ERR_UNSUPPORTED;      // (no plan has another path)
 }
 
 int pcops_edge_pool_stats_rows(long long G) { return (int)((G + 63) / 64); }
-int pcops_edge_pool_fwd_stats_rows(int b, int n, int m, int s, int c) {
-    if (ec_fwd_supported(b, n, m, s, c) && s <= 256) return ec_edge_pool_stats_rows(b, n, m);
-    return pcops_edge_pool_stats_rows((long long)b * m);
+
+// pcops_edge_pool_fwd: round 5's kernels (edgeconv.hip: 64-channel slices, offsets staged in LDS, XCD-contiguous clouds) where
+// the shape fits, else edge_pool_fwd_kernel; stats_rows is what the path writes and what the query tells the caller to allocate
+struct EdgeFwdPlan { bool ec; int stats_rows; };
+static EdgeFwdPlan edge_pool_fwd_plan(int b, int n, int m, int s, int c) {
+    if (ec_fwd_supported(b, n, m, s, c) && s <= 256) return {true, ec_edge_pool_stats_rows(b, n, m)};
+    return {false, pcops_edge_pool_stats_rows((long long)b * m)};
 }
+int pcops_edge_pool_fwd_stats_rows(int b, int n, int m, int s, int c) { return edge_pool_fwd_plan(b, n, m, s, c).stats_rows; }
 
 int pcops_edge_pool_fwd(int b, int n, int m, int s, int c, const float *Q, const float *Ctr, const int *idx,
                         const float *gamma, float *SQ, float *qsel, unsigned char *arg, float *stats_partial,
@@ -2295,17 +2286,13 @@ int pcops_edge_pool_fwd(int b, int n, int m, int s, int c, const float *Q, const
     if (G == 0) return PCOPS_OK;
     PCOPS_REQUIRE_PTR(Q); PCOPS_REQUIRE_PTR(Ctr); PCOPS_REQUIRE_PTR(idx); PCOPS_REQUIRE_PTR(gamma);
     PCOPS_REQUIRE_PTR(SQ); PCOPS_REQUIRE_PTR(qsel); PCOPS_REQUIRE_PTR(arg);
-    // round 5: 64-channel slices, offsets staged in LDS, XCD-contiguous clouds (edgeconv.hip); same outputs, and
-    // b m / 64 = pcops_edge_pool_stats_rows(G) rows of partial statistics
-    if (ec_fwd_supported(b, n, m, s, c) && s <= 256) {
-        // (writes pcops_edge_pool_fwd_stats_rows(...) rows, not the shape-less upper bound: ABI version 4, pcops.h)
+    const EdgeFwdPlan pl = edge_pool_fwd_plan(b, n, m, s, c);
+    if (pl.ec)
         return ec_edge_pool_fwd(b, n, m, s, c, Q, c, Ctr, c, idx, gamma, SQ, qsel, arg, stats_partial, stat_pivot, false, as_stream(stream));
-    }
     const int gl = 256 / (c / 4);
-    pcops_note_plan(10, 0, stats_partial ? pcops_edge_pool_stats_rows(G) : 0, 0, 0);
-    hipLaunchKernelGGL(edge_pool_fwd_kernel, dim3(pcops_edge_pool_stats_rows(G)), dim3(256),
-                       (size_t)gl * 2 * c * sizeof(float), as_stream(stream), G, n, m, s, c, Q, Ctr, idx, gamma, SQ, qsel,
-                       arg, stats_partial, stat_pivot, 64);
+    pcops_note_plan(10, 0, stats_partial ? pl.stats_rows : 0, 0, 0);
+    hipLaunchKernelGGL(edge_pool_fwd_kernel, dim3(pl.stats_rows), dim3(256), (size_t)gl * 2 * c * sizeof(float),
+                       as_stream(stream), G, n, m, s, c, Q, Ctr, idx, gamma, SQ, qsel, arg, stats_partial, stat_pivot, 64);
     return pcops_launch_status();
 }
 
@@ -2322,6 +2309,43 @@ int pcops_edge_pool_out(long long G, int c, const float *qsel, const float *Ctr,
     return pcops_launch_status();
 }
 
+// ---- pcops_edge_pool_bwd: the plan.  `mode` is field [1] of what pcops_last_launch_plan reports:
+//   0  global atomics: dCtr + arg-row term streamed, dense term by the chunked walk (dQ zeroed first)
+//   1  no global atomics: the sparse arg-row term through an LDS-resident slice (this also initialises dQ, no memset),
+//      then the dense term by the owner of every source point
+//   2  deterministic mode: the first kernel only writes dCtr, the owner adds both terms in ascending row order
+//   3  round 5 (edgeconv.hip): the arg-row term + dCtr as in 1, then the dense term by a leaner owner walk over a packed
+//      inverse index, clouds XCD-contiguous
+//   4  round 5, second half: both terms and dCtr in ONE owner walk (edgeconv.hip ec_bwd_lds_kernel)
+struct EdgeBwdPlan {
+    int status, mode, lpr;
+    size_t slice_lds;         // modes 1, 3
+};
+static EdgeBwdPlan edge_pool_bwd_plan(int b, int n, int m, int s, int c) {
+    static const bool owner = env_switch("PCOPS_EDGE_BWD_OWNER", true);
+    const bool det = pcops_get_deterministic() != 0, some = (long long)b * m > 0;
+    EdgeBwdPlan pl = {PCOPS_OK, 0, c <= 256 ? c / 4 : 64, (size_t)n * kEdgeSlice * sizeof(float)};
+    const bool use_owner = some && c % kEdgeSlice == 0 && (det || (owner && pl.slice_lds <= 160 * 1024));
+    if (det && some && !use_owner) pl.status = PCOPS_ERR_UNSUPPORTED;
+    if (!use_owner) return pl;
+    if (det) pl.mode = 2;
+    else if (!ec_bwd_supported(b, n, m, s, c)) pl.mode = 1;
+    else pl.mode = ec_bwd_fused_ok(n, m, s, c) ? 4 : 3;
+    return pl;
+}
+
+// mode 4, dense tensors or the column halves of one product (ld_form)
+static int edge_bwd_fused(int b, int n, int m, int s, int c, const float *Q, int ldq, const float *Ctr, int ldc, const int *idx,
+                          const float *gpool, const float *ysel, const float *SQ, const unsigned char *arg, const float *scale,
+                          const float *shift, const float *p, const float *q, const float *t, float *dQ, int lddq, float *dCtr,
+                          int lddc, void *workspace, bool ld_form, hipStream_t st) {
+    pcops_note_plan(11, 4, 0, 0, ld_form ? 1 : 0);
+    const int rc = ec_csr_build(b, n, m, s, idx, workspace, st);
+    if (rc) return rc;
+    return ec_bwd_fused(b, n, m, s, c, Q, ldq, Ctr, ldc, gpool, ysel, SQ, arg, scale, shift, p, q, t, workspace, dQ, lddq, dCtr,
+                        lddc, st);
+}
+
 int pcops_edge_pool_bwd(int b, int n, int m, int s, int c, const float *Q, const float *Ctr, const int *idx,
                         const float *gpool, const float *ysel, const float *SQ, const unsigned char *arg,
                         const float *scale, const float *shift, const float *p, const float *q, const float *t,
@@ -2331,94 +2355,57 @@ int pcops_edge_pool_bwd(int b, int n, int m, int s, int c, const float *Q, const
     PCOPS_REQUIRE_PTR(dQ);
     hipStream_t st = as_stream(stream);
     const long long G = (long long)b * m;
-    static const bool owner = [] { const char *e = getenv("PCOPS_EDGE_BWD_OWNER"); return !(e && e[0] == '0'); }();
-    const bool det = pcops_get_deterministic() != 0;
-    const size_t slice_lds = (size_t)n * kEdgeSlice * sizeof(float);
-    const bool use_owner = G > 0 && c % kEdgeSlice == 0 && (det || (owner && slice_lds <= 160 * 1024));
-    if (det && G > 0 && !use_owner) return PCOPS_ERR_UNSUPPORTED;
-    if (!use_owner && hipMemsetAsync(dQ, 0, sizeof(float) * (size_t)b * n * c, st) != hipSuccess) return PCOPS_ERR_LAUNCH;
+    const EdgeBwdPlan pl = edge_pool_bwd_plan(b, n, m, s, c);
+    if (pl.status) return pl.status;
+    if (pl.mode == 0 && hipMemsetAsync(dQ, 0, sizeof(float) * (size_t)b * n * c, st) != hipSuccess) return PCOPS_ERR_LAUNCH;
     if (G == 0) return PCOPS_OK;
     PCOPS_REQUIRE_PTR(Q); PCOPS_REQUIRE_PTR(Ctr); PCOPS_REQUIRE_PTR(idx); PCOPS_REQUIRE_PTR(gpool); PCOPS_REQUIRE_PTR(ysel);
     PCOPS_REQUIRE_PTR(SQ); PCOPS_REQUIRE_PTR(arg); PCOPS_REQUIRE_PTR(scale); PCOPS_REQUIRE_PTR(shift); PCOPS_REQUIRE_PTR(p);
     PCOPS_REQUIRE_PTR(q); PCOPS_REQUIRE_PTR(t); PCOPS_REQUIRE_PTR(dCtr); PCOPS_REQUIRE_PTR(workspace);
-    if (use_owner && !det && ec_bwd_supported(b, n, m, s, c) && ec_bwd_fused_ok(n, m, s, c)) {
-        // round 5, second half: both terms and dCtr in ONE owner walk (edgeconv.hip ec_bwd_lds_kernel)
-        pcops_note_plan(11, 4, 0, 0, 0);
-        int rc = ec_csr_build(b, n, m, s, idx, workspace, st);
+    if (pl.mode == 4)
+        return edge_bwd_fused(b, n, m, s, c, Q, c, Ctr, c, idx, gpool, ysel, SQ, arg, scale, shift, p, q, t, dQ, c, dCtr, c,
+                              workspace, false, st);
+    const dim3 sgrid(b * (c / kEdgeSlice));
+    if (pl.mode == 3) {
+        int rc = pcops_launch_lds(edge_pool_bwd_sparse_kernel<false>, sgrid, dim3(1024), pl.slice_lds, 160 * 1024, st, n, m, s, c,
+                                  gpool, ysel, SQ, Ctr, arg, idx, scale, shift, p, q, t, dCtr, dQ);
         if (rc) return rc;
-        return ec_bwd_fused(b, n, m, s, c, Q, c, Ctr, c, gpool, ysel, SQ, arg, scale, shift, p, q, t, workspace, dQ, c, dCtr, c, st);
-    }
-    if (use_owner && !det && ec_bwd_supported(b, n, m, s, c)) {
-        // round 5 (edgeconv.hip): the arg-row term + dCtr as before (LDS slices, plain stores: initialises dQ), then the
-        // dense term by a leaner owner walk over a packed inverse index, clouds XCD-contiguous
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(edge_pool_bwd_sparse_kernel<false>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-            return PCOPS_ERR_LAUNCH;
         pcops_note_plan(11, 3, 0, 0, 0);
-        hipLaunchKernelGGL(edge_pool_bwd_sparse_kernel<false>, dim3(b * (c / kEdgeSlice)), dim3(1024), slice_lds, st, n, m, s, c,
-                           gpool, ysel, SQ, Ctr, arg, idx, scale, shift, p, q, t, dCtr, dQ);
-        int rc = ec_csr_build(b, n, m, s, idx, workspace, st);
+        rc = ec_csr_build(b, n, m, s, idx, workspace, st);
         if (rc) return rc;
         return ec_walk(b, n, m, s, c, Q, c, Ctr, c, nullptr, p, q, t, workspace, dQ, c, st);
     }
-    int2 *order = static_cast<int2 *>(workspace);
-    int *start = reinterpret_cast<int *>(order + (size_t)b * m * s);
-    const size_t blds = (2 * (size_t)n + 1024) * sizeof(int);
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(sa_csr_build_kernel),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-        return PCOPS_ERR_LAUNCH;
-    int2 *sorted = det ? reinterpret_cast<int2 *>(start + (((size_t)b * (n + 1) + 1) & ~(size_t)1)) : nullptr;
-    hipLaunchKernelGGL(sa_csr_build_kernel, dim3(b), dim3(1024), blds, st, n, m * s, idx, order, start, m, s,
-                       (const RowBlock *)nullptr, (const int *)nullptr, sorted);
-    const int lpr = c <= 256 ? c / 4 : 64;
-    if (use_owner) {
-        // no global atomics: the sparse arg-row term through an LDS-resident slice (this also initialises dQ, no
-        // memset), then the dense term by the owner of every source point.  Deterministic mode: the first kernel only
-        // writes dCtr, the owner adds both terms in ascending row order.
-        const EdgeSparse sp = {gpool, ysel, scale, shift, p, arg};
-        const unsigned dgrid = 2048;
-#define PCOPS_EDGE_DENSE(LPR_, DET_)                                                                                  \
-    hipLaunchKernelGGL((edge_pool_bwd_dense_kernel<LPR_, DET_>), dim3(dgrid), dim3(256), 0, st, b, n, m, s, c, Q, Ctr, q, t, \
-                       DET_ ? sorted : order, start, dQ, sp)
-        if (det) {
-            pcops_note_plan(11, 2, 0, 0, 0);
-            hipLaunchKernelGGL(edge_pool_bwd_sparse_kernel<true>, dim3(b * (c / kEdgeSlice)), dim3(1024), 0, st, n, m, s, c,
-                               gpool, ysel, SQ, Ctr, arg, idx, scale, shift, p, q, t, dCtr, dQ);
-            switch (lpr) {
-                case 8: PCOPS_EDGE_DENSE(8, true); break;
-                case 16: PCOPS_EDGE_DENSE(16, true); break;
-                case 32: PCOPS_EDGE_DENSE(32, true); break;
-                default: PCOPS_EDGE_DENSE(64, true); break;
-            }
+    CsrLists l;
+    if (const int rc = csr_build(b, n, m, s, m * s, idx, workspace, nullptr, nullptr, pl.mode == 2, st, &l)) return rc;
+    const int lpr = (pl.lpr == 8 || pl.lpr == 16 || pl.lpr == 32) ? pl.lpr : 64;
+    if (pl.mode == 0) {
+        pcops_note_plan(11, 0, 0, 0, 0);
+        const long long total = G * c;
+        const unsigned grid = cdiv(total, 256) < 16384u ? cdiv(total, 256) : 16384u;
+        hipLaunchKernelGGL(edge_pool_bwd_ctr_kernel, dim3(grid), dim3(256), 0, st, total, n, m, s, c, gpool, ysel, SQ, Ctr,
+                           arg, idx, scale, shift, p, q, t, dCtr, dQ);
+        return pcops_dispatch<8, 16, 32, 64>(lpr, PCOPS_ERR_UNSUPPORTED, [&](auto LPR) {
+            hipLaunchKernelGGL(edge_pool_bwd_q_kernel<decltype(LPR)::value>, dim3(2 * kCsrGrid), dim3(256), 0, st, b, n, m, s, c,
+                               Q, Ctr, q, t, l.order, dQ);
             return pcops_launch_status();
-        }
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(edge_pool_bwd_sparse_kernel<false>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-            return PCOPS_ERR_LAUNCH;
-        pcops_note_plan(11, 1, 0, 0, 0);
-        hipLaunchKernelGGL(edge_pool_bwd_sparse_kernel<false>, dim3(b * (c / kEdgeSlice)), dim3(1024), slice_lds, st, n, m, s, c,
-                           gpool, ysel, SQ, Ctr, arg, idx, scale, shift, p, q, t, dCtr, dQ);
-        switch (lpr) {
-            case 8: PCOPS_EDGE_DENSE(8, false); break;
-            case 16: PCOPS_EDGE_DENSE(16, false); break;
-            case 32: PCOPS_EDGE_DENSE(32, false); break;
-            default: PCOPS_EDGE_DENSE(64, false); break;
-        }
-#undef PCOPS_EDGE_DENSE
+        });
+    }
+    const EdgeSparse sp = {gpool, ysel, scale, shift, p, arg};
+    if (pl.mode == 2) {
+        hipLaunchKernelGGL(edge_pool_bwd_sparse_kernel<true>, sgrid, dim3(1024), 0, st, n, m, s, c, gpool, ysel, SQ, Ctr, arg,
+                           idx, scale, shift, p, q, t, dCtr, dQ);
+    } else if (const int rc = pcops_launch_lds(edge_pool_bwd_sparse_kernel<false>, sgrid, dim3(1024), pl.slice_lds, 160 * 1024,
+                                               st, n, m, s, c, gpool, ysel, SQ, Ctr, arg, idx, scale, shift, p, q, t, dCtr, dQ)) {
+        return rc;
+    }
+    pcops_note_plan(11, pl.mode, 0, 0, 0);
+    return pcops_dispatch<8, 16, 32, 64>(lpr, PCOPS_ERR_UNSUPPORTED, [&](auto LPR) {
+        constexpr int L = decltype(LPR)::value;
+        auto kern = pl.mode == 2 ? edge_pool_bwd_dense_kernel<L, true> : edge_pool_bwd_dense_kernel<L, false>;
+        hipLaunchKernelGGL(kern, dim3(2048), dim3(256), 0, st, b, n, m, s, c, Q, Ctr, q, t, pl.mode == 2 ? l.sorted : l.order,
+                           l.start, dQ, sp);
         return pcops_launch_status();
-    }
-    const long long total = G * c;
-    const unsigned grid = cdiv(total, 256) < 16384u ? cdiv(total, 256) : 16384u;
-    pcops_note_plan(11, 0, 0, 0, 0);
-    hipLaunchKernelGGL(edge_pool_bwd_ctr_kernel, dim3(grid), dim3(256), 0, st, total, n, m, s, c, gpool, ysel, SQ, Ctr,
-                       arg, idx, scale, shift, p, q, t, dCtr, dQ);
-    switch (lpr) {
-        case 8: hipLaunchKernelGGL(edge_pool_bwd_q_kernel<8>, dim3(2 * kCsrGrid), dim3(256), 0, st, b, n, m, s, c, Q, Ctr, q, t, order, dQ); break;
-        case 16: hipLaunchKernelGGL(edge_pool_bwd_q_kernel<16>, dim3(2 * kCsrGrid), dim3(256), 0, st, b, n, m, s, c, Q, Ctr, q, t, order, dQ); break;
-        case 32: hipLaunchKernelGGL(edge_pool_bwd_q_kernel<32>, dim3(2 * kCsrGrid), dim3(256), 0, st, b, n, m, s, c, Q, Ctr, q, t, order, dQ); break;
-        default: hipLaunchKernelGGL(edge_pool_bwd_q_kernel<64>, dim3(2 * kCsrGrid), dim3(256), 0, st, b, n, m, s, c, Q, Ctr, q, t, order, dQ); break;
-    }
-    return pcops_launch_status();
+    });
 }
 
 // ---- the [Q | Ctr] forms (round 5): Q and Ctr are the column halves of ONE (b, n, 2 c) product of the layer's input
@@ -2497,13 +2484,9 @@ int pcops_edge_pool_bwd_ld(int b, int n, int m, int s, int c, const float *Q, in
     PCOPS_REQUIRE_PTR(q); PCOPS_REQUIRE_PTR(t); PCOPS_REQUIRE_PTR(dQ); PCOPS_REQUIRE_PTR(dCtr); PCOPS_REQUIRE_PTR(workspace);
     if (!edge_ld_shape_ok(b, n, m, s, c) || (long long)b * n * ldq * 4 >= (1ll << 32)) return PCOPS_ERR_UNSUPPORTED;
     hipStream_t st = as_stream(stream);
-    if (ec_bwd_fused_ok(n, m, s, c)) {
-        pcops_note_plan(11, 4, 0, 0, 1);
-        int rc0 = ec_csr_build(b, n, m, s, idx, workspace, st);
-        if (rc0) return rc0;
-        return ec_bwd_fused(b, n, m, s, c, Q, ldq, Ctr, ldc, gpool, ysel, SQ, arg, scale, shift, p, q, t, workspace, dQ, lddq,
-                            dCtr, lddc, st);
-    }
+    if (ec_bwd_fused_ok(n, m, s, c))
+        return edge_bwd_fused(b, n, m, s, c, Q, ldq, Ctr, ldc, idx, gpool, ysel, SQ, arg, scale, shift, p, q, t, dQ, lddq, dCtr,
+                              lddc, workspace, true, st);
     pcops_note_plan(11, 3, 0, 0, 1);
     int rc = ec_sparse(b, n, m, s, c, gpool, ysel, SQ, Ctr, ldc, arg, idx, scale, shift, p, q, t, dCtr, lddc, dQ, lddq, st);
     if (rc) return rc;
@@ -2528,13 +2511,7 @@ int pcops_sa_scatter_bwd_ld(int b, int n, int m, int s, int c, const float *G, c
     PCOPS_REQUIRE_PTR(G); PCOPS_REQUIRE_PTR(p); PCOPS_REQUIRE_PTR(q); PCOPS_REQUIRE_PTR(t); PCOPS_REQUIRE_PTR(idx);
     PCOPS_REQUIRE_PTR(Q); PCOPS_REQUIRE_PTR(Ctr); PCOPS_REQUIRE_PTR(dQ); PCOPS_REQUIRE_PTR(dCtr); PCOPS_REQUIRE_PTR(workspace);
     if (!edge_ld_shape_ok(b, n, m, s, c) || (long long)b * n * ldq * 4 >= (1ll << 32)) return PCOPS_ERR_UNSUPPORTED;
-    hipStream_t st = as_stream(stream);
-    pcops_note_plan(13, 0, 0, 0, 1);
-    int rc = ec_csr_build(b, n, m, s, idx, workspace, st);
-    if (rc) return rc;
-    rc = ec_tnet_ctr(b, n, m, s, c, Q, ldq, Ctr, ldc, G, idx, p, q, t, dCtr, lddc, st);
-    if (rc) return rc;
-    return ec_walk(b, n, m, s, c, Q, ldq, Ctr, ldc, G, p, q, t, workspace, dQ, lddq, st);
+    return scatter_qctr(b, n, m, s, c, G, p, q, t, idx, Q, ldq, Ctr, ldc, dQ, lddq, dCtr, lddc, workspace, true, as_stream(stream));
 }
 
 // ---- first layer of a stack over whole clouds in their own order: Y = Q + Ctr[cloud]  (cloud_bias_*_kernel above)
@@ -2548,7 +2525,7 @@ int pcops_cloud_bias_fwd(long long rows, int rows_per_group, int c, const float 
     PCOPS_REQUIRE_PTR(Q); PCOPS_REQUIRE_PTR(Ctr); PCOPS_REQUIRE_PTR(Y);
     if (!pcops_cloud_bias_supported(rows, rows_per_group, c)) return PCOPS_ERR_UNSUPPORTED;
     if ((reinterpret_cast<uintptr_t>(Q) | reinterpret_cast<uintptr_t>(Ctr) | reinterpret_cast<uintptr_t>(Y)) & 15) return PCOPS_ERR_UNSUPPORTED;
-    static const bool nt_on = [] { const char *e = getenv("PCOPS_NT_STORE"); return !(e && e[0] == '0'); }();   // kernel A/B only
+    static const bool nt_on = env_switch("PCOPS_NT_STORE", true);   // kernel A/B only
     const int rl = 256 / (c / 4);
     hipLaunchKernelGGL(cloud_bias_fwd_kernel, dim3(pcops_cloud_bias_rows(rows)), dim3(256), (size_t)rl * 2 * c * sizeof(float),
                        as_stream(stream), rows, rows_per_group, c, Q, Ctr, Y, stats_partial, stats_partial ? stat_pivot : nullptr,

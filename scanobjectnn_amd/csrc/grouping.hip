@@ -512,12 +512,8 @@ extern "C" int pcops_selection_sort(int b, int n, int m, int k, const float *dis
         int waves = (int)(65536 / ((size_t)8 * n));
         waves = waves < 1 ? 1 : (waves > 4 ? 4 : waves);
         const size_t lds = (size_t)waves * 8 * n;
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(selection_sort_wave_kernel<false>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024) != hipSuccess)
-            return PCOPS_ERR_LAUNCH;
-        hipLaunchKernelGGL(selection_sort_wave_kernel<false>, dim3(cdiv(rows, waves)), dim3(256), lds, as_stream(stream),
-                           rows, n, k, waves, dist, outi, out, 0, 1, (const float *)nullptr, (const float *)nullptr);
-        return pcops_launch_status();
+        return pcops_launch_lds(selection_sort_wave_kernel<false>, dim3(cdiv(rows, waves)), dim3(256), lds, 64 * 1024,
+                                as_stream(stream), rows, n, k, waves, dist, outi, out, 0, 1, nullptr, nullptr);
     }
     hipLaunchKernelGGL(selection_sort_kernel, dim3(cdiv(rows, 64)), dim3(64), 0, as_stream(stream),
                        rows, n, k, dist, outi, out);
@@ -541,12 +537,8 @@ extern "C" int pcops_knn_point(int b, int n, int c, int m, int k, const float *x
     int waves = (int)(65536 / ((size_t)8 * n));
     waves = waves < 1 ? 1 : (waves > 4 ? 4 : waves);
     const size_t lds = (size_t)waves * 8 * n;
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(selection_sort_wave_kernel<true>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024) != hipSuccess)
-        return PCOPS_ERR_LAUNCH;
-    hipLaunchKernelGGL(selection_sort_wave_kernel<true>, dim3(cdiv(rows, waves)), dim3(256), lds, as_stream(stream), rows, n,
-                       k, waves, (const float *)nullptr, idx, val, c, m, xyz1, xyz2);
-    return pcops_launch_status();
+    return pcops_launch_lds(selection_sort_wave_kernel<true>, dim3(cdiv(rows, waves)), dim3(256), lds, 64 * 1024,
+                            as_stream(stream), rows, n, k, waves, nullptr, idx, val, c, m, xyz1, xyz2);
 }
 
 extern "C" int pcops_knn_point_dist(int b, int n, int c, int m, const float *xyz1, const float *xyz2, float *dist,

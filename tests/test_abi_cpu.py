@@ -37,6 +37,48 @@ def test_binding_table_covers_header():
     assert set(declared_symbols()) == bound
 
 
+def test_binding_signatures_come_from_the_header():
+    """the ctypes tables are parsed from include/pcops.h; literal spot checks, one per mapped type"""
+    from scanobjectnn_amd import _lib
+    I, F, P, LL, U64 = ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_ulonglong
+    sig, plain = _lib.SIGNATURES, _lib.PLAIN
+    assert sig["pcops_mlp_wgrad"] == ([LL, I, I, P, I] + [P] * 9 + [I] + [P] * 5, True)              # long long first
+    assert sig["pcops_query_ball_point"] == ([I, I, I, F, I, P, P, P, P], True)                       # a float
+    assert sig["pcops_mlp_gemm_fwd_rows"] == ([I, I, I, P, I] + [P] * 8, True)                        # pcops_rows_t * last
+    assert sig["pcops_small_gemm_pair"] == ([P], True)                                                # a struct pointer only
+    assert sig["pcops_adam_step"] == ([LL, P, P, P, P, F, F, F, F], True)
+    assert plain["pcops_set_deterministic"] == ([I], None)                                            # void return
+    assert plain["pcops_strerror"] == ([I], ctypes.c_char_p)                                          # char * return
+    assert plain["pcops_sa_scatter_workspace_bytes"] == ([I, I, I, I], U64)                           # unsigned long long
+    assert plain["pcops_edge_first_rows"] == ([], I)                                                  # (void)
+    assert plain["pcops_knn_graph_path"] == ([I, I, I, I, P], I)                                      # a plain one with a pointer
+    assert len(sig) + len(plain) == len(declared_symbols())
+
+
+def test_header_parser_refuses_what_it_cannot_map():
+    from scanobjectnn_amd import _lib
+    with pytest.raises(_lib.PcopsError, match="pcops_scaled"):
+        _lib.parse_header("int pcops_ok(int n, pcops_stream_t stream);\nint pcops_scaled(int n, double x);\n")
+    with pytest.raises(_lib.PcopsError, match="pcops_make"):
+        _lib.parse_header("float *pcops_make(int n);")
+
+
+def test_header_parser_ignores_comments_and_typedefs():
+    from scanobjectnn_amd import _lib
+    text = ("#ifdef __cplusplus\nextern \"C\" {\n#endif\n"
+            "typedef void *pcops_stream_t; /* hipStream_t */\n"
+            "typedef struct pcops_rows { void *blocks; int *rows; } pcops_rows_t;\n"
+            "/* int pcops_gone(int n, double x);\n   int pcops_gone_too(void); */\n"
+            "// int pcops_gone_as_well(double x);\n"
+            "int pcops_kept(long long n, const float *x, const pcops_rows_t *rows,\n"
+            "               pcops_stream_t stream);   /* trailing remark (with parentheses) */\n"
+            "unsigned long long pcops_bytes(int n);\n"
+            "#ifdef __cplusplus\n}\n#endif\n")
+    sig, plain = _lib.parse_header(text)
+    assert sig == {"pcops_kept": ([ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p], True)}
+    assert plain == {"pcops_bytes": ([ctypes.c_int], ctypes.c_ulonglong)}
+
+
 def test_argument_validation_without_gpu():
     """status codes come back before any launch: NULL pointers / bad attributes (OP_REQUIRES of the reference)"""
     from scanobjectnn_amd import _lib
