@@ -74,6 +74,13 @@ def test_wgrad_workspace_is_a_deterministic_split(lib):
         per_split = (k * c * 5 * o + o) * 4
         assert nbytes % per_split == 0 and 0 <= nbytes // per_split <= 16
     assert lib.pcops_spider_conv_wgrad_workspace_bytes(16, 1024, 300, 20, 5, 64) == 0     # unsupported shape
+    # the shapes tests/test_spider_paths_gpu.py reaches the split branches with (b, n, k, c, o -> splits): a change of the
+    # split rule shows here as a diff, not as a branch that silently stops being run
+    for (b, n, k, c, o), splits in (((1, 40, 5, 3, 16), 1), ((2, 64, 1, 16, 64), 2), ((3, 65, 7, 17, 48), 4),
+                                    ((2, 300, 20, 40, 80), 9), ((1, 130, 20, 256, 256), 1), ((2, 520, 4, 3, 16), 16),
+                                    ((1, 70, 64, 5, 32), 2), ((1, 96, 3, 256, 512), 2)):
+        nbytes = lib.pcops_spider_conv_wgrad_workspace_bytes(b, n, c, k, 5, o)
+        assert nbytes == (0 if splits == 1 else splits * (k * c * 5 * o + o) * 4), (b, n, k, c, o)
 
 
 def test_layer_outside_the_kernel_ranges_raises_before_any_launch():
