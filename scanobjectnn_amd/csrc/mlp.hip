@@ -25,9 +25,17 @@
 // of 32 staged through LDS with 16-byte reads; the A fragment uses the "label permutation" trick: a
 // lane reads 4 consecutive k of its row with ONE ds_read_b128 and feeds them to 4 MFMAs whose k labels
 // are matched on the B side, so no transpose is ever needed.
+//
+// Host side: every launcher plans once and launches once.  A plan struct (WsPlan from ws_plan, WgradPlan from wgrad_choose,
+// BwdFusedPlan from bwd_fused_plan) holds the whole decision -- kernel family, tile, grid, LDS bytes, the resolved template
+// modes; the launcher notes the variant FROM the plan (pcops_last_launch_plan) and dispatches FROM the plan, run-time values
+// turned into template arguments by pcops_dispatch and the LDS ceiling raised by pcops_launch_lds (common.h).  A dispatch
+// names only the instantiations a build part emits today: a combination nobody launches is `if constexpr`-ed away, never
+// compiled.  The shape queries of the C ABI (pcops_mlp_wgrad_splits, the *_supported calls) ask the same planners.
 #include <stdlib.h>
 
 #include "common.h"
+#include <initializer_list>
 #include <type_traits>
 
 // ---- build parts.  This file is compiled SEVEN times (Makefile: -DPCOPS_MLP_PART=0..6, in parallel): every part parses the
@@ -1668,75 +1676,53 @@ static bool nt_stores_enabled() {
 }
 static int nt_for_bytes(long long bytes) { return (nt_stores_enabled() && bytes >= (256ll << 20)) ? 1 : 0; }
 
+// gemm_ws_kernel's VAR for a launch: bit 0 the fused pooling epilogue (forward only), bit 1 streamed weights (the A_XYZ operand
+// has no such variant: 0), on top of BASE = 0 fp32 pipe, 4 split operands, 12 split operands with pooling groups that are not
+// whole tiles (always pooled).  wp: bit 0 pooled, bit 1 streamed
+template <int AM, int EM>
+constexpr int ws_var(int wp, int base) {
+    if (base == 12) return 13 | (wp & 2);
+    if ((wp & 2) && AM == A_XYZ) return base;
+    return base | ((wp & 1) && EM == E_FWD ? 1 : 0) | (wp & 2);
+}
+
+// one column tile (NT blocks of 32 columns, EH epilogue passes) of the family BASE names
+template <int AM, int EM, int NT, int EH, int BASE>
+static int launch_gemm_ws_tile(GemmArgs &a, const WsPlan &pl, hipStream_t st) {
+    a.nrowgrp = pl.gy;
+    const int P = (a.stats && EM != E_PLAIN && EM != E_PLAINA) ? pcops_mlp_stats_rows(a.M) : 0;
+    const dim3 grid(pl.gy > P ? pl.gy : P, pl.ncb);
+    const int wp = (EM == E_FWD && a.pool_sub > 0 ? 1 : 0) | (pl.wst ? 2 : 0);
+    return pcops_dispatch<0, 1, 2, 3>(wp, PCOPS_ERR_UNSUPPORTED, [&](auto wp_) {
+        constexpr int VAR = ws_var<AM, EM>(decltype(wp_)::value, BASE);
+        return pcops_launch_lds(gemm_ws_kernel<NT, AM, EM, (BASE ? 32 : 64), 8, EH, VAR>, grid, dim3(512), pl.lds,
+                                160 * 1024, st, a);
+    });
+}
+template <int AM, int EM, int BASE>
+static int launch_gemm_ws_family(GemmArgs &a, const WsPlan &pl, hipStream_t st) {
+    if (pl.bn == 128) return launch_gemm_ws_tile<AM, EM, 4, (BASE ? 4 : 2), BASE>(a, pl, st);
+    if (pl.bn == 96) return launch_gemm_ws_tile<AM, EM, 3, 3, BASE>(a, pl, st);
+    return launch_gemm_ws_tile<AM, EM, 2, (BASE ? 2 : 1), BASE>(a, pl, st);
+}
+
 template <int AM, int EM>
 PCOPS_HIDDEN int launch_gemm_ws(GemmArgs &a, const WsPlan &pl, hipStream_t st) {
     a.nt_out = a.Y ? nt_for_bytes((long long)a.M * a.ldy * 4) : 0;
-#define PCOPS_WS_LAUNCH(NT_, EH_)                                                                     \
-    do {                                                                                              \
-        const bool pool_ = EM == E_FWD && a.pool_sub > 0;                                             \
-        auto kern = (pl.wst && pool_) ? gemm_ws_kernel<NT_, AM, EM, 64, 8, EH_, ((AM == A_XYZ || EM != E_FWD) ? 0 : 3)> \
-                    : pl.wst ? gemm_ws_kernel<NT_, AM, EM, 64, 8, EH_, (AM == A_XYZ ? 0 : 2)>            \
-                    : pool_ ? gemm_ws_kernel<NT_, AM, EM, 64, 8, EH_, (EM == E_FWD ? 1 : 0)>              \
-                            : gemm_ws_kernel<NT_, AM, EM, 64, 8, EH_, 0>;                                 \
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern),                                 \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) \
-            return PCOPS_ERR_LAUNCH;                                                                  \
-        a.nrowgrp = pl.gy;                                                                            \
-        const int P_ = (a.stats && EM != E_PLAIN && EM != E_PLAINA) ? pcops_mlp_stats_rows(a.M) : 0;  \
-        hipLaunchKernelGGL(kern, dim3(pl.gy > P_ ? pl.gy : P_, pl.ncb), dim3(512), pl.lds, st, a);    \
-    } while (0)
     pcops_note_pipe(pl.bf3 ? 1 : 0);
     pcops_note_plan(2, pl.bf3 ? 1 : 0, pl.bn, pl.wst ? 1 : 0,
                     (EM == E_FWD && a.pool_s4 > 0) ? 3 : ((EM == E_FWD && a.pool_sub > 0) ? 1 : (AM == A_DYPOOLU ? 1 :
                     (AM == A_DYPOOL ? 2 : (AM == A_DYPOOLB ? 4 : 0)))));
     if constexpr (EM == E_FWD || (EM == E_MASK && is_dy(AM)) || has_add(EM)) {
-    if (pl.bf3) {
-#define PCOPS_WS3_LAUNCH(NT_, EH_)                                                                    \
-    do {                                                                                              \
-        const bool pool_ = EM == E_FWD && a.pool_sub > 0;                                             \
-        auto kern = (pl.wst && pool_) ? gemm_ws_kernel<NT_, AM, EM, 32, 8, EH_, ((AM == A_XYZ || EM != E_FWD) ? 4 : 7)> \
-                    : pl.wst ? gemm_ws_kernel<NT_, AM, EM, 32, 8, EH_, (AM == A_XYZ ? 4 : 6)>            \
-                    : pool_ ? gemm_ws_kernel<NT_, AM, EM, 32, 8, EH_, (EM == E_FWD ? 5 : 4)>              \
-                            : gemm_ws_kernel<NT_, AM, EM, 32, 8, EH_, 4>;                                 \
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern),                                 \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) \
-            return PCOPS_ERR_LAUNCH;                                                                  \
-        a.nrowgrp = pl.gy;                                                                            \
-        const int P_ = (a.stats && EM != E_PLAIN && EM != E_PLAINA) ? pcops_mlp_stats_rows(a.M) : 0;  \
-        hipLaunchKernelGGL(kern, dim3(pl.gy > P_ ? pl.gy : P_, pl.ncb), dim3(512), pl.lds, st, a);    \
-    } while (0)
-        if constexpr ((AM == A_BNRELU || AM == A_PLAIN) && EM == E_FWD) {
-            if (a.pool_s4 > 0) {     // groups that are not whole tiles: their own instantiations (VAR | 8), split operands only
-#define PCOPS_WS3S4_LAUNCH(NT_, EH_)                                                                  \
-    do {                                                                                              \
-        auto kern = pl.wst ? gemm_ws_kernel<NT_, AM, EM, 32, 8, EH_, 15> : gemm_ws_kernel<NT_, AM, EM, 32, 8, EH_, 13>; \
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern),                                 \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) \
-            return PCOPS_ERR_LAUNCH;                                                                  \
-        a.nrowgrp = pl.gy;                                                                            \
-        const int P_ = a.stats ? pcops_mlp_stats_rows(a.M) : 0;                                       \
-        hipLaunchKernelGGL(kern, dim3(pl.gy > P_ ? pl.gy : P_, pl.ncb), dim3(512), pl.lds, st, a);    \
-    } while (0)
-                if (pl.bn == 128) PCOPS_WS3S4_LAUNCH(4, 4);
-                else if (pl.bn == 96) PCOPS_WS3S4_LAUNCH(3, 3);
-                else PCOPS_WS3S4_LAUNCH(2, 2);
-#undef PCOPS_WS3S4_LAUNCH
-                return pcops_launch_status();
+        if (pl.bf3) {
+            if constexpr ((AM == A_BNRELU || AM == A_PLAIN) && EM == E_FWD) {
+                if (a.pool_s4 > 0) return launch_gemm_ws_family<AM, EM, 12>(a, pl, st);
             }
+            return launch_gemm_ws_family<AM, EM, 4>(a, pl, st);
         }
-        if (pl.bn == 128) PCOPS_WS3_LAUNCH(4, 4);
-        else if (pl.bn == 96) PCOPS_WS3_LAUNCH(3, 3);
-        else PCOPS_WS3_LAUNCH(2, 2);
-#undef PCOPS_WS3_LAUNCH
-        return pcops_launch_status();
-    }
     }
     if (a.pool_s4 > 0) return PCOPS_ERR_UNSUPPORTED;      // (only the split-operand kernels carry that epilogue)
-    if (pl.bn == 128) PCOPS_WS_LAUNCH(4, 2);
-    else if (pl.bn == 96) PCOPS_WS_LAUNCH(3, 3);
-    else PCOPS_WS_LAUNCH(2, 1);
-#undef PCOPS_WS_LAUNCH
-    return pcops_launch_status();
+    return launch_gemm_ws_family<AM, EM, 0>(a, pl, st);
 }
 
 // ---- which build part emits which launcher (see PCOPS_MLP_PART at the top): explicit instantiation in the owning part,
@@ -1801,22 +1787,34 @@ static bool ws_enabled() {
     return on;
 }
 
+// the wave-stream launch with A_DYPOOL resolved: compacted rows take A_DYPOOLB, groups of whole tiles A_DYPOOLU
+template <int AM, int EM>
+static int launch_gemm_ws_resolved(GemmArgs &a, const WsPlan &pl, hipStream_t st) {
+    if constexpr (AM == A_DYPOOL) {
+        if (a.blocks) return launch_gemm_ws<A_DYPOOLB, EM>(a, pl, st);
+        if (a.S % 32 == 0) return launch_gemm_ws<A_DYPOOLU, EM>(a, pl, st);
+    }
+    return launch_gemm_ws<AM, EM>(a, pl, st);
+}
+
 // one entry for both variants: the wave-stream kernel when the shape suits it, the tiled kernel otherwise.
 // The partial-statistics buffer always has pcops_mlp_stats_rows(M) rows; rows a kernel does not emit are zeroed.
 template <int AM, int EM>
 static int launch_gemm(GemmArgs &a, hipStream_t st) {
     WsPlan pl;
-    if (ws_enabled() && ws_plan(a, AM, &pl, ws_kind(EM))) {
-        int rc;
-        if (AM == A_DYPOOL && a.blocks) rc = launch_gemm_ws<(AM == A_DYPOOL ? A_DYPOOLB : AM), EM>(a, pl, st);
-        else if (AM == A_DYPOOL && a.S % 32 == 0) rc = launch_gemm_ws<(AM == A_DYPOOL ? A_DYPOOLU : AM), EM>(a, pl, st);
-        else rc = launch_gemm_ws<AM, EM>(a, pl, st);
-        return rc;
-    }
+    if (ws_enabled() && ws_plan(a, AM, &pl, ws_kind(EM))) return launch_gemm_ws_resolved<AM, EM>(a, pl, st);
     if (a.blocks) return PCOPS_ERR_UNSUPPORTED;      // compacted rows: wave-stream kernels only
     pcops_note_pipe(0);                              // the tiled kernel: fp32 MFMA
     pcops_note_plan(1, 0, 0, 0, AM == A_DYPOOL ? 2 : ((EM == E_FWD && a.pool_sub > 0) ? 1 : 0));
     return launch_gemm_rt<AM, EM>(a, st);
+}
+
+// wave-stream kernel or nothing (the xyz-form modes have no tiled fallback)
+template <int AM, int EM>
+static int launch_gemm_ws_only(GemmArgs &a, hipStream_t st) {
+    WsPlan pl;
+    if (!(ws_enabled() && ws_plan(a, AM, &pl, ws_kind(EM)))) return PCOPS_ERR_UNSUPPORTED;
+    return launch_gemm_ws_resolved<AM, EM>(a, pl, st);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -4547,10 +4545,16 @@ static bool gram_full_on() {
     return on;
 }
 
-struct PcWgradPlan {
-    int tk, tn, kblocks, nblocks, groups;
-    bool k96;        // 65..96 input channels: the 96 x 32 consumer layout (wgrad_pc_kernel)
+// ---- plans of the weight-gradient kernels.  A plan's family is also the `path` code pcops_last_launch_plan reports (pcops.h)
+enum WgradFamily { WG_NONE = 0, WG_BF3 = 4, WG_PC = 5, WG_WS = 6, WG_LEGACY = 7 };
+struct WgradPlan {
+    int family;
+    int tk, tn, rs;                  // tile: blocks of K and N per workgroup, rows per stripe
+    bool k96;                        // 65..96 input channels: the 96 x 32 consumer layout (wgrad_pc_kernel, wgrad_bf3_kernel)
+    int bn;                          // columns per tile, as reported
+    int kblocks, nblocks, groups;    // the grid; groups = partial copies the kernel writes (the split count)
     size_t lds;
+    int am, dm;                      // the kernel's template modes: dm resolved from dmode, blocks and S % 32 (wgrad_choose)
 };
 
 static bool wgrad_k96_enabled() {
@@ -4560,62 +4564,6 @@ static bool wgrad_k96_enabled() {
     }();
     return on;
 }
-
-static bool wgrad_pc_plan(long long M, int K, int N, int ldx, const void *X, const void *G, const void *Y,
-                          const void *gpool, const void *argmax, PcWgradPlan *pl, bool narrow = false) {
-    if (M < 8 * 1024) return false;
-    if (K % 4 != 0 || N % 4 != 0 || ldx % 4 != 0) return false;
-    if ((reinterpret_cast<uintptr_t>(X) & 15) || (reinterpret_cast<uintptr_t>(G) & 15) ||
-        (reinterpret_cast<uintptr_t>(Y) & 15) || (reinterpret_cast<uintptr_t>(gpool) & 15) ||
-        (reinterpret_cast<uintptr_t>(argmax) & 3))
-        return false;
-    pl->tk = K <= 64 ? 1 : 2;
-    pl->tn = N <= 64 ? 1 : (N <= 128 ? 2 : 4);
-    if (narrow && pl->tn == 4 && (N + 127) / 128 * 128 < (N + 255) / 256 * 256) pl->tn = 2;   // less padding (N = 320)
-    pl->k96 = K > 64 && K <= 96 && pl->tn == 2 && wgrad_k96_enabled();
-    const int KB = 64 * pl->tk, NB = 64 * pl->tn;
-    pl->kblocks = (K + KB - 1) / KB;
-    pl->nblocks = (N + NB - 1) / NB;
-    // one persistent workgroup per CU over the whole grid; two for the 64x64 tile (its LDS and register footprints
-    // allow it, and one workgroup's stripe barrier then hides under the other's MFMAs; measured slower for 64x128)
-    int groups = (pl->tk * pl->tn == 1 ? 512 : 256) / (pl->kblocks * pl->nblocks);
-    if (groups < 1) groups = 1;
-    const long long maxg = (M + 31) / 32;
-    if (groups > maxg) groups = (int)maxg;
-    if (groups >= 8) groups &= ~7;
-    pl->groups = groups;
-    const int rs = pl->tk * pl->tn <= 2 ? 64 : 32;
-    pl->lds = (size_t)(6 * KB + 5 * NB + 2 * rs * (KB + NB)) * sizeof(float);
-    return pl->lds <= 160 * 1024;
-}
-
-struct Bf3WgradPlan {
-    int kblocks, nblocks, groups;
-    size_t lds;
-};
-
-// split-operand weight gradient (wgrad_bf3_kernel): the large layers wider than 64 on both sides
-static bool wgrad_bf3_plan(long long M, int K, int N, int ldx, const void *X, const void *G, const void *Y,
-                           const void *gpool, const void *argmax, Bf3WgradPlan *pl) {
-    const bool on = pcops_get_option(PCOPS_OPT_WGRAD_SPLIT_BF16) != 0;
-    if (!on || M < 32768 || K <= 64 || N <= 64) return false;
-    if (K % 4 != 0 || N % 4 != 0 || ldx % 4 != 0) return false;
-    if ((reinterpret_cast<uintptr_t>(X) & 15) || (reinterpret_cast<uintptr_t>(G) & 15) ||
-        (reinterpret_cast<uintptr_t>(Y) & 15) || (reinterpret_cast<uintptr_t>(gpool) & 15) ||
-        (reinterpret_cast<uintptr_t>(argmax) & 3))
-        return false;
-    pl->kblocks = (K + 127) / 128;
-    pl->nblocks = (N + 127) / 128;
-    int groups = 256 / (pl->kblocks * pl->nblocks);
-    if (groups < 1) groups = 1;
-    const long long maxg = (M + 31) / 32;
-    if (groups > maxg) groups = (int)maxg;
-    if (groups >= 8) groups &= ~7;
-    pl->groups = groups;
-    pl->lds = (size_t)(6 * 128 + 5 * 128) * sizeof(float) + (size_t)2 * 3 * 256 * 40 * 2;
-    return true;
-}
-
 static bool wgrad_pc_enabled() {
     static const bool on = [] {
         const char *e = getenv("PCOPS_WGRAD_PC");
@@ -4624,33 +4572,90 @@ static bool wgrad_pc_enabled() {
     return on;
 }
 
-struct WsWgradPlan {
-    int tk, tn, rs, kblocks, nblocks, groups;
-    size_t lds;
-};
+// what every plan asks of the operands: widths and row stride in whole float4, 16-byte aligned tensors (NULL passes: the
+// shape queries of the C ABI plan without tensors)
+static bool wgrad_operands_ok(const WgradArgs &a) {
+    if (a.K % 4 != 0 || a.N % 4 != 0 || a.ldx % 4 != 0) return false;
+    return !((reinterpret_cast<uintptr_t>(a.X) | reinterpret_cast<uintptr_t>(a.G) | reinterpret_cast<uintptr_t>(a.Y) |
+              reinterpret_cast<uintptr_t>(a.gpool)) & 15) && !(reinterpret_cast<uintptr_t>(a.argmax) & 3);
+}
+// one persistent workgroup per CU over the whole grid: `want` row groups, at most maxg, whole multiples of 8 from 8 on
+static int clamp_groups(long long want, long long maxg) {
+    if (want < 1) want = 1;
+    if (want > maxg) want = maxg;
+    return (int)(want >= 8 ? want & ~7ll : want);
+}
 
-static bool wgrad_ws_plan(long long M, int K, int N, int ldx, const void *X, const void *G, const void *Y,
-                          const void *gpool, const void *argmax, WsWgradPlan *pl) {
-    if (M < 8 * 1024) return false;
-    if (K % 4 != 0 || N % 4 != 0 || ldx % 4 != 0) return false;
-    if ((reinterpret_cast<uintptr_t>(X) & 15) || (reinterpret_cast<uintptr_t>(G) & 15) ||
-        (reinterpret_cast<uintptr_t>(Y) & 15) || (reinterpret_cast<uintptr_t>(gpool) & 15) ||
-        (reinterpret_cast<uintptr_t>(argmax) & 3))
-        return false;
+// Every planner comes in two halves: *_tile takes the widths alone, fills the tile, the grid's blocks and the LDS bytes and
+// returns the row groups it wants before the clamp to M (pcops_mlp_wgrad_splits sizes the scratch with that); *_plan adds what
+// depends on the rows and the pointers.
+
+// producer/consumer kernel (wgrad_pc_kernel).  narrow: the Gram matrix prefers less padding (N = 320)
+static int wgrad_pc_tile(int K, int N, bool narrow, WgradPlan *pl) {
+    pl->tk = K <= 64 ? 1 : 2;
+    pl->tn = N <= 64 ? 1 : (N <= 128 ? 2 : 4);
+    if (narrow && pl->tn == 4 && (N + 127) / 128 * 128 < (N + 255) / 256 * 256) pl->tn = 2;
+    pl->k96 = K > 64 && K <= 96 && pl->tn == 2 && wgrad_k96_enabled();
+    const int KB = 64 * pl->tk, NB = 64 * pl->tn;
+    pl->bn = NB;
+    pl->kblocks = (K + KB - 1) / KB;
+    pl->nblocks = (N + NB - 1) / NB;
+    pl->rs = pl->tk * pl->tn <= 2 ? 64 : 32;
+    pl->lds = (size_t)(6 * KB + 5 * NB + 2 * pl->rs * (KB + NB)) * sizeof(float);
+    // two workgroups per CU for the 64x64 tile (its LDS and register footprints allow it, and one workgroup's stripe
+    // barrier then hides under the other's MFMAs; measured slower for 64x128)
+    return (pl->tk * pl->tn == 1 ? 512 : 256) / (pl->kblocks * pl->nblocks);
+}
+static bool wgrad_pc_plan(const WgradArgs &a, WgradPlan *pl, bool narrow = false) {
+    if (a.M < 8 * 1024 || !wgrad_operands_ok(a)) return false;
+    pl->groups = clamp_groups(wgrad_pc_tile(a.K, a.N, narrow, pl), (a.M + 31) / 32);
+    return pl->lds <= 160 * 1024;
+}
+
+// split-operand weight gradient (wgrad_bf3_kernel): the large layers wider than 64 on both sides
+static int wgrad_bf3_tile(int K, int N, WgradPlan *pl) {
+    pl->tk = pl->tn = 2; pl->rs = 32; pl->bn = 128;
+    pl->kblocks = (K + 127) / 128;
+    pl->nblocks = (N + 127) / 128;
+    pl->lds = (size_t)(6 * 128 + 5 * 128) * sizeof(float) + (size_t)2 * 3 * 256 * 40 * 2;
+    return 256 / (pl->kblocks * pl->nblocks);
+}
+static bool wgrad_bf3_plan(const WgradArgs &a, WgradPlan *pl) {
+    const bool on = pcops_get_option(PCOPS_OPT_WGRAD_SPLIT_BF16) != 0;
+    if (!on || a.M < 32768 || a.K <= 64 || a.N <= 64 || !wgrad_operands_ok(a)) return false;
+    pl->groups = clamp_groups(wgrad_bf3_tile(a.K, a.N, pl), (a.M + 31) / 32);
+    // 65 .. 96 input channels behind a BN + ReLU (MSG's 96 -> 128): the 96 x 32 consumer layout (PCOPS_WGRAD_BF3_K96=0: off)
+    static const bool k96_on = [] { const char *e = getenv("PCOPS_WGRAD_BF3_K96"); return !(e && e[0] == '0'); }();
+    pl->k96 = k96_on && a.K <= 96 && a.amode == A_BNRELU;
+    return true;
+}
+
+// single-role kernel (wgrad_ws_kernel)
+static int wgrad_ws_tile(int K, int N, WgradPlan *pl) {
     if (K <= 64 && N <= 64) { pl->tk = 2; pl->tn = 2; pl->rs = 32; }
     else if (K <= 64) { pl->tk = 2; pl->tn = 4; pl->rs = 32; }
     else { pl->tk = 4; pl->tn = 4; pl->rs = 16; }
+    pl->k96 = false;
     const int KB = 32 * pl->tk, NB = 32 * pl->tn;
+    pl->bn = NB;
     pl->kblocks = (K + KB - 1) / KB;
     pl->nblocks = (N + NB - 1) / NB;
-    int groups = 256 / (pl->kblocks * pl->nblocks);    // one persistent workgroup per CU over the whole grid
-    if (groups < 1) groups = 1;
-    const long long maxg = ((M + pl->rs - 1) / pl->rs + 3) / 4;
-    if (groups > maxg) groups = (int)maxg;
-    if (groups >= 8) groups &= ~7;
-    pl->groups = groups;
     pl->lds = (size_t)(2 * KB + 5 * NB + 4 * pl->rs * (KB + NB) + KB * NB + NB) * sizeof(float);
+    return 256 / (pl->kblocks * pl->nblocks);
+}
+static bool wgrad_ws_plan(const WgradArgs &a, WgradPlan *pl) {
+    if (a.M < 8 * 1024 || !wgrad_operands_ok(a)) return false;
+    const int want = wgrad_ws_tile(a.K, a.N, pl);
+    pl->groups = clamp_groups(want, ((a.M + pl->rs - 1) / pl->rs + 3) / 4);
     return pl->lds <= 160 * 1024;
+}
+
+// the producer/consumer plan of a shape alone (aligned operands assumed): what the *_supported queries of the C ABI ask
+static bool wgrad_pc_shape_ok(long long M, int K, int N, int ldx, bool narrow = false) {
+    WgradArgs a = {};
+    a.M = M; a.K = K; a.N = N; a.ldx = ldx;
+    WgradPlan pl;
+    return wgrad_pc_plan(a, &pl, narrow);
 }
 
 namespace {
@@ -5494,18 +5499,6 @@ __global__ __launch_bounds__(256) void small_gemm_pair_kernel(SgProblem p0, SgPr
 #endif  // PCOPS_PART(0)
 
 // ============================================================================ C ABI
-// wave-stream kernel or nothing (the xyz-form modes have no tiled fallback)
-template <int AM, int EM>
-static int launch_gemm_ws_only(GemmArgs &a, hipStream_t st) {
-    WsPlan pl;
-    if (!(ws_enabled() && ws_plan(a, AM, &pl, ws_kind(EM)))) return PCOPS_ERR_UNSUPPORTED;
-    int rc;
-    if (AM == A_DYPOOL && a.blocks) rc = launch_gemm_ws<(AM == A_DYPOOL ? A_DYPOOLB : AM), EM>(a, pl, st);
-    else if (AM == A_DYPOOL && a.S % 32 == 0) rc = launch_gemm_ws<(AM == A_DYPOOL ? A_DYPOOLU : AM), EM>(a, pl, st);
-    else rc = launch_gemm_ws<AM, EM>(a, pl, st);
-    return rc;
-}
-
 // ---- launchers of the weight-gradient, one-pass-backward and Gram kernels: build parts 4 and 5 (PCOPS_MLP_PART)
 PCOPS_HIDDEN int wgrad_impl(WgradArgs &a, float *partial, float *dW, float *db, hipStream_t st);
 PCOPS_HIDDEN int bwd_fused_launch(WgradArgs &a, bool xyz, int groups, float *partial, float *dW, float *db, hipStream_t st,
@@ -5525,140 +5518,130 @@ static int wgrad_legacy_splits(long long M, int K, int N) {
     return (int)((M + rows - 1) / rows);
 }
 
-#if PCOPS_PART(4)
-/* dW[K][N] = A^T dY, db[N] = 1^T dY;  A = X (a_scale==NULL) or relu(X*a_scale + a_shift);
- * dY as in pcops_mlp_gemm_dgrad.  partial: float [splits][K][N] + [splits][N] scratch (caller). */
-int wgrad_impl(WgradArgs &a, float *partial, float *dW, float *db, hipStream_t st) {
-    const long long M = a.M;
-    const int K = a.K, N = a.N, ldx = a.ldx;
-    const float *X = a.X, *G = a.G, *Y = a.Y, *gpool = a.gpool;
-    const unsigned char *argmax = a.argmax;
-    int splits;
-    WsWgradPlan pl;
-    PcWgradPlan pc;
-    // producer/consumer kernel for the pooled forms and the widest tile; the single-role kernel (256 accumulator
-    // registers per wave) is ahead on the narrow materialised-G shapes
-    if (a.blocks && !(ws_enabled() && wgrad_pc_enabled() && wgrad_pc_plan(M, K, N, ldx, X, G, Y, gpool, argmax, &pc)))
-        return PCOPS_ERR_UNSUPPORTED;            // compacted rows: producer/consumer kernel only
-    const bool self = a.dmode == A_SELFD;
-    if (self && !(ws_enabled() && wgrad_pc_enabled() && wgrad_pc_plan(M, K, N, ldx, X, G, Y, gpool, argmax, &pc, true)))
-        return PCOPS_ERR_UNSUPPORTED;            // Gram matrix: producer/consumer kernel only
-    Bf3WgradPlan b3;
-    pcops_note_pipe(0);
-    if (ws_enabled() && wgrad_pc_enabled() && !self && a.amode != A_XYZ &&
-        wgrad_bf3_plan(M, K, N, ldx, X, G, Y, gpool, argmax, &b3)) {
-        pcops_note_pipe(1);
-        pcops_note_plan(4, 1, 128, 0, a.blocks ? 4 : (a.dmode == A_DY ? 0 : (a.S % 32 == 0 ? 1 : 2)));
-        splits = b3.groups;
-        a.part = partial; a.dbpart = partial + (long long)splits * K * N;
-        const dim3 grid(b3.groups, b3.kblocks, b3.nblocks);
-        // 65 .. 96 input channels behind a BN + ReLU (MSG's 96 -> 128): the 96 x 32 consumer layout (PCOPS_WGRAD_BF3_K96=0: off)
-        static const bool k96_on = [] { const char *e = getenv("PCOPS_WGRAD_BF3_K96"); return !(e && e[0] == '0'); }();
-        const bool k96 = k96_on && K <= 96 && K % 4 == 0;
-#define PCOPS_B3_LAUNCH(AM_, DM_)                                                                          \
-    do {                                                                                                   \
-        auto kern = (k96 && AM_ == A_BNRELU) ? wgrad_bf3_kernel<AM_, DM_, AM_ == A_BNRELU> : wgrad_bf3_kernel<AM_, DM_>;   \
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern),                                      \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)     \
-            return PCOPS_ERR_LAUNCH;                                                                       \
-        hipLaunchKernelGGL(kern, grid, dim3(512), b3.lds, st, a);                                          \
-    } while (0)
-        if (a.amode == A_BNRELU && a.dmode == A_DY && a.blocks) PCOPS_B3_LAUNCH(A_BNRELU, A_DYW);
-        else if (a.amode == A_PLAIN && a.dmode == A_DY && a.blocks) PCOPS_B3_LAUNCH(A_PLAIN, A_DYW);
-        else if (a.amode == A_BNRELU && a.dmode != A_DY && a.blocks) PCOPS_B3_LAUNCH(A_BNRELU, A_DYPOOLB);
-        else if (a.amode == A_PLAIN && a.dmode != A_DY && a.blocks) PCOPS_B3_LAUNCH(A_PLAIN, A_DYPOOLB);
-        else if (a.amode == A_BNRELU && a.dmode == A_DY) PCOPS_B3_LAUNCH(A_BNRELU, A_DY);
-        else if (a.amode == A_BNRELU && a.S % 32 == 0) PCOPS_B3_LAUNCH(A_BNRELU, A_DYPOOLU);
-        else if (a.amode == A_BNRELU) PCOPS_B3_LAUNCH(A_BNRELU, A_DYPOOL);
-        else if (a.dmode == A_DY) PCOPS_B3_LAUNCH(A_PLAIN, A_DY);
-        else if (a.S % 32 == 0) PCOPS_B3_LAUNCH(A_PLAIN, A_DYPOOLU);
-        else PCOPS_B3_LAUNCH(A_PLAIN, A_DYPOOL);
-#undef PCOPS_B3_LAUNCH
-    } else if (ws_enabled() && wgrad_pc_enabled() && wgrad_pc_plan(M, K, N, ldx, X, G, Y, gpool, argmax, &pc, self) &&
-        (gpool || pc.tn == 4 || a.amode == A_XYZ || a.blocks || self ||
-         !wgrad_ws_plan(M, K, N, ldx, X, G, Y, gpool, argmax, &pl))) {
-        splits = pc.groups;
-        a.part = partial; a.dbpart = partial + (long long)splits * K * N;
-        const dim3 grid(pc.groups, pc.kblocks, pc.nblocks);
-        pcops_note_plan(5, 0, 64 * pc.tn, 0, a.blocks ? 4 : (a.dmode == A_DY || self ? 0 : (a.S % 32 == 0 ? 1 : 2)));
-#define PCOPS_PC_LAUNCH(TK_, TN_, AM_, DM_)                                                                \
-    do {                                                                                                   \
-        auto kern = wgrad_pc_kernel<TK_, TN_, AM_, DM_, K96_>;                                                \
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern),                                      \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)     \
-            return PCOPS_ERR_LAUNCH;                                                                       \
-        hipLaunchKernelGGL(kern, grid, dim3(512), pc.lds, st, a);                                          \
-    } while (0)
-#define PCOPS_PC_MODES(TK_, TN_, K96V_)                                                                    \
-    do {                                                                                                   \
-        constexpr bool K96_ = K96V_;                                                                       \
-        if (a.dmode == A_SELFD && a.amode == A_PLAIN) PCOPS_PC_LAUNCH(TK_, TN_, A_PLAIN, A_SELFD);         \
-        else if (a.dmode == A_SELFD) PCOPS_PC_LAUNCH(TK_, TN_, A_BNRELU, A_SELFD);                         \
-        else if (a.amode == A_XYZ && a.dmode == A_DY && a.blocks) PCOPS_PC_LAUNCH(TK_, TN_, A_XYZ, A_DYW); \
-        else if (a.amode == A_BNRELU && a.dmode == A_DY && a.blocks) PCOPS_PC_LAUNCH(TK_, TN_, A_BNRELU, A_DYW); \
-        else if (a.amode == A_PLAIN && a.dmode == A_DY && a.blocks) PCOPS_PC_LAUNCH(TK_, TN_, A_PLAIN, A_DYW);   \
-        else if (a.amode == A_XYZ && a.dmode == A_DY) PCOPS_PC_LAUNCH(TK_, TN_, A_XYZ, A_DY);              \
-        else if (a.amode == A_XYZ && a.blocks) PCOPS_PC_LAUNCH(TK_, TN_, A_XYZ, A_DYPOOLB);                \
-        else if (a.amode == A_BNRELU && a.dmode != A_DY && a.blocks) PCOPS_PC_LAUNCH(TK_, TN_, A_BNRELU, A_DYPOOLB); \
-        else if (a.amode == A_PLAIN && a.dmode != A_DY && a.blocks) PCOPS_PC_LAUNCH(TK_, TN_, A_PLAIN, A_DYPOOLB);   \
-        else if (a.amode == A_XYZ && a.S % 32 == 0) PCOPS_PC_LAUNCH(TK_, TN_, A_XYZ, A_DYPOOLU);           \
-        else if (a.amode == A_XYZ) PCOPS_PC_LAUNCH(TK_, TN_, A_XYZ, A_DYPOOL);                             \
-        else if (a.amode == A_BNRELU && a.dmode == A_DY) PCOPS_PC_LAUNCH(TK_, TN_, A_BNRELU, A_DY);        \
-        else if (a.amode == A_BNRELU && a.S % 32 == 0) PCOPS_PC_LAUNCH(TK_, TN_, A_BNRELU, A_DYPOOLU);     \
-        else if (a.amode == A_BNRELU) PCOPS_PC_LAUNCH(TK_, TN_, A_BNRELU, A_DYPOOL);                       \
-        else if (a.dmode == A_DY) PCOPS_PC_LAUNCH(TK_, TN_, A_PLAIN, A_DY);                                \
-        else if (a.S % 32 == 0) PCOPS_PC_LAUNCH(TK_, TN_, A_PLAIN, A_DYPOOLU);                             \
-        else PCOPS_PC_LAUNCH(TK_, TN_, A_PLAIN, A_DYPOOL);                                                 \
-    } while (0)
-        if (pc.tk == 1 && pc.tn == 1) PCOPS_PC_MODES(1, 1, false);
-        else if (pc.tk == 1 && pc.tn == 2) PCOPS_PC_MODES(1, 2, false);
-        else if (pc.tk == 1) PCOPS_PC_MODES(1, 4, false);
-        else if (pc.tn == 1) PCOPS_PC_MODES(2, 1, false);
-        else if (pc.tn == 2 && pc.k96) PCOPS_PC_MODES(2, 2, true);
-        else if (pc.tn == 2) PCOPS_PC_MODES(2, 2, false);
-        else PCOPS_PC_MODES(2, 4, false);
-#undef PCOPS_PC_MODES
-#undef PCOPS_PC_LAUNCH
-    } else if (a.amode == A_XYZ) {
-        return PCOPS_ERR_UNSUPPORTED;
-    } else if (ws_enabled() && wgrad_ws_plan(M, K, N, ldx, X, G, Y, gpool, argmax, &pl)) {
-        splits = pl.groups;
-        a.part = partial; a.dbpart = partial + (long long)splits * K * N;
-        const dim3 grid(pl.groups, pl.kblocks, pl.nblocks);
-        pcops_note_plan(6, 0, 32 * pl.tn, 0, a.dmode == A_DY ? 0 : 2);
-#define PCOPS_WG_LAUNCH(TK_, TN_, RS_, AM_, DM_)                                                           \
-    do {                                                                                                   \
-        auto kern = wgrad_ws_kernel<TK_, TN_, RS_, AM_, DM_>;                                              \
-        static hipError_t once = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),                 \
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-        (void)once;                                                                                        \
-        hipLaunchKernelGGL(kern, grid, dim3(256), pl.lds, st, a);                                          \
-    } while (0)
-#define PCOPS_WG_MODES(TK_, TN_, RS_)                                                                      \
-    do {                                                                                                   \
-        if (a.amode == A_BNRELU && a.dmode == A_DY) PCOPS_WG_LAUNCH(TK_, TN_, RS_, A_BNRELU, A_DY);        \
-        else if (a.amode == A_BNRELU) PCOPS_WG_LAUNCH(TK_, TN_, RS_, A_BNRELU, A_DYPOOL);                  \
-        else if (a.dmode == A_DY) PCOPS_WG_LAUNCH(TK_, TN_, RS_, A_PLAIN, A_DY);                           \
-        else PCOPS_WG_LAUNCH(TK_, TN_, RS_, A_PLAIN, A_DYPOOL);                                            \
-    } while (0)
-        if (pl.tk == 2 && pl.tn == 2) PCOPS_WG_MODES(2, 2, 32);
-        else if (pl.tk == 2) PCOPS_WG_MODES(2, 4, 32);
-        else PCOPS_WG_MODES(4, 4, 16);
-#undef PCOPS_WG_MODES
-#undef PCOPS_WG_LAUNCH
+// the dY-side template mode of a weight-gradient or one-pass-backward kernel, resolved once: compacted rows take the block
+// forms (A_DYW, A_DYPOOLB), pooled groups of whole 32-row tiles A_DYPOOLU
+static int resolve_dmode(const WgradArgs &a, bool pooled) {
+    if (a.dmode == A_SELFD) return A_SELFD;
+    if (!pooled) return a.blocks ? A_DYW : A_DY;
+    return a.blocks ? A_DYPOOLB : (a.S % 32 == 0 ? A_DYPOOLU : A_DYPOOL);
+}
+// ... and the `pool` field pcops_last_launch_plan reports for it (pcops.h)
+static int pool_code(int dm) {
+    return (dm == A_DYW || dm == A_DYPOOLB) ? 4 : (dm == A_DYPOOLU ? 1 : (dm == A_DYPOOL ? 2 : 0));
+}
+
+// Which kernel takes a weight gradient, decided ONCE and without side effects: wgrad_impl notes and launches what this
+// returns.  The producer/consumer kernel for the pooled forms and the widest tile; the single-role kernel (256 accumulator
+// registers per wave) is ahead on the narrow materialised-G shapes; compacted rows, the Gram matrix and the xyz operand have
+// the producer/consumer kernel or nothing.
+static WgradPlan wgrad_choose(const WgradArgs &a) {
+    const bool self = a.dmode == A_SELFD, xyz = a.amode == A_XYZ;
+    const bool pc_on = ws_enabled() && wgrad_pc_enabled();
+    WgradPlan pl = {}, pc = {}, ws = {};
+    pl.family = WG_NONE;
+    const bool pc_ok = pc_on && wgrad_pc_plan(a, &pc, self);
+    if (pc_on && !self && !xyz && !(a.blocks && !pc_ok) && wgrad_bf3_plan(a, &pl)) {
+        pl.family = WG_BF3;
+    } else if (pc_ok && (a.gpool || pc.tn == 4 || xyz || a.blocks || self || !wgrad_ws_plan(a, &ws))) {
+        pl = pc;
+        pl.family = WG_PC;
+    } else if (a.blocks || self || xyz) {
+        return pl;
+    } else if (ws_enabled() && wgrad_ws_plan(a, &ws)) {
+        pl = ws;
+        pl.family = WG_WS;
     } else {
-        splits = wgrad_legacy_splits(M, K, N);
-        pcops_note_plan(7, 0, 128, 0, a.dmode == A_DY ? 0 : 2);
-        a.rows_per_block = (int)((((M + splits - 1) / splits) + 7) / 8 * 8);
-        a.part = partial; a.dbpart = partial + (long long)splits * K * N;
-        hipLaunchKernelGGL((wgrad_kernel<2, 4>), dim3((K + 63) / 64, (N + 127) / 128, splits), dim3(256), 0, st, a);
+        pl.family = WG_LEGACY;
+        pl.bn = 128;
+        pl.kblocks = (a.K + 63) / 64;
+        pl.nblocks = (a.N + 127) / 128;
+        pl.groups = wgrad_legacy_splits(a.M, a.K, a.N);
     }
-    int rc = pcops_launch_status();
+    pl.am = a.amode;
+    pl.dm = resolve_dmode(a, a.dmode != A_DY);
+    // (the single-role and the legacy kernel have one pooled form for every group size)
+    if ((pl.family == WG_WS || pl.family == WG_LEGACY) && pl.dm == A_DYPOOLU) pl.dm = A_DYPOOL;
+    return pl;
+}
+
+#if PCOPS_PART(4)
+// the (operand, dY) mode pairs each family's kernel is built for
+constexpr bool wgrad_has_kernel(int family, int am, int dm) {
+    return family == WG_PC ? !(am == A_XYZ && dm == A_SELFD)
+         : family == WG_BF3 ? (am != A_XYZ && dm != A_SELFD)
+                            : (am != A_XYZ && (dm == A_DY || dm == A_DYPOOL));
+}
+// f(AM, DM) with the plan's modes as integral constants
+template <int FAMILY, typename F>
+static int wgrad_dispatch_modes(const WgradPlan &pl, F &&f) {
+    return pcops_dispatch<A_PLAIN, A_BNRELU, A_XYZ>(pl.am, PCOPS_ERR_UNSUPPORTED, [&](auto am_) {
+        return pcops_dispatch<A_DY, A_DYW, A_DYPOOL, A_DYPOOLU, A_DYPOOLB, A_SELFD>(pl.dm, PCOPS_ERR_UNSUPPORTED, [&](auto dm_) {
+            if constexpr (wgrad_has_kernel(FAMILY, decltype(am_)::value, decltype(dm_)::value)) return f(am_, dm_);
+            else return (int)PCOPS_ERR_UNSUPPORTED;
+        });
+    });
+}
+
+// (the LDS ceiling of the single-role kernels is raised once per instantiation, not per call)
+template <int TK, int TN, int RS, int AM, int DM>
+static int wgrad_ws_launch(const WgradArgs &a, const WgradPlan &pl, hipStream_t st) {
+    auto kern = wgrad_ws_kernel<TK, TN, RS, AM, DM>;
+    static const hipError_t once = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
+                                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)once;
+    hipLaunchKernelGGL(kern, dim3(pl.groups, pl.kblocks, pl.nblocks), dim3(256), pl.lds, st, a);
+    return pcops_launch_status();
+}
+
+static int wgrad_launch(const WgradArgs &a, const WgradPlan &pl, hipStream_t st) {
+    const dim3 grid(pl.groups, pl.kblocks, pl.nblocks);
+    switch (pl.family) {
+    case WG_BF3:
+        return wgrad_dispatch_modes<WG_BF3>(pl, [&](auto am_, auto dm_) {
+            constexpr int AM = decltype(am_)::value, DM = decltype(dm_)::value;
+            if constexpr (AM == A_BNRELU) {
+                if (pl.k96) return pcops_launch_lds(wgrad_bf3_kernel<AM, DM, true>, grid, dim3(512), pl.lds, 160 * 1024, st, a);
+            }
+            return pcops_launch_lds(wgrad_bf3_kernel<AM, DM>, grid, dim3(512), pl.lds, 160 * 1024, st, a);
+        });
+    case WG_PC:      // tiles as 100 tk + 10 tn + k96
+        return pcops_dispatch<110, 120, 140, 210, 220, 221, 240>(100 * pl.tk + 10 * pl.tn + (pl.k96 ? 1 : 0), PCOPS_ERR_UNSUPPORTED, [&](auto t_) {
+            constexpr int T = decltype(t_)::value;
+            return wgrad_dispatch_modes<WG_PC>(pl, [&](auto am_, auto dm_) {
+                return pcops_launch_lds(wgrad_pc_kernel<T / 100, T / 10 % 10, decltype(am_)::value, decltype(dm_)::value, T % 10 != 0>,
+                                        grid, dim3(512), pl.lds, 160 * 1024, st, a);
+            });
+        });
+    case WG_WS:      // tiles as 10 tk + tn; 16-row stripes under the widest
+        return pcops_dispatch<22, 24, 44>(10 * pl.tk + pl.tn, PCOPS_ERR_UNSUPPORTED, [&](auto t_) {
+            constexpr int T = decltype(t_)::value;
+            return wgrad_dispatch_modes<WG_WS>(pl, [&](auto am_, auto dm_) {
+                return wgrad_ws_launch<T / 10, T % 10, (T == 44 ? 16 : 32), decltype(am_)::value, decltype(dm_)::value>(a, pl, st);
+            });
+        });
+    case WG_LEGACY:
+        hipLaunchKernelGGL((wgrad_kernel<2, 4>), dim3(pl.kblocks, pl.nblocks, pl.groups), dim3(256), 0, st, a);
+        return pcops_launch_status();
+    }
+    return PCOPS_ERR_UNSUPPORTED;
+}
+
+/* dW[K][N] = A^T dY, db[N] = 1^T dY;  A = X (a_scale==NULL) or relu(X*a_scale + a_shift);
+ * dY as in pcops_mlp_gemm_dgrad.  partial: float [splits][K][N] + [splits][N] scratch (caller).
+ * One choice (wgrad_choose), its note, its launch, the sum of the partials; a refusal notes and launches nothing. */
+int wgrad_impl(WgradArgs &a, float *partial, float *dW, float *db, hipStream_t st) {
+    const WgradPlan pl = wgrad_choose(a);
+    if (pl.family == WG_NONE) return PCOPS_ERR_UNSUPPORTED;
+    pcops_note_pipe(pl.family == WG_BF3 ? 1 : 0);
+    pcops_note_plan(pl.family, pl.family == WG_BF3 ? 1 : 0, pl.bn, 0, pool_code(pl.dm));
+    const long long L = (long long)a.K * a.N;
+    a.part = partial; a.dbpart = partial + pl.groups * L;
+    if (pl.family == WG_LEGACY) a.rows_per_block = (int)((((a.M + pl.groups - 1) / pl.groups) + 7) / 8 * 8);
+    const int rc = wgrad_launch(a, pl, st);
     if (rc) return rc;
     // dW and db partials are adjacent ([splits][K*N] then [splits][N]): one launch sums both
-    const long long L = (long long)K * N;
-    hipLaunchKernelGGL(sum_partials2_kernel, dim3(cdiv(L, 64) + (db ? cdiv(N, 64) : 0)), dim3(1024), 0, st, splits, L,
-                       partial, dW, (long long)N, a.dbpart, db);
+    hipLaunchKernelGGL(sum_partials2_kernel, dim3(cdiv(L, 64) + (db ? cdiv(a.N, 64) : 0)), dim3(1024), 0, st, pl.groups, L,
+                       partial, dW, (long long)a.N, a.dbpart, db);
     return pcops_launch_status();
 }
 #endif
@@ -5671,17 +5654,79 @@ static bool nsk_on() {
     }();
     return on;
 }
-// (the split-operand dW variant exists for the 128-column tile over read rows only -- see bwd_fused_launch)
-template <int TN, int DM, bool X>
-static auto bwd_fused_dw3_kernel() -> void (*)(WgradArgs) {
-    if constexpr (TN == 2 && !X) return bwd_fused_kernel<TN, DM, X, false, true, false, false, true>;
-    else return nullptr;
+
+struct BwdFusedPlan {
+    int tn;                  // 64-column blocks of the tile
+    bool xyz, side, gw;      // the operand forms (see the entry points)
+    bool dx3, dw3, nsk;      // split-operand dX half / dW half, the column skip
+    int dm;                  // the kernel's dY mode (resolve_dmode; the EdgeConv form has A_DYPOOL for every group size)
+    size_t lds;
+};
+
+// dynamic LDS of bwd_fused_kernel<TN = NB / 64, ..>: the coefficient vectors coefA | coefD, then one of three layouts
+static size_t bwd_fused_lds(int NB, bool xyz, bool side, bool dw3) {
+    const int coef = (xyz ? 6 : 2) * 64 + 3 * NB, extra = side ? 12 : 4;       // (extra floats per stripe row)
+    if (dw3 && side && PCOPS_BF_RM)     // stripes [2][32][64 + extra], pieces T[2][3][64 + NB][32] and row-major R[2][3][32][NB + 8] (bf16)
+        return (size_t)(coef + 2 * 32 * (64 + extra)) * sizeof(float) + (size_t)2 * 3 * (64 + NB) * 32 * 2 +
+               (size_t)2 * 3 * 32 * (NB + 8) * 2;
+    if (dw3)                            // stripes [2][32][64 + NB + extra], pieces T[2][3][64 + NB][40] (bf16; W staged under T[1])
+        return (size_t)(coef + 2 * 32 * (64 + NB + extra)) * sizeof(float) + (size_t)2 * 3 * (64 + NB) * 40 * 2;
+    // fp32 dW half: W staged [NB][64], stripes [2][32][2 * 64 + NB + extra]
+    return (size_t)(coef + NB * 64 + 2 * 32 * (2 * 64 + NB + extra)) * sizeof(float);
 }
+
+static BwdFusedPlan bwd_fused_plan(const WgradArgs &a, bool xyz, bool side) {
+    BwdFusedPlan pl;
+    pl.tn = a.N <= 64 ? 1 : 2;
+    pl.xyz = xyz; pl.side = side;
+    pl.gw = a.gram_part != nullptr;     // Gram form of the weight gradient (pcops_mlp_bwd_fused_gw*): partial also
+                                        // holds [groups][K][K] + [groups][K] behind the dW / db partials
+    const int optv = pcops_get_option(PCOPS_OPT_BWD_FUSED_DX_SPLIT_BF16);
+    pl.dx3 = optv != 0;
+    pl.nsk = nsk_on() && pl.tn == 2 && a.N <= 96;
+    // split-operand dW half (bwd_fused_kernel<.., DW3>; option value 2, the default): on the 128-column tile of layers whose
+    // input is READ.  Measured where it is not built (round 6, profiles/r06_bwd_fused_dw3.txt): the 64-column tile (+7 %: two
+    // waves' worth of matrix work saved, the producers' piece splitting added) and the xyz forms (+9 %: their producers
+    // already rebuild the first layer per row) are slower with it; nor with the Gram form or the column skip (N <= 96).
+    pl.dw3 = optv >= 2 && pl.tn == 2 && !xyz && !pl.gw && !pl.nsk;
+    pl.dm = side ? A_DYPOOL : resolve_dmode(a, a.gpool != nullptr);
+    pl.lds = bwd_fused_lds(64 * pl.tn, xyz, side, pl.dw3);
+    return pl;
+}
+
+// the instantiations that exist, by form; nullptr where a combination is not built (the plan never asks for those)
+template <int TN, int DM>
+static auto bwd_fused_gw_kernel(const BwdFusedPlan &pl) -> void (*)(WgradArgs) {
+    if constexpr (DM == A_DYPOOL) {
+        if (pl.side) return bwd_fused_kernel<TN, A_DYPOOL, false, false, true, true, true>;
+    }
+    if constexpr (TN == 2) {
+        if (pl.nsk) return bwd_fused_kernel<TN, DM, false, true, true, false, true>;
+    }
+    return bwd_fused_kernel<TN, DM, false, false, true, false, true>;
+}
+// (the first EdgeConv layer below: pooled groups of k neighbours, plain rows -- pcops_mlp_bwd_fused_edge checks)
 template <int TN>
-static auto bwd_fused_dw3_side_kernel() -> void (*)(WgradArgs) {
-    if constexpr (TN == 2) return bwd_fused_kernel<TN, A_DYPOOL, false, false, true, true, false, true>;
-    else return nullptr;
+static auto bwd_fused_side_kernel(const BwdFusedPlan &pl) -> void (*)(WgradArgs) {
+    if constexpr (TN == 2) {
+        if (pl.dw3) return bwd_fused_kernel<TN, A_DYPOOL, false, false, true, true, false, true>;
+    }
+    if (pl.dw3) return nullptr;
+    return pl.dx3 ? bwd_fused_kernel<TN, A_DYPOOL, false, false, true, true> : bwd_fused_kernel<TN, A_DYPOOL, false, false, false, true>;
 }
+// (the split-operand dW variant exists for the 128-column tile over read rows only, the column skip for that tile only)
+template <int TN, int DM, bool X>
+static auto bwd_fused_plain_kernel(const BwdFusedPlan &pl) -> void (*)(WgradArgs) {
+    if constexpr (TN == 2 && !X) {
+        if (pl.dw3) return bwd_fused_kernel<TN, DM, X, false, true, false, false, true>;
+    }
+    if (pl.dw3) return nullptr;
+    if constexpr (TN == 2) {
+        if (pl.nsk) return pl.dx3 ? bwd_fused_kernel<TN, DM, X, true, true> : bwd_fused_kernel<TN, DM, X, true>;
+    }
+    return pl.dx3 ? bwd_fused_kernel<TN, DM, X, false, true> : bwd_fused_kernel<TN, DM, X>;
+}
+
 int bwd_fused_launch(WgradArgs &a, bool xyz, int groups, float *partial, float *dW, float *db, hipStream_t st,
                      bool side, const float *gw_bias) {
     const int K = a.K, N = a.N;
@@ -5689,100 +5734,31 @@ int bwd_fused_launch(WgradArgs &a, bool xyz, int groups, float *partial, float *
     { const char *e = getenv("PCOPS_BF_DEBUG"); a.rows_per_block = e ? atoi(e) : 0; }      // tools/ablate_bwd_fused.py
 #endif
     a.part = partial; a.dbpart = db ? partial + (long long)groups * K * N : nullptr;
-    const bool gw = a.gram_part != nullptr;     // Gram form of the weight gradient (pcops_mlp_bwd_fused_gw*): partial also
-                                                // holds [groups][K][K] + [groups][K] behind the dW / db partials
-    const int tn = N <= 64 ? 1 : 2;
-    const int NB = 64 * tn;
-    const int optv = pcops_get_option(PCOPS_OPT_BWD_FUSED_DX_SPLIT_BF16);
-    const bool dx3 = optv != 0;
-    // split-operand dW half (bwd_fused_kernel<.., DW3>; option value 2, the default): on the 128-column tile of layers whose
-    // input is READ.  Measured where it is not built (round 6, profiles/r06_bwd_fused_dw3.txt): the 64-column tile (+7 %: two
-    // waves' worth of matrix work saved, the producers' piece splitting added) and the xyz forms (+9 %: their producers
-    // already rebuild the first layer per row) are slower with it; nor with the Gram form or the column skip (N <= 96).
-    const bool dw3 = optv >= 2 && tn == 2 && !xyz && !a.gram_part && !(nsk_on() && N <= 96);
-    const size_t lds = (dw3 && side && PCOPS_BF_RM) ? (size_t)((xyz ? 6 : 2) * 64 + 3 * NB + 2 * 32 * (64 + (side ? 12 : 4))) * sizeof(float) +
-                                 (size_t)2 * 3 * (64 + NB) * 32 * 2 + (size_t)2 * 3 * 32 * (NB + 8) * 2
-                     : dw3 ? (size_t)((xyz ? 6 : 2) * 64 + 3 * NB + 2 * 32 * (64 + NB + (side ? 12 : 4))) * sizeof(float) +
-                                 (size_t)2 * 3 * (64 + NB) * 40 * 2
-                           : (size_t)((xyz ? 6 : 2) * 64 + 3 * NB + NB * 64 + 2 * 32 * (2 * 64 + NB + (side ? 12 : 4))) * sizeof(float);
-    const bool pooled = a.gpool != nullptr;
-    const bool nsk = nsk_on() && tn == 2 && N <= 96;
-    pcops_note_pipe(dw3 ? 1 : (dx3 ? 2 : 0));
-    pcops_note_plan(3, dw3 ? 2 : (dx3 ? 1 : 0), NB, 0, (gw ? 8 : 0) + (a.blocks ? 4 : (!pooled ? 0 : (a.S % 32 == 0 && !side ? 1 : 2))));
-    if (gw) {
-        if (!dx3 || xyz || a.blocks || !a.gpool) return PCOPS_ERR_UNSUPPORTED;
-#define PCOPS_BFG_LAUNCH(TN_, DM_, NSK_, SIDE_)                                                            \
-    do {                                                                                                   \
-        auto kern = bwd_fused_kernel<TN_, DM_, false, NSK_, true, SIDE_, true>;                            \
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern),                                      \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)     \
-            return PCOPS_ERR_LAUNCH;                                                                       \
-        hipLaunchKernelGGL(kern, dim3(groups), dim3(512), lds, st, a);                                     \
-    } while (0)
-        const bool u = a.S % 32 == 0;
-        if (side) {
-            if (tn == 1) PCOPS_BFG_LAUNCH(1, A_DYPOOL, false, true);
-            else PCOPS_BFG_LAUNCH(2, A_DYPOOL, false, true);
-        } else if (tn == 1) {
-            if (u) PCOPS_BFG_LAUNCH(1, A_DYPOOLU, false, false);
-            else PCOPS_BFG_LAUNCH(1, A_DYPOOL, false, false);
-        } else if (nsk) {
-            if (u) PCOPS_BFG_LAUNCH(2, A_DYPOOLU, true, false);
-            else PCOPS_BFG_LAUNCH(2, A_DYPOOL, true, false);
-        } else {
-            if (u) PCOPS_BFG_LAUNCH(2, A_DYPOOLU, false, false);
-            else PCOPS_BFG_LAUNCH(2, A_DYPOOL, false, false);
-        }
-#undef PCOPS_BFG_LAUNCH
-        int rcg = pcops_launch_status();
-        if (rcg) return rcg;
+    const BwdFusedPlan pl = bwd_fused_plan(a, xyz, side);
+    pcops_note_pipe(pl.dw3 ? 1 : (pl.dx3 ? 2 : 0));
+    pcops_note_plan(3, pl.dw3 ? 2 : (pl.dx3 ? 1 : 0), 64 * pl.tn, 0, (pl.gw ? 8 : 0) + pool_code(pl.dm));
+    if (pl.gw && (!pl.dx3 || xyz || a.blocks || !a.gpool)) return PCOPS_ERR_UNSUPPORTED;
+    auto run = [&](void (*kern)(WgradArgs)) {
+        return pcops_launch_lds(kern, dim3(groups), dim3(512), pl.lds, 160 * 1024, st, a);
+    };
+    const int rc = pcops_dispatch<1, 2>(pl.tn, PCOPS_ERR_UNSUPPORTED, [&](auto tn_) {
+        constexpr int TN = decltype(tn_)::value;
+        if (pl.gw)
+            return pcops_dispatch<A_DYPOOL, A_DYPOOLU>(pl.dm, PCOPS_ERR_UNSUPPORTED, [&](auto dm_) {
+                return run(bwd_fused_gw_kernel<TN, decltype(dm_)::value>(pl));
+            });
+        if (side) return run(bwd_fused_side_kernel<TN>(pl));
+        return pcops_dispatch<A_DY, A_DYW, A_DYPOOL, A_DYPOOLU, A_DYPOOLB>(pl.dm, PCOPS_ERR_UNSUPPORTED, [&](auto dm_) {
+            constexpr int DM = decltype(dm_)::value;
+            return run(xyz ? bwd_fused_plain_kernel<TN, DM, true>(pl) : bwd_fused_plain_kernel<TN, DM, false>(pl));
+        });
+    });
+    if (rc) return rc;
+    if (pl.gw) {
         hipLaunchKernelGGL(bwd_fused_gw_finish_kernel, dim3(K, cdiv(N, 128)), dim3(128), 0, st, groups, K, N, a.part,
                            a.dbpart, a.gram_part, a.xsum_part, a.W, gw_bias, a.q, a.t, dW, db);
         return pcops_launch_status();
     }
-#define PCOPS_BF_LAUNCH(TN_, DM_, X_)                                                                      \
-    do {                                                                                                   \
-        auto kern = dw3 ? bwd_fused_dw3_kernel<TN_, DM_, X_>()                                               \
-                  : dx3 ? ((TN_ == 2 && nsk) ? bwd_fused_kernel<TN_, DM_, X_, TN_ == 2, true>                  \
-                                              : bwd_fused_kernel<TN_, DM_, X_, false, true>)                    \
-                        : ((TN_ == 2 && nsk) ? bwd_fused_kernel<TN_, DM_, X_, TN_ == 2> : bwd_fused_kernel<TN_, DM_, X_>);                                                      \
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern),                                      \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)     \
-            return PCOPS_ERR_LAUNCH;                                                                       \
-        hipLaunchKernelGGL(kern, dim3(groups), dim3(512), lds, st, a);                                     \
-    } while (0)
-#define PCOPS_BF_MODES(TN_, X_)                                                                            \
-    do {                                                                                                   \
-        if (!pooled && a.blocks) PCOPS_BF_LAUNCH(TN_, A_DYW, X_);                                          \
-        else if (a.blocks) PCOPS_BF_LAUNCH(TN_, A_DYPOOLB, X_);                                            \
-        else if (!pooled) PCOPS_BF_LAUNCH(TN_, A_DY, X_);                                                  \
-        else if (a.S % 32 == 0) PCOPS_BF_LAUNCH(TN_, A_DYPOOLU, X_);                                       \
-        else PCOPS_BF_LAUNCH(TN_, A_DYPOOL, X_);                                                           \
-    } while (0)
-    if (side) {
-        // (the first EdgeConv layer below: pooled groups of k neighbours, plain rows -- pcops_mlp_bwd_fused_edge checks)
-#define PCOPS_BF_SIDE(TN_)                                                                                 \
-    do {                                                                                                   \
-        auto kern = dw3 ? bwd_fused_dw3_side_kernel<TN_>()                                                 \
-                  : dx3 ? bwd_fused_kernel<TN_, A_DYPOOL, false, false, true, true>                        \
-                        : bwd_fused_kernel<TN_, A_DYPOOL, false, false, false, true>;                      \
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern),                                      \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)     \
-            return PCOPS_ERR_LAUNCH;                                                                       \
-        hipLaunchKernelGGL(kern, dim3(groups), dim3(512), lds, st, a);                                     \
-    } while (0)
-        if (tn == 1) PCOPS_BF_SIDE(1);
-        else PCOPS_BF_SIDE(2);
-#undef PCOPS_BF_SIDE
-    } else
-    if (tn == 1 && xyz) PCOPS_BF_MODES(1, true);
-    else if (tn == 1) PCOPS_BF_MODES(1, false);
-    else if (xyz) PCOPS_BF_MODES(2, true);
-    else PCOPS_BF_MODES(2, false);
-#undef PCOPS_BF_MODES
-#undef PCOPS_BF_LAUNCH
-    int rc = pcops_launch_status();
-    if (rc) return rc;
     const long long L = (long long)K * N;
     hipLaunchKernelGGL(sum_partials2_kernel, dim3(cdiv(L, 64) + (db ? cdiv(N, 64) : 0)), dim3(1024), 0, st, groups, L,
                        partial, dW, (long long)N, a.dbpart, db);
@@ -5790,54 +5766,52 @@ int bwd_fused_launch(WgradArgs &a, bool xyz, int groups, float *partial, float *
 }
 
 int gram_full_launch(GramArgs &g, int nbk, bool bnrelu, int gg, size_t lds, hipStream_t st) {
-#define PCOPS_GRAM_LAUNCH(NBK_)                                                                            \
-    do {                                                                                                   \
-        auto kern = bnrelu ? gram_full_kernel<NBK_, true> : gram_full_kernel<NBK_, false>;               \
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern),                                      \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)     \
-            return PCOPS_ERR_LAUNCH;                                                                       \
-        hipLaunchKernelGGL(kern, dim3(gg), dim3(512), lds, st, g);                                         \
-    } while (0)
-        switch (nbk) {
-            case 1: PCOPS_GRAM_LAUNCH(1); break;
-            case 2: PCOPS_GRAM_LAUNCH(2); break;
-            case 3: PCOPS_GRAM_LAUNCH(3); break;
-            case 4: PCOPS_GRAM_LAUNCH(4); break;
-            case 5: PCOPS_GRAM_LAUNCH(5); break;
-            case 6: PCOPS_GRAM_LAUNCH(6); break;
-            case 7: PCOPS_GRAM_LAUNCH(7); break;
-            case 8: PCOPS_GRAM_LAUNCH(8); break;
-            case 9: PCOPS_GRAM_LAUNCH(9); break;
-            default: PCOPS_GRAM_LAUNCH(10); break;
-        }
-#undef PCOPS_GRAM_LAUNCH
-    return PCOPS_OK;
+    return pcops_dispatch<1, 2, 3, 4, 5, 6, 7, 8, 9, 10>(nbk, PCOPS_ERR_UNSUPPORTED, [&](auto nbk_) {
+        constexpr int NBK = decltype(nbk_)::value;
+        return pcops_launch_lds(bnrelu ? gram_full_kernel<NBK, true> : gram_full_kernel<NBK, false>, dim3(gg), dim3(512), lds,
+                                160 * 1024, st, g);
+    });
 }
 
 // compacted rows: the widths the pooled top layers of the grouped stacks have (Kp = 64, 128), BN + ReLU input
 int gram_full_rows_launch(GramArgs &g, int nbk, int gg, size_t lds, hipStream_t st) {
-    auto kern = nbk == 2 ? gram_full_kernel<2, true, true> : gram_full_kernel<4, true, true>;
     if (nbk != 2 && nbk != 4) return PCOPS_ERR_UNSUPPORTED;
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) !=
-        hipSuccess)
-        return PCOPS_ERR_LAUNCH;
-    hipLaunchKernelGGL(kern, dim3(gg), dim3(512), lds, st, g);
-    return PCOPS_OK;
+    return pcops_launch_lds(nbk == 2 ? gram_full_kernel<2, true, true> : gram_full_kernel<4, true, true>, dim3(gg), dim3(512), lds,
+                            160 * 1024, st, g);
 }
 
 // ... on the bf16 matrix pipe with split operands (gram_rows_bf3_kernel: Kp = 128, ldx % 4 == 0 -- checked by the caller)
 int gram_rows_bf3_launch(GramArgs &g, int gg, hipStream_t st) {
     const size_t lds = 2 * 128 * sizeof(float) + (size_t)2 * 3 * 128 * 40 * 2;
-    auto kern = gram_rows_bf3_kernel<128>;
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) !=
-        hipSuccess)
-        return PCOPS_ERR_LAUNCH;
-    hipLaunchKernelGGL(kern, dim3(gg), dim3(512), lds, st, g);
-    return PCOPS_OK;
+    return pcops_launch_lds(gram_rows_bf3_kernel<128>, dim3(gg), dim3(512), lds, 160 * 1024, st, g);
 }
 #endif
 
 #if PCOPS_PART(0)
+static int rows_ok(const pcops_rows_t *rows) {
+    if (!rows) return PCOPS_OK;
+    PCOPS_REQUIRE_PTR(rows->blocks); PCOPS_REQUIRE_PTR(rows->block_start); PCOPS_REQUIRE_PTR(rows->rows);
+    if (reinterpret_cast<uintptr_t>(rows->blocks) & 15) return PCOPS_ERR_UNSUPPORTED;
+    return PCOPS_OK;
+}
+// a compacted row set (may be NULL: all rows) into GemmArgs / WgradArgs
+template <typename Args>
+static int set_rows(Args &a, const pcops_rows_t *rows) {
+    const int rc = rows_ok(rows);
+    if (rc || !rows) return rc;
+    a.blocks = static_cast<const RowBlock *>(rows->blocks);
+    a.Mdev = rows->rows;
+    return PCOPS_OK;
+}
+// the operands every forward entry point takes
+static GemmArgs fwd_args(int M, int K, int N, const float *X, int ldx, const float *pro_scale, const float *pro_shift,
+                         const float *W, const float *bias, float *Y, float *stats_partial, const float *stat_pivot) {
+    GemmArgs a = {};
+    a.M = M; a.K = K; a.N = N; a.X = X; a.ldx = ldx; a.v0 = pro_scale; a.v1 = pro_shift;
+    a.W = W; a.bias = bias; a.Y = Y; a.ldy = N; a.stats = stats_partial; a.pivot = stats_partial ? stat_pivot : nullptr;
+    return a;
+}
+
 extern "C" {
 
 int pcops_mlp_stats_rows(int M) {
@@ -5853,22 +5827,6 @@ unsigned long long pcops_mlp_reduce_workspace_bytes(int N) {
     return (unsigned long long)kRedSlices * 2 * (unsigned long long)N * sizeof(double);
 }
 
-static int rows_ok(const pcops_rows_t *rows) {
-    if (!rows) return PCOPS_OK;
-    PCOPS_REQUIRE_PTR(rows->blocks); PCOPS_REQUIRE_PTR(rows->block_start); PCOPS_REQUIRE_PTR(rows->rows);
-    if (reinterpret_cast<uintptr_t>(rows->blocks) & 15) return PCOPS_ERR_UNSUPPORTED;
-    return PCOPS_OK;
-}
-#define PCOPS_ROWS(args_, rows_)                                                      \
-    do {                                                                              \
-        const int rrc_ = rows_ok(rows_);                                              \
-        if (rrc_) return rrc_;                                                        \
-        if (rows_) {                                                                  \
-            (args_).blocks = static_cast<const RowBlock *>((rows_)->blocks);          \
-            (args_).Mdev = (rows_)->rows;                                             \
-        }                                                                             \
-    } while (0)
-
 int pcops_mlp_gemm_fwd_rows(int M, int K, int N, const float *X, int ldx, const float *pro_scale,
                             const float *pro_shift, const float *W, const float *bias, float *Y,
                             float *stats_partial, const float *stat_pivot, const pcops_rows_t *rows,
@@ -5878,10 +5836,8 @@ int pcops_mlp_gemm_fwd_rows(int M, int K, int N, const float *X, int ldx, const 
     PCOPS_REQUIRE_PTR(X); PCOPS_REQUIRE_PTR(W); PCOPS_REQUIRE_PTR(Y);
     PCOPS_REQUIRE_ARG((pro_scale == nullptr) == (pro_shift == nullptr));
     if (pro_scale) PCOPS_REQUIRE_SHAPE(K % 4 == 0);  // coefficient vectors are read 4 at a time
-    GemmArgs a = {};
-    a.M = M; a.K = K; a.N = N; a.X = X; a.ldx = ldx; a.v0 = pro_scale; a.v1 = pro_shift;
-    a.W = W; a.bias = bias; a.Y = Y; a.ldy = N; a.stats = stats_partial; a.pivot = stats_partial ? stat_pivot : nullptr;
-    PCOPS_ROWS(a, rows);
+    GemmArgs a = fwd_args(M, K, N, X, ldx, pro_scale, pro_shift, W, bias, Y, stats_partial, stat_pivot);
+    if (const int rc = set_rows(a, rows)) return rc;
     if (pro_scale) return launch_gemm<A_BNRELU, E_FWD>(a, as_stream(stream));
     return launch_gemm<A_PLAIN, E_FWD>(a, as_stream(stream));
 }
@@ -5942,9 +5898,7 @@ int pcops_mlp_gemm_fwd_pool(int M, int K, int N, int S, const float *X, int ldx,
     if (!fwd_pool_shape_ok(M, K, N, S) || ldx != K) return PCOPS_ERR_UNSUPPORTED;
     if ((reinterpret_cast<uintptr_t>(ysel) & 15) || (reinterpret_cast<uintptr_t>(argsel) & 3))
         return PCOPS_ERR_UNSUPPORTED;
-    GemmArgs a = {};
-    a.M = M; a.K = K; a.N = N; a.X = X; a.ldx = ldx; a.v0 = pro_scale; a.v1 = pro_shift;
-    a.W = W; a.bias = bias; a.Y = Y; a.ldy = N; a.stats = stats_partial; a.pivot = stats_partial ? stat_pivot : nullptr;
+    GemmArgs a = fwd_args(M, K, N, X, ldx, pro_scale, pro_shift, W, bias, Y, stats_partial, stat_pivot);
     set_pool_group(a, S);
     a.pgamma = gamma; a.ysel = ysel; a.psel = argsel;
     WsPlan pl;
@@ -5965,11 +5919,9 @@ int pcops_mlp_gemm_fwd_pool_rows(int M, int K, int N, const float *X, int ldx, c
     PCOPS_REQUIRE_PTR(rows);
     if (ldx != K || (reinterpret_cast<uintptr_t>(ypart) & 15) || (reinterpret_cast<uintptr_t>(ppart) & 3))
         return PCOPS_ERR_UNSUPPORTED;
-    GemmArgs a = {};
-    a.M = M; a.K = K; a.N = N; a.X = X; a.ldx = ldx; a.v0 = pro_scale; a.v1 = pro_shift;
-    a.W = W; a.bias = bias; a.Y = Y; a.ldy = N; a.stats = stats_partial; a.pivot = stats_partial ? stat_pivot : nullptr;
+    GemmArgs a = fwd_args(M, K, N, X, ldx, pro_scale, pro_shift, W, bias, Y, stats_partial, stat_pivot);
     a.pool_sub = 1; a.pgamma = gamma; a.ysel = ypart; a.psel = ppart;       // one partial per 16-row block
-    PCOPS_ROWS(a, rows);
+    if (const int rc = set_rows(a, rows)) return rc;
     WsPlan pl;
     if (!(ws_enabled() && ws_plan(a, A_BNRELU, &pl))) return PCOPS_ERR_UNSUPPORTED;
     return launch_gemm<A_BNRELU, E_FWD>(a, as_stream(stream));
@@ -6185,7 +6137,7 @@ int pcops_mlp_gemm_dgrad_rows(int M, int K, int Nout, const float *G, const floa
     a.v3 = pool_scale; a.v4 = pool_shift; a.gpool = gpool; a.argmax = argmax; a.S = S > 0 ? S : 1;
     a.W = Wt; a.Y = Gprev; a.ldy = Nout; a.Yprev = Yprev; a.msc = prev_scale; a.msh = prev_shift;
     a.stats = stats_partial;
-    PCOPS_ROWS(a, rows);
+    if (const int rc = set_rows(a, rows)) return rc;
     hipStream_t st = as_stream(stream);
     if (gpool) {
         PCOPS_REQUIRE_PTR(argmax); PCOPS_REQUIRE_PTR(pool_scale); PCOPS_REQUIRE_PTR(pool_shift);
@@ -6206,9 +6158,8 @@ int pcops_mlp_xyz_supported(int M, int C1, int N2) {
     GemmArgs d = {};
     d.M = M; d.K = N2; d.N = C1; d.ldx = N2; d.ldy = C1;
     WsPlan pl;
-    PcWgradPlan pc;
     return ws_enabled() && wgrad_pc_enabled() && C1 % 4 == 0 && ws_plan(f, A_XYZ, &pl) && ws_plan(d, A_DY, &pl) &&
-           wgrad_pc_plan(M, C1, N2, C1, nullptr, nullptr, nullptr, nullptr, nullptr, &pc) ? 1 : 0;
+           wgrad_pc_shape_ok(M, C1, N2, C1) ? 1 : 0;
 }
 
 /* forward of the layer FOLLOWING an arithmetic first layer: X = relu(pro_scale * y + pro_shift), y rebuilt from
@@ -6228,11 +6179,9 @@ int pcops_mlp_gemm_fwd_xyz_rows(int M, int K, int N, const float *off4, const fl
     PCOPS_REQUIRE_PTR(off4); PCOPS_REQUIRE_PTR(xyzw); PCOPS_REQUIRE_PTR(pro_scale); PCOPS_REQUIRE_PTR(pro_shift);
     PCOPS_REQUIRE_PTR(W); PCOPS_REQUIRE_PTR(Y);
     if (reinterpret_cast<uintptr_t>(off4) & 15) return PCOPS_ERR_UNSUPPORTED;
-    GemmArgs a = {};
-    a.M = M; a.K = K; a.N = N; a.X = nullptr; a.ldx = K; a.v0 = pro_scale; a.v1 = pro_shift;
+    GemmArgs a = fwd_args(M, K, N, nullptr, K, pro_scale, pro_shift, W, bias, Y, stats_partial, stat_pivot);
     a.off4 = off4; a.xw = xyzw; a.xw_ld = K;
-    a.W = W; a.bias = bias; a.Y = Y; a.ldy = N; a.stats = stats_partial; a.pivot = stats_partial ? stat_pivot : nullptr;
-    PCOPS_ROWS(a, rows);
+    if (const int rc = set_rows(a, rows)) return rc;
     return launch_gemm_ws_only<A_XYZ, E_FWD>(a, as_stream(stream));
 }
 
@@ -6267,7 +6216,7 @@ int pcops_mlp_gemm_dgrad_xyz_rows(int M, int K, int Nout, const float *G, const 
     a.W = Wt; a.Y = Gprev; a.ldy = Nout; a.msc = prev_scale; a.msh = prev_shift;
     a.off4 = off4; a.xw = xyzw; a.xw_ld = Nout;
     a.stats = stats_partial; a.xstats = xyz_stats;
-    PCOPS_ROWS(a, rows);
+    if (const int rc = set_rows(a, rows)) return rc;
     hipStream_t st = as_stream(stream);
     if (gpool) {
         PCOPS_REQUIRE_PTR(argmax); PCOPS_REQUIRE_PTR(pool_scale); PCOPS_REQUIRE_PTR(pool_shift);
@@ -6283,43 +6232,22 @@ int pcops_mlp_gemm_dgrad_xyz_rows(int M, int K, int Nout, const float *G, const 
 static int gram_full_groups(long long M, int K, int ldx, const void *X) {
     if (!gram_full_on() || !ws_enabled() || M < 65536 || K > 320 || K < 32 || K % 4 != 0 || ldx % 4 != 0) return 0;
     if (reinterpret_cast<uintptr_t>(X) & 15) return 0;
-    long long g = 256;
-    const long long ns = (M + 31) / 32;
-    if (g > ns) g = ns;
-    if (g >= 8) g &= ~7ll;
-    return (int)g;
+    return clamp_groups(256, (M + 31) / 32);
 }
 
 int pcops_mlp_wgrad_splits(long long M, int K, int N) {
-    // upper bound of the partial copies ANY of the three wgrad kernels writes for this shape (the scratch is sized
-    // with it): the group counts of wgrad_pc_plan / wgrad_ws_plan before their M clamp, and the legacy split count.
+    // upper bound of the partial copies ANY weight-gradient kernel writes for this shape (the scratch is sized with it): the
+    // row groups every planner wants before its clamp to M, asked of the planners themselves, and the legacy split count.
     // (It used to be a flat 512, i.e. 1 GiB of scratch for the 512 -> 1024 layer whose kernels write 16 partials.)
+    WgradPlan pl;
     int best = wgrad_legacy_splits(M, K, N);
-    {   // wgrad_pc_plan
-        const int tk = K <= 64 ? 1 : 2, tn = N <= 64 ? 1 : (N <= 128 ? 2 : 4);
-        const int kb = (K + 64 * tk - 1) / (64 * tk), nb = (N + 64 * tn - 1) / (64 * tn);
-        int g = (tk * tn == 1 ? 512 : 256) / (kb * nb);
-        if (g < 1) g = 1;
+    for (const int g : {wgrad_pc_tile(K, N, false, &pl), wgrad_pc_tile(K, N, true, &pl), wgrad_bf3_tile(K, N, &pl),
+                        wgrad_ws_tile(K, N, &pl)})
         if (g > best) best = g;
-        if (K == N) {                 // pcops_mlp_gram of this width may take the single-pass kernel: a copy per workgroup
-            const int gg = gram_full_groups(M, K, 4, nullptr);
-            if (gg > best) best = gg;
-        }
-    }
-    {   // wgrad_ws_plan
-        int tk, tn;
-        if (K <= 64 && N <= 64) { tk = 2; tn = 2; }
-        else if (K <= 64) { tk = 2; tn = 4; }
-        else { tk = 4; tn = 4; }
-        const int kb = (K + 32 * tk - 1) / (32 * tk), nb = (N + 32 * tn - 1) / (32 * tn);
-        int g = 256 / (kb * nb);
-        if (g < 1) g = 1;
-        if (g > best) best = g;
-    }
+    // pcops_mlp_gram of this width may take the single-pass kernel: a copy per workgroup
+    if (K == N && gram_full_groups(M, K, 4, nullptr) > best) best = gram_full_groups(M, K, 4, nullptr);
     return best;
 }
-
-
 
 /* 1 when EVERY launch of a grouped stack on compacted rows has a kernel for its shape -- the *_rows entry points have no
  * tiled fallback, so a caller decides with this (and nothing else) whether to compact: group size a multiple of the
@@ -6338,10 +6266,7 @@ int pcops_gather_stack_rows_supported(int b, int n, int m, int s, int has_q, int
         GemmArgs d = {};                 // data gradient: (M, N) -> (M, K)
         d.M = (int)M; d.K = N; d.N = K; d.ldx = N; d.ldy = K; d.S = s;
         WsPlan pl;
-        PcWgradPlan pc;
-        if (!ws_plan(f, A_BNRELU, &pl) || !ws_plan(d, A_DY, &pl) ||
-            !wgrad_pc_plan(M, K, N, K, nullptr, nullptr, nullptr, nullptr, nullptr, &pc))
-            return 0;
+        if (!ws_plan(f, A_BNRELU, &pl) || !ws_plan(d, A_DY, &pl) || !wgrad_pc_shape_ok(M, K, N, K)) return 0;
     }
     if (has_q && !pcops_sa_scatter_rows_supported(n, m, s, widths[0])) return 0;
     return 1;
@@ -6357,11 +6282,7 @@ static int bwd_fused_groups(long long M, int K, int N, int S, int pooled) {
     // the bandwidth-bound 64-wide layers only: wider ones are matrix-pipe bound in both kernels and gain nothing
     if (M < 65536 || M > 0x7fffff00ll || K > 64 || K % 4 != 0 || N > 128 || N % 4 != 0) return 0;
     if (pooled && (S < 1 || S > 255)) return 0;
-    long long g = 256;
-    const long long ns = (M + 31) / 32;
-    if (g > ns) g = ns;
-    if (g >= 8) g &= ~7ll;
-    return (int)g;
+    return clamp_groups(256, (M + 31) / 32);
 }
 
 int pcops_mlp_bwd_fused_groups(long long M, int K, int N, int S, int pooled) { return bwd_fused_groups(M, K, N, S, pooled); }
@@ -6374,60 +6295,6 @@ int pcops_mlp_bwd_fused(long long M, int K, int N, const float *Yprev, const flo
                                     Gprev, stats_partial, nullptr, stream);
 }
 
-
-int pcops_mlp_bwd_fused_rows(long long M, int K, int N, const float *Yprev, const float *a_scale, const float *a_shift,
-                             const float *G, const float *Y, const float *p, const float *q, const float *t,
-                             const float *gpool, const unsigned char *argmax, int S, const float *W, float *partial,
-                             float *dW, float *db, float *Gprev, float *stats_partial, const pcops_rows_t *rows,
-                             pcops_stream_t stream) {
-    PCOPS_REQUIRE_SHAPE(M >= 1 && K >= 1 && N >= 1);
-    PCOPS_REQUIRE_PTR(Yprev); PCOPS_REQUIRE_PTR(a_scale); PCOPS_REQUIRE_PTR(a_shift); PCOPS_REQUIRE_PTR(Y);
-    PCOPS_REQUIRE_PTR(p); PCOPS_REQUIRE_PTR(q); PCOPS_REQUIRE_PTR(t); PCOPS_REQUIRE_PTR(W);
-    PCOPS_REQUIRE_PTR(partial); PCOPS_REQUIRE_PTR(dW); PCOPS_REQUIRE_PTR(Gprev); PCOPS_REQUIRE_PTR(stats_partial);
-    if (!gpool) PCOPS_REQUIRE_PTR(G);
-    if (gpool) PCOPS_REQUIRE_PTR(argmax);
-    const int groups = bwd_fused_groups(M, K, N, S, gpool != nullptr);
-    if (groups == 0) return PCOPS_ERR_UNSUPPORTED;
-    if ((reinterpret_cast<uintptr_t>(Yprev) & 15) || (reinterpret_cast<uintptr_t>(G) & 15) ||
-        (reinterpret_cast<uintptr_t>(Y) & 15) || (reinterpret_cast<uintptr_t>(gpool) & 15) ||
-        (reinterpret_cast<uintptr_t>(W) & 15) || (reinterpret_cast<uintptr_t>(argmax) & 3))
-        return PCOPS_ERR_UNSUPPORTED;
-    WgradArgs a = {};
-    a.M = M; a.K = K; a.N = N;
-    a.amode = A_BNRELU; a.X = Yprev; a.ldx = K; a.asc = a_scale; a.ash = a_shift;
-    a.dmode = gpool ? A_DYPOOL : A_DY; a.G = G; a.Y = Y; a.ldy = N; a.p = p; a.q = q; a.t = t;
-    a.gpool = gpool; a.argmax = argmax; a.S = S > 0 ? S : 1;
-    a.W = W; a.Gprev = Gprev; a.gstats = stats_partial;
-    a.nt_out = nt_for_bytes((long long)M * K * 4);
-    PCOPS_ROWS(a, rows);
-    return bwd_fused_launch(a, false, groups, partial, dW, db, as_stream(stream));
-}
-
-static int bwd_fused_edge_groups(long long M, int K, int N, int S, int gram);
-
-int pcops_mlp_bwd_fused_edge(long long M, int K, int N, const float *Yprev, const float *a_scale, const float *a_shift,
-                                  const float *Y, const float *p, const float *q, const float *t, const float *gpool,
-                                  const unsigned char *argmax, int S, const float *W, float *partial, float *dW, float *db,
-                                  float *stats_partial, const float *edge_rows, float *edge_stats, pcops_stream_t stream) {
-    PCOPS_REQUIRE_SHAPE(M >= 1 && K >= 1 && N >= 1 && S >= 1);
-    PCOPS_REQUIRE_PTR(Yprev); PCOPS_REQUIRE_PTR(a_scale); PCOPS_REQUIRE_PTR(a_shift); PCOPS_REQUIRE_PTR(Y);
-    PCOPS_REQUIRE_PTR(p); PCOPS_REQUIRE_PTR(q); PCOPS_REQUIRE_PTR(t); PCOPS_REQUIRE_PTR(W); PCOPS_REQUIRE_PTR(gpool);
-    PCOPS_REQUIRE_PTR(argmax); PCOPS_REQUIRE_PTR(partial); PCOPS_REQUIRE_PTR(dW); PCOPS_REQUIRE_PTR(stats_partial);
-    PCOPS_REQUIRE_PTR(edge_rows); PCOPS_REQUIRE_PTR(edge_stats);
-    const int groups = bwd_fused_edge_groups(M, K, N, S, 0);
-    if (groups == 0) return PCOPS_ERR_UNSUPPORTED;
-    if ((reinterpret_cast<uintptr_t>(Yprev) & 15) || (reinterpret_cast<uintptr_t>(Y) & 15) ||
-        (reinterpret_cast<uintptr_t>(gpool) & 15) || (reinterpret_cast<uintptr_t>(W) & 15) ||
-        (reinterpret_cast<uintptr_t>(argmax) & 3) || (reinterpret_cast<uintptr_t>(edge_rows) & 15))
-        return PCOPS_ERR_UNSUPPORTED;
-    WgradArgs a = {};
-    a.M = M; a.K = K; a.N = N;
-    a.amode = A_BNRELU; a.X = Yprev; a.ldx = K; a.asc = a_scale; a.ash = a_shift;
-    a.dmode = A_DYPOOL; a.G = nullptr; a.Y = Y; a.ldy = N; a.p = p; a.q = q; a.t = t;
-    a.gpool = gpool; a.argmax = argmax; a.S = S;
-    a.W = W; a.Gprev = nullptr; a.gstats = stats_partial; a.xstats = edge_stats; a.side = edge_rows;
-    return bwd_fused_launch(a, false, groups, partial, dW, db, as_stream(stream), true);
-}
 
 /* ---- the one-pass backward of a POOLED layer with its weight gradient in the Gram form (round 6; bwd_fused_kernel<.., GW>):
  * uncompacted rows, groups of 11 <= S <= 255 rows (whole 32-row tiles included; the edge form below: S % 32 != 0 only),
@@ -6452,33 +6319,78 @@ int pcops_mlp_bwd_fused_edge_groups(long long M, int K, int N, int S, int gram) 
     return bwd_fused_edge_groups(M, K, N, S, gram);
 }
 
+// What the one-pass-backward entry points share: the checks in their order -- shape, pointers (the common ones, `also` the entry
+// point's own, G or the arg-max by form), a plan for the shape (groups), alignment -- and the common operands into a.  The
+// caller has set a.side (the EdgeConv forms) and sets what else its form takes.
+static int bwd_fused_args(WgradArgs &a, bool shape_ok, int groups, std::initializer_list<const void *> also, long long M,
+                          int K, int N, const float *X, const float *a_scale, const float *a_shift, const float *G,
+                          const float *Y, const float *p, const float *q, const float *t, const float *gpool,
+                          const unsigned char *argmax, int S, const float *W, const float *partial, const float *dW,
+                          float *Gprev, float *stats_partial) {
+    PCOPS_REQUIRE_SHAPE(shape_ok);
+    if (!X || !a_scale || !a_shift || !Y || !p || !q || !t || !W || !partial || !dW || !stats_partial)
+        return PCOPS_ERR_NULL_POINTER;
+    for (const void *ptr : also) PCOPS_REQUIRE_PTR(ptr);
+    if (!gpool) PCOPS_REQUIRE_PTR(G);
+    if (gpool) PCOPS_REQUIRE_PTR(argmax);
+    if (groups == 0) return PCOPS_ERR_UNSUPPORTED;
+    if (((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(G) | reinterpret_cast<uintptr_t>(Y) |
+          reinterpret_cast<uintptr_t>(gpool) | reinterpret_cast<uintptr_t>(W) | reinterpret_cast<uintptr_t>(a.side)) & 15) ||
+        (reinterpret_cast<uintptr_t>(argmax) & 3))
+        return PCOPS_ERR_UNSUPPORTED;
+    a.M = M; a.K = K; a.N = N;
+    a.amode = A_BNRELU; a.X = X; a.ldx = K; a.asc = a_scale; a.ash = a_shift;
+    a.dmode = gpool ? A_DYPOOL : A_DY; a.G = G; a.Y = Y; a.ldy = N; a.p = p; a.q = q; a.t = t;
+    a.gpool = gpool; a.argmax = argmax; a.S = S > 0 ? S : 1;
+    a.W = W; a.Gprev = Gprev; a.gstats = stats_partial;
+    a.nt_out = Gprev ? nt_for_bytes((long long)M * K * 4) : 0;
+    return PCOPS_OK;
+}
+
+// the Gram form's [groups][K][K] + [groups][K] behind the dW / db partials
 static void gw_carve(WgradArgs &a, float *partial, int groups, int K, int N) {
     a.gram_part = partial + (long long)groups * ((long long)K * N + N);
     a.xsum_part = a.gram_part + (long long)groups * K * K;
+}
+
+int pcops_mlp_bwd_fused_rows(long long M, int K, int N, const float *Yprev, const float *a_scale, const float *a_shift,
+                             const float *G, const float *Y, const float *p, const float *q, const float *t,
+                             const float *gpool, const unsigned char *argmax, int S, const float *W, float *partial,
+                             float *dW, float *db, float *Gprev, float *stats_partial, const pcops_rows_t *rows,
+                             pcops_stream_t stream) {
+    WgradArgs a = {};
+    const int groups = bwd_fused_groups(M, K, N, S, gpool != nullptr);
+    if (const int rc = bwd_fused_args(a, M >= 1 && K >= 1 && N >= 1, groups, {Gprev}, M, K, N, Yprev, a_scale, a_shift, G, Y,
+                                      p, q, t, gpool, argmax, S, W, partial, dW, Gprev, stats_partial))
+        return rc;
+    if (const int rc = set_rows(a, rows)) return rc;
+    return bwd_fused_launch(a, false, groups, partial, dW, db, as_stream(stream));
+}
+
+int pcops_mlp_bwd_fused_edge(long long M, int K, int N, const float *Yprev, const float *a_scale, const float *a_shift,
+                                  const float *Y, const float *p, const float *q, const float *t, const float *gpool,
+                                  const unsigned char *argmax, int S, const float *W, float *partial, float *dW, float *db,
+                                  float *stats_partial, const float *edge_rows, float *edge_stats, pcops_stream_t stream) {
+    WgradArgs a = {};
+    a.side = edge_rows; a.xstats = edge_stats;
+    const int groups = bwd_fused_edge_groups(M, K, N, S, 0);
+    if (const int rc = bwd_fused_args(a, M >= 1 && K >= 1 && N >= 1 && S >= 1, groups, {gpool, argmax, edge_rows, edge_stats},
+                                      M, K, N, Yprev, a_scale, a_shift, nullptr, Y, p, q, t, gpool, argmax, S, W, partial, dW,
+                                      nullptr, stats_partial))
+        return rc;
+    return bwd_fused_launch(a, false, groups, partial, dW, db, as_stream(stream), true);
 }
 
 int pcops_mlp_bwd_fused_gw(long long M, int K, int N, const float *Yprev, const float *a_scale, const float *a_shift,
                            const float *Y, const float *p, const float *q, const float *t, const float *gpool,
                            const unsigned char *argmax, int S, const float *W, const float *bias, float *partial, float *dW,
                            float *db, float *Gprev, float *stats_partial, pcops_stream_t stream) {
-    PCOPS_REQUIRE_SHAPE(M >= 1 && K >= 1 && N >= 1 && S >= 1);
-    PCOPS_REQUIRE_PTR(Yprev); PCOPS_REQUIRE_PTR(a_scale); PCOPS_REQUIRE_PTR(a_shift); PCOPS_REQUIRE_PTR(Y);
-    PCOPS_REQUIRE_PTR(p); PCOPS_REQUIRE_PTR(q); PCOPS_REQUIRE_PTR(t); PCOPS_REQUIRE_PTR(W); PCOPS_REQUIRE_PTR(gpool);
-    PCOPS_REQUIRE_PTR(argmax); PCOPS_REQUIRE_PTR(partial); PCOPS_REQUIRE_PTR(dW); PCOPS_REQUIRE_PTR(db);
-    PCOPS_REQUIRE_PTR(Gprev); PCOPS_REQUIRE_PTR(stats_partial);
-    const int groups = bwd_fused_gw_groups(M, K, N, S);
-    if (groups == 0) return PCOPS_ERR_UNSUPPORTED;
-    if ((reinterpret_cast<uintptr_t>(Yprev) & 15) || (reinterpret_cast<uintptr_t>(Y) & 15) ||
-        (reinterpret_cast<uintptr_t>(gpool) & 15) || (reinterpret_cast<uintptr_t>(W) & 15) ||
-        (reinterpret_cast<uintptr_t>(argmax) & 3))
-        return PCOPS_ERR_UNSUPPORTED;
     WgradArgs a = {};
-    a.M = M; a.K = K; a.N = N;
-    a.amode = A_BNRELU; a.X = Yprev; a.ldx = K; a.asc = a_scale; a.ash = a_shift;
-    a.dmode = A_DYPOOL; a.G = nullptr; a.Y = Y; a.ldy = N; a.p = p; a.q = q; a.t = t;
-    a.gpool = gpool; a.argmax = argmax; a.S = S;
-    a.W = W; a.Gprev = Gprev; a.gstats = stats_partial;
-    a.nt_out = nt_for_bytes((long long)M * K * 4);
+    const int groups = bwd_fused_gw_groups(M, K, N, S);
+    if (const int rc = bwd_fused_args(a, M >= 1 && K >= 1 && N >= 1 && S >= 1, groups, {gpool, argmax, db, Gprev}, M, K, N,
+                                      Yprev, a_scale, a_shift, nullptr, Y, p, q, t, gpool, argmax, S, W, partial, dW, Gprev,
+                                      stats_partial))
+        return rc;
     gw_carve(a, partial, groups, K, N);
     return bwd_fused_launch(a, false, groups, partial, dW, db, as_stream(stream), false, bias);
 }
@@ -6488,23 +6400,13 @@ int pcops_mlp_bwd_fused_edge_gw(long long M, int K, int N, const float *Yprev, c
                                 const unsigned char *argmax, int S, const float *W, const float *bias, float *partial,
                                 float *dW, float *db, float *stats_partial, const float *edge_rows, float *edge_stats,
                                 pcops_stream_t stream) {
-    PCOPS_REQUIRE_SHAPE(M >= 1 && K >= 1 && N >= 1 && S >= 1);
-    PCOPS_REQUIRE_PTR(Yprev); PCOPS_REQUIRE_PTR(a_scale); PCOPS_REQUIRE_PTR(a_shift); PCOPS_REQUIRE_PTR(Y);
-    PCOPS_REQUIRE_PTR(p); PCOPS_REQUIRE_PTR(q); PCOPS_REQUIRE_PTR(t); PCOPS_REQUIRE_PTR(W); PCOPS_REQUIRE_PTR(gpool);
-    PCOPS_REQUIRE_PTR(argmax); PCOPS_REQUIRE_PTR(partial); PCOPS_REQUIRE_PTR(dW); PCOPS_REQUIRE_PTR(db);
-    PCOPS_REQUIRE_PTR(stats_partial); PCOPS_REQUIRE_PTR(edge_rows); PCOPS_REQUIRE_PTR(edge_stats);
-    const int groups = bwd_fused_edge_groups(M, K, N, S, 1);
-    if (groups == 0) return PCOPS_ERR_UNSUPPORTED;
-    if ((reinterpret_cast<uintptr_t>(Yprev) & 15) || (reinterpret_cast<uintptr_t>(Y) & 15) ||
-        (reinterpret_cast<uintptr_t>(gpool) & 15) || (reinterpret_cast<uintptr_t>(W) & 15) ||
-        (reinterpret_cast<uintptr_t>(argmax) & 3) || (reinterpret_cast<uintptr_t>(edge_rows) & 15))
-        return PCOPS_ERR_UNSUPPORTED;
     WgradArgs a = {};
-    a.M = M; a.K = K; a.N = N;
-    a.amode = A_BNRELU; a.X = Yprev; a.ldx = K; a.asc = a_scale; a.ash = a_shift;
-    a.dmode = A_DYPOOL; a.G = nullptr; a.Y = Y; a.ldy = N; a.p = p; a.q = q; a.t = t;
-    a.gpool = gpool; a.argmax = argmax; a.S = S;
-    a.W = W; a.Gprev = nullptr; a.gstats = stats_partial; a.xstats = edge_stats; a.side = edge_rows;
+    a.side = edge_rows; a.xstats = edge_stats;
+    const int groups = bwd_fused_edge_groups(M, K, N, S, 1);
+    if (const int rc = bwd_fused_args(a, M >= 1 && K >= 1 && N >= 1 && S >= 1, groups,
+                                      {gpool, argmax, db, edge_rows, edge_stats}, M, K, N, Yprev, a_scale, a_shift, nullptr, Y,
+                                      p, q, t, gpool, argmax, S, W, partial, dW, nullptr, stats_partial))
+        return rc;
     gw_carve(a, partial, groups, K, N);
     return bwd_fused_launch(a, false, groups, partial, dW, db, as_stream(stream), true, bias);
 }
@@ -6514,25 +6416,13 @@ int pcops_mlp_bwd_fused_xyz_rows(long long M, int K, int N, const float *off4, c
                                  const float *t, const float *gpool, const unsigned char *argmax, int S, const float *W,
                                  float *partial, float *dW, float *db, float *stats_partial, float *xyz_stats,
                                  const pcops_rows_t *rows, pcops_stream_t stream) {
-    PCOPS_REQUIRE_SHAPE(M >= 1 && K >= 4 && K % 4 == 0 && N >= 1);
-    PCOPS_REQUIRE_PTR(off4); PCOPS_REQUIRE_PTR(xyzw); PCOPS_REQUIRE_PTR(a_scale); PCOPS_REQUIRE_PTR(a_shift);
-    PCOPS_REQUIRE_PTR(Y); PCOPS_REQUIRE_PTR(p); PCOPS_REQUIRE_PTR(q); PCOPS_REQUIRE_PTR(t); PCOPS_REQUIRE_PTR(W);
-    PCOPS_REQUIRE_PTR(partial); PCOPS_REQUIRE_PTR(dW); PCOPS_REQUIRE_PTR(stats_partial); PCOPS_REQUIRE_PTR(xyz_stats);
-    if (!gpool) PCOPS_REQUIRE_PTR(G);
-    if (gpool) PCOPS_REQUIRE_PTR(argmax);
-    const int groups = bwd_fused_groups(M, K, N, S, gpool != nullptr);
-    if (groups == 0) return PCOPS_ERR_UNSUPPORTED;
-    if ((reinterpret_cast<uintptr_t>(off4) & 15) || (reinterpret_cast<uintptr_t>(G) & 15) ||
-        (reinterpret_cast<uintptr_t>(Y) & 15) || (reinterpret_cast<uintptr_t>(gpool) & 15) ||
-        (reinterpret_cast<uintptr_t>(W) & 15) || (reinterpret_cast<uintptr_t>(argmax) & 3))
-        return PCOPS_ERR_UNSUPPORTED;
     WgradArgs a = {};
-    a.M = M; a.K = K; a.N = N;
-    a.amode = A_XYZ; a.X = off4; a.ldx = 4; a.off4 = off4; a.xw = xyzw; a.xw_ld = K; a.asc = a_scale; a.ash = a_shift;
-    a.dmode = gpool ? A_DYPOOL : A_DY; a.G = G; a.Y = Y; a.ldy = N; a.p = p; a.q = q; a.t = t;
-    a.gpool = gpool; a.argmax = argmax; a.S = S > 0 ? S : 1;
-    a.W = W; a.Gprev = nullptr; a.gstats = stats_partial; a.xstats = xyz_stats;
-    PCOPS_ROWS(a, rows);
+    const int groups = bwd_fused_groups(M, K, N, S, gpool != nullptr);
+    if (const int rc = bwd_fused_args(a, M >= 1 && K >= 4 && K % 4 == 0 && N >= 1, groups, {xyzw, xyz_stats}, M, K, N, off4,
+                                      a_scale, a_shift, G, Y, p, q, t, gpool, argmax, S, W, partial, dW, nullptr, stats_partial))
+        return rc;
+    a.amode = A_XYZ; a.ldx = 4; a.off4 = off4; a.xw = xyzw; a.xw_ld = K; a.xstats = xyz_stats;
+    if (const int rc = set_rows(a, rows)) return rc;
     return bwd_fused_launch(a, true, groups, partial, dW, db, as_stream(stream));
 }
 
@@ -6559,7 +6449,7 @@ int pcops_mlp_wgrad_rows(long long M, int K, int N, const float *X, int ldx, con
     a.amode = a_scale ? A_BNRELU : A_PLAIN; a.X = X; a.ldx = ldx; a.asc = a_scale; a.ash = a_shift;
     a.dmode = gpool ? A_DYPOOL : A_DY; a.G = G; a.Y = Y; a.ldy = N; a.p = p; a.q = q; a.t = t;
     a.dsc = pool_scale; a.dsh = pool_shift; a.gpool = gpool; a.argmax = argmax; a.S = S > 0 ? S : 1;
-    PCOPS_ROWS(a, rows);
+    if (const int rc = set_rows(a, rows)) return rc;
     return wgrad_impl(a, partial, dW, db, as_stream(stream));
 }
 
@@ -6591,7 +6481,7 @@ int pcops_mlp_wgrad_xyz_rows(long long M, int K, int N, const float *off4, const
     a.off4 = off4; a.xw = xyzw; a.xw_ld = K;
     a.dmode = gpool ? A_DYPOOL : A_DY; a.G = G; a.Y = Y; a.ldy = N; a.p = p; a.q = q; a.t = t;
     a.dsc = pool_scale; a.dsh = pool_shift; a.gpool = gpool; a.argmax = argmax; a.S = S > 0 ? S : 1;
-    PCOPS_ROWS(a, rows);
+    if (const int rc = set_rows(a, rows)) return rc;
     return wgrad_impl(a, partial, dW, db, as_stream(stream));
 }
 
@@ -6604,10 +6494,9 @@ static bool dgrad_top_plan(int M, int Kp, WsPlan *pl) {
 
 int pcops_mlp_pool_top_supported(int M, int Kp, int N, int S) {
     WsPlan pl;
-    PcWgradPlan pc;
     if (S < 1 || S > 256 || M % S != 0 || N % 4 != 0 || N > 1024) return 0;
     if (!dgrad_top_plan(M, Kp, &pl)) return 0;
-    if (!(wgrad_pc_enabled() && wgrad_pc_plan(M, Kp, Kp, Kp, nullptr, nullptr, nullptr, nullptr, nullptr, &pc, true))) return 0;
+    if (!(wgrad_pc_enabled() && wgrad_pc_shape_ok(M, Kp, Kp, Kp, true))) return 0;
     const long long slots = (long long)(M / S) * (S < N ? S : N);
     return slots * Kp * 4 < (long long)kOOB ? 1 : 0;
 }
@@ -6639,6 +6528,15 @@ int pcops_mlp_gemm_dgrad_top(int M, int Kp, const float *Yprev, const float *pre
                                          stats_partial, nullptr, stream);
 }
 
+// what follows a single-pass Gram kernel: its gg partial copies summed into gram (upper blocks) and xsum, the lower triangle mirrored
+static int gram_finish(const GramArgs &g, int gg, float *gram, float *xsum, hipStream_t st) {
+    const long long L = (long long)g.K * g.K;
+    hipLaunchKernelGGL(sum_partials2_kernel, dim3(cdiv(L, 64) + (xsum ? cdiv(g.K, 64) : 0)), dim3(1024), 0, st, gg, L,
+                       g.part, gram, (long long)g.K, g.xpart, xsum);
+    hipLaunchKernelGGL(mirror_lower_kernel, dim3(g.K), dim3(256), 0, st, g.K, gram);
+    return pcops_launch_status();
+}
+
 /* gram [Kp][Kp] = X^T X, xsum [Kp] = X^T 1 with X = relu(Yprev * a_scale + a_shift);  partial as pcops_mlp_wgrad
  * (pcops_mlp_wgrad_splits(M, Kp, Kp) copies) */
 int pcops_mlp_gram(long long M, int Kp, const float *Yprev, int ldx, const float *a_scale, const float *a_shift,
@@ -6654,17 +6552,8 @@ int pcops_mlp_gram(long long M, int Kp, const float *Yprev, int ldx, const float
         GramArgs g = {M, Kp, ldx, Yprev, a_scale, a_shift, partial, partial + (long long)gg * Kp * Kp};
         const int nbk = (Kp + 31) / 32;
         const size_t lds = (size_t)(2 * 32 * nbk + 2 * 32 * (32 * nbk + 4)) * sizeof(float);
-        {
-            const int rcl = gram_full_launch(g, nbk, a_scale != nullptr, gg, lds, st);
-            if (rcl) return rcl;
-        }
-        int rc = pcops_launch_status();
-        if (rc) return rc;
-        const long long L = (long long)Kp * Kp;
-        hipLaunchKernelGGL(sum_partials2_kernel, dim3(cdiv(L, 64) + (xsum ? cdiv(Kp, 64) : 0)), dim3(1024), 0, st, gg, L,
-                           partial, gram, (long long)Kp, g.xpart, xsum);
-        hipLaunchKernelGGL(mirror_lower_kernel, dim3(Kp), dim3(256), 0, st, Kp, gram);
-        return pcops_launch_status();
+        const int rc = gram_full_launch(g, nbk, a_scale != nullptr, gg, lds, st);
+        return rc ? rc : gram_finish(g, gg, gram, xsum, st);
     }
     WgradArgs a = {};
     a.M = M; a.K = Kp; a.N = Kp;
@@ -6720,19 +6609,10 @@ int pcops_mlp_pool_top_addend_rows(int M, int Kp, int N, int S, const float *gou
     const size_t lds = ((size_t)N * Kp + 4 * 256 + 4 * 128 * 8) * sizeof(float);
     const int grid = (G + 3) / 4 < 256 ? (G + 3) / 4 : 256;
     hipStream_t st = as_stream(stream);
-#define PCOPS_ADDR_LAUNCH(KP_)                                                                              \
-    do {                                                                                                    \
-        auto kern = pool_top_addend_rows_kernel<KP_>;                                                       \
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                160 * 1024) != hipSuccess)                                                  \
-            return PCOPS_ERR_LAUNCH;                                                                        \
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(1024), lds, st, G, N, gout, ysel, argmax, pool_scale, pool_shift, p, \
-                           Wt, rows->block_start, addend, rowmap);                                          \
-    } while (0)
-    if (Kp == 64) PCOPS_ADDR_LAUNCH(64);
-    else PCOPS_ADDR_LAUNCH(128);
-#undef PCOPS_ADDR_LAUNCH
-    return pcops_launch_status();
+    return pcops_dispatch<64, 128>(Kp, PCOPS_ERR_UNSUPPORTED, [&](auto kp_) {
+        return pcops_launch_lds(pool_top_addend_rows_kernel<decltype(kp_)::value>, dim3(grid), dim3(1024), lds, 160 * 1024, st, G, N,
+                                gout, ysel, argmax, pool_scale, pool_shift, p, Wt, rows->block_start, addend, rowmap);
+    });
 }
 
 int pcops_mlp_pool_top_wsparse_rows(int M, int Kp, int N, int S, const float *gout, const float *ysel,
@@ -6755,15 +6635,6 @@ int pcops_mlp_pool_top_wsparse_rows(int M, int Kp, int N, int S, const float *go
     const size_t lds = (size_t)S * (Kp + 1) * sizeof(float);
     float *part2 = partial + (long long)kTopRowsWs * Kp * N;
     hipStream_t st = as_stream(stream);
-#define PCOPS_WSPR_LAUNCH(KP_)                                                                              \
-    do {                                                                                                    \
-        auto kern = pool_top_wsparse_rows_kernel<KP_>;                                                      \
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                160 * 1024) != hipSuccess)                                                  \
-            return PCOPS_ERR_LAUNCH;                                                                        \
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, G, N, S, gout, ysel, argmax, pool_scale, pool_shift, p, \
-                           Yprev, prev_scale, prev_shift, rows->block_start, partial, part2);               \
-    } while (0)
     // PCOPS_OPT_POOL_TOP_ROWS_PIPELINED = 1 (default): the software-pipelined kernel (both widths; NR = the float4 a thread
     // holds of a group of S rows).  Same grid, so pcops_mlp_pool_top_wsparse_rows_partial covers both.
     // two images of NR x (256 / (Kp / 4)) = 64 or 128 rows each: every row a group can have, because
@@ -6771,25 +6642,14 @@ int pcops_mlp_pool_top_wsparse_rows(int M, int Kp, int N, int S, const float *go
     const int img_rows = S <= 64 ? 64 : 128;
     if (S > img_rows) return PCOPS_ERR_UNSUPPORTED;
     const size_t lds_pipe = (size_t)2 * img_rows * (Kp + 4) * sizeof(float);
-#define PCOPS_WSPP_LAUNCH(KP_, NR_)                                                                         \
-    do {                                                                                                    \
-        auto kern = pool_top_wsparse_rows_pipe_kernel<KP_, NR_>;                                            \
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                160 * 1024) != hipSuccess)                                                  \
-            return PCOPS_ERR_LAUNCH;                                                                        \
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds_pipe, st, G, N, S, gout, ysel, argmax, pool_scale, pool_shift, p, \
-                           Yprev, prev_scale, prev_shift, rows->block_start, partial, part2);               \
-    } while (0)
-    if (pcops_get_option(PCOPS_OPT_POOL_TOP_ROWS_PIPELINED) != 0) {
-        if (Kp == 64 && S <= 64) PCOPS_WSPP_LAUNCH(64, 4);
-        else if (Kp == 64) PCOPS_WSPP_LAUNCH(64, 8);
-        else if (S <= 64) PCOPS_WSPP_LAUNCH(128, 8);
-        else PCOPS_WSPP_LAUNCH(128, 16);
-    } else if (Kp == 64) PCOPS_WSPR_LAUNCH(64);
-    else PCOPS_WSPR_LAUNCH(128);
-#undef PCOPS_WSPP_LAUNCH
-#undef PCOPS_WSPR_LAUNCH
-    int rc = pcops_launch_status();
+    const bool piped = pcops_get_option(PCOPS_OPT_POOL_TOP_ROWS_PIPELINED) != 0;
+    const int rc = pcops_dispatch<64, 128>(Kp, PCOPS_ERR_UNSUPPORTED, [&](auto kp_) {
+        constexpr int KP = decltype(kp_)::value;
+        auto kern = !piped ? pool_top_wsparse_rows_kernel<KP>
+                  : S <= 64 ? pool_top_wsparse_rows_pipe_kernel<KP, KP / 16> : pool_top_wsparse_rows_pipe_kernel<KP, KP / 8>;
+        return pcops_launch_lds(kern, dim3(grid), dim3(256), piped ? lds_pipe : lds, 160 * 1024, st, G, N, S, gout, ysel, argmax,
+                                pool_scale, pool_shift, p, Yprev, prev_scale, prev_shift, rows->block_start, partial, part2);
+    });
     if (rc) return rc;
     const long long L = (long long)Kp * N;
     hipLaunchKernelGGL(sum_partials2_kernel, dim3(cdiv(L, 64) + cdiv(N, 64)), dim3(1024), 0, st, grid, L, partial, Ssp,
@@ -6813,7 +6673,7 @@ int pcops_mlp_gemm_dgrad_top_rows(int M, int Kp, const float *Yprev, const float
     a.stats = stats_partial; a.addend = addend; a.rowmap = rowmap; a.add_ld = Kp; a.vconst = vconst;
     a.add_bytes = addend_rows * Kp * 4;
     if (addend_rows < 1 || a.add_bytes >= (long long)kOOB) return PCOPS_ERR_UNSUPPORTED;
-    PCOPS_ROWS(a, rows);
+    if (const int rc = set_rows(a, rows)) return rc;
     if (!prev_scale) {      // X is the stack's raw input: plain dX, no mask, no statistics
         a.stats = nullptr;
         return launch_gemm_ws_only<A_PLAIN, E_PLAINA>(a, as_stream(stream));
@@ -6839,16 +6699,10 @@ int pcops_mlp_gram_rows(long long M, int Kp, const float *Yprev, int ldx, const 
     // PCOPS_OPT_GRAM_SPLIT_BF16 = 1 (default): Kp = 128 on the bf16 matrix pipe with split operands (gram_rows_bf3_kernel); Kp = 64
     // keeps the fp32 kernel under either value (two blocks a side: three upper blocks over four waves, nothing to deal better)
     const bool bf3 = Kp == 128 && pcops_get_option(PCOPS_OPT_GRAM_SPLIT_BF16) != 0;
-    const int rcl = bf3 ? gram_rows_bf3_launch(g, gg, st) : gram_full_rows_launch(g, nbk, gg, lds, st);
-    if (rcl) return rcl;
-    if (bf3) pcops_note_pipe(1);
-    int rc = pcops_launch_status();
+    const int rc = bf3 ? gram_rows_bf3_launch(g, gg, st) : gram_full_rows_launch(g, nbk, gg, lds, st);
     if (rc) return rc;
-    const long long L = (long long)Kp * Kp;
-    hipLaunchKernelGGL(sum_partials2_kernel, dim3(cdiv(L, 64) + (xsum ? cdiv(Kp, 64) : 0)), dim3(1024), 0, st, gg, L,
-                       partial, gram, (long long)Kp, g.xpart, xsum);
-    hipLaunchKernelGGL(mirror_lower_kernel, dim3(Kp), dim3(256), 0, st, Kp, gram);
-    return pcops_launch_status();
+    if (bf3) pcops_note_pipe(1);
+    return gram_finish(g, gg, gram, xsum, st);
 }
 
 int pcops_mlp_dy_apply(long long M, int N, const float *G, const float *Y, const float *p, const float *q, const float *t,

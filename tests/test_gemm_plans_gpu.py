@@ -559,6 +559,75 @@ def test_wgrad(case, opt):
     assert pl == WGRAD_EXPECT[case[0]][opt], (case[0], opt, pl)
 
 
+# One case per arm of the weight-gradient dispatch (wgrad_launch: family x tile x operand mode x resolved dY mode) that takes
+# uncompacted rows and a read operand and that no other test of the suite launches, at the smallest rows the planners admit
+# (8 192 for the producer/consumer plan, 32 768 for the split-operand plan), widths from {64, 96, 128, 320}, groups of 32
+# (whole tiles) and 20 rows.  Names: pc<tk><tn> the producer/consumer tile (k96: its 96 x 32 consumer layout), bf3 the
+# split-operand kernel (which takes a shape under option 1 only: under option 0 the case runs the kernel of its first tuple).
+# (name, M, K, N, ldx, prologue, S)
+WGRAD_ARM_CASES = [
+    ("pc11_plain_s32", 8192, 64, 64, 64, False, 32),
+    ("pc11_plain_s20", 8200, 64, 64, 64, False, 20),
+    ("pc12_plain_s32", 8192, 64, 128, 64, False, 32),
+    ("pc14_bn_s32", 8192, 64, 320, 64, True, 32),
+    ("pc14_bn_s20", 8200, 64, 320, 64, True, 20),
+    ("pc14_plain_s32", 8192, 64, 320, 64, False, 32),
+    ("pc14_plain_s20", 8200, 64, 320, 64, False, 20),
+    ("pc21_bn_s20", 8200, 128, 64, 128, True, 20),
+    ("pc21_plain_s32", 8192, 128, 64, 128, False, 32),
+    ("pc21_plain_s20", 8200, 128, 64, 128, False, 20),
+    ("pc22k96_bn_s32", 8192, 96, 128, 96, True, 32),
+    ("pc22k96_bn_s20", 8200, 96, 128, 96, True, 20),
+    ("pc22k96_plain_s32", 8192, 96, 128, 96, False, 32),
+    ("pc22k96_plain_s20", 8200, 96, 128, 96, False, 20),
+    ("pc22_bn_s20", 8200, 128, 128, 128, True, 20),
+    ("pc22_plain_s32", 8192, 128, 128, 128, False, 32),
+    ("pc22_plain_s20", 8200, 128, 128, 128, False, 20),
+    ("pc24_bn_s32", 8192, 128, 320, 128, True, 32),
+    ("pc24_bn_s20", 8200, 128, 320, 128, True, 20),
+    ("pc24_plain_s20", 8200, 128, 320, 128, False, 20),
+    ("pc14_bn_dy", 8192, 64, 320, 64, True, 0),
+    ("bf3_plain_s32", 32768, 128, 128, 128, False, 32),
+    ("bf3_plain_s16", 32768, 128, 128, 128, False, 16),
+]
+WGRAD_ARM_EXPECT = {
+    "pc11_plain_s32": [(5, 0, 64, 0, 1), (5, 0, 64, 0, 1)],
+    "pc11_plain_s20": [(5, 0, 64, 0, 2), (5, 0, 64, 0, 2)],
+    "pc12_plain_s32": [(5, 0, 128, 0, 1), (5, 0, 128, 0, 1)],
+    "pc14_bn_s32": [(5, 0, 256, 0, 1), (5, 0, 256, 0, 1)],
+    "pc14_bn_s20": [(5, 0, 256, 0, 2), (5, 0, 256, 0, 2)],
+    "pc14_plain_s32": [(5, 0, 256, 0, 1), (5, 0, 256, 0, 1)],
+    "pc14_plain_s20": [(5, 0, 256, 0, 2), (5, 0, 256, 0, 2)],
+    "pc21_bn_s20": [(5, 0, 64, 0, 2), (5, 0, 64, 0, 2)],
+    "pc21_plain_s32": [(5, 0, 64, 0, 1), (5, 0, 64, 0, 1)],
+    "pc21_plain_s20": [(5, 0, 64, 0, 2), (5, 0, 64, 0, 2)],
+    "pc22k96_bn_s32": [(5, 0, 128, 0, 1), (5, 0, 128, 0, 1)],
+    "pc22k96_bn_s20": [(5, 0, 128, 0, 2), (5, 0, 128, 0, 2)],
+    "pc22k96_plain_s32": [(5, 0, 128, 0, 1), (5, 0, 128, 0, 1)],
+    "pc22k96_plain_s20": [(5, 0, 128, 0, 2), (5, 0, 128, 0, 2)],
+    "pc22_bn_s20": [(5, 0, 128, 0, 2), (5, 0, 128, 0, 2)],
+    "pc22_plain_s32": [(5, 0, 128, 0, 1), (5, 0, 128, 0, 1)],
+    "pc22_plain_s20": [(5, 0, 128, 0, 2), (5, 0, 128, 0, 2)],
+    "pc24_bn_s32": [(5, 0, 256, 0, 1), (5, 0, 256, 0, 1)],
+    "pc24_bn_s20": [(5, 0, 256, 0, 2), (5, 0, 256, 0, 2)],
+    "pc24_plain_s20": [(5, 0, 256, 0, 2), (5, 0, 256, 0, 2)],
+    "pc14_bn_dy": [(5, 0, 256, 0, 0), (5, 0, 256, 0, 0)],
+    "bf3_plain_s32": [(5, 0, 128, 0, 1), (4, 1, 128, 0, 1)],
+    "bf3_plain_s16": [(5, 0, 128, 0, 2), (4, 1, 128, 0, 2)],
+}
+
+
+# (the option decides nothing below 32 768 rows: those cases run under its default only)
+WGRAD_ARM_RUNS = [(c, o) for c in WGRAD_ARM_CASES for o in ((0, 1) if c[1] >= 32768 else (1,))]
+
+
+@pytest.mark.parametrize("case,opt", WGRAD_ARM_RUNS, ids=["%s-%d" % (c[0], o) for c, o in WGRAD_ARM_RUNS])
+def test_wgrad_arms(case, opt):
+    pl = _wgrad_run(case, opt)
+    OBSERVED["wgrad"].add(pl)
+    assert pl == WGRAD_ARM_EXPECT[case[0]][opt], (case[0], opt, pl)
+
+
 # ------------------------------------------------------------------------ one-pass backward: the queries and the launchers
 # Each launcher of the family has a query; where the query answers > 0 the launcher must take the shape and compute what
 # the two-kernel path computes, where it answers 0 the launcher must refuse and write nothing.  (Before the edge forms had
@@ -792,6 +861,7 @@ EXPECT_VARIANTS = {
     "wgrad": [
         (4, 1, 128, 0, 0), (4, 1, 128, 0, 1), (5, 0, 64, 0, 2), (5, 0, 128, 0, 1), (5, 0, 128, 0, 2),
         (5, 0, 256, 0, 0), (6, 0, 64, 0, 0), (6, 0, 128, 0, 0), (7, 0, 128, 0, 0), (7, 0, 128, 0, 2),
+        (4, 1, 128, 0, 2), (5, 0, 64, 0, 1), (5, 0, 256, 0, 1), (5, 0, 256, 0, 2),          # test_wgrad_arms
     ],
     "bwd_fused": [
         (3, 0, 64, 0, 0), (3, 0, 64, 0, 1), (3, 0, 64, 0, 2), (3, 0, 128, 0, 0), (3, 0, 128, 0, 1), (3, 0, 128, 0, 2),
