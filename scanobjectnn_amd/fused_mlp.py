@@ -14,8 +14,20 @@ Two kinds of first layer:
   gather  Y1[b,j,s,:] = Q[b, idx[b,j,s], :] + Ctr[b,j,:] + (xyz[b,idx] - new_xyz[b,j]) Wxyz + bias -- the first conv
           of a GROUPED stack applied before the grouping (it is linear; see csrc/gather.hip), so neither the
           grouped input nor a (3+C)-wide concat is ever built and its backward is one scatter-add.
+
+Plan, then launch.  `plan_stack` takes every decision of a stack ONCE, before the first launch and without side effects,
+from the shapes, the operands present, SyncBN state, the weights' alignment, the module flags below and the library's
+shape queries: a `StackPlan` (arithmetic first layer? compacted rows kept? edge rows stored?) with one `LayerPlan` per
+layer (forward arm, Y stored?, pooled form, backward arm, the group / split count its launches need).
+`FusedMLPStack.forward` stores it on the node and both passes are loops over it that call one short function per arm;
+`backward` asks the library nothing but buffer sizes, probes nothing and reads no flag -- the forward form and the
+backward form of a layer are one decision.  The backward arms are planned only when a backward can happen.
+Contract: the module flags (read at call time, in forward) and the library's options do not change between a stack's
+forward and its backward.
 """
 import os
+from collections import namedtuple
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 
@@ -55,6 +67,192 @@ def _p(t):
     return t.data_ptr() if t is not None else None
 
 
+# ---------------------------------------------------------------------------------------------------- the stack plan
+# forward arms of a layer: the three gather first layers ([Q | Ctr] product, whole clouds + per-cloud term, generic) and
+# the products (on the arithmetic first layer, compacted rows with / without the pooled epilogue, pooled epilogue, plain)
+F_QC, F_CLOUD, F_GATHER, F_XYZ, F_POOL_ROWS, F_ROWS, F_POOL, F_GEMM = (
+    "qc", "cloud_bias", "gather", "xyz", "pool_rows", "rows", "pool", "gemm")
+# backward arms of a layer.  First layer of a gather stack: arithmetic, direct edge, [Q | Ctr] scatter, cloud-bias,
+# generic scatter (with the identity shortcut where the scatter is a reshape).  Products: algebraic top layer, one pass
+# for both gradients in its five forms, separate weight + data gradient (below it a stored / the arithmetic layer)
+B_XYZ_FIRST, B_EDGE_FIRST, B_QC, B_CLOUD, B_SCATTER, B_SCATTER_ID = (
+    "xyz_first", "edge_first", "qc_scatter", "cloud_bias", "scatter", "scatter_identity")
+B_TOP, B_SPLIT, B_SPLIT_XYZ = "top", "split", "split_xyz"
+B_ONEPASS, B_ONEPASS_XYZ, B_ONEPASS_GW, B_ONEPASS_EDGE, B_ONEPASS_EDGE_GW = (
+    "onepass", "onepass_xyz", "onepass_gw", "onepass_edge", "onepass_edge_gw")
+_ONEPASS = (B_ONEPASS, B_ONEPASS_XYZ, B_ONEPASS_GW, B_ONEPASS_EDGE, B_ONEPASS_EDGE_GW)
+# the arms that read the layer's own stored Y / the Y of the layer below
+_READS_Y = (B_CLOUD, B_SCATTER, B_SCATTER_ID, B_SPLIT, B_SPLIT_XYZ) + _ONEPASS
+_READS_Y_BELOW = (B_TOP, B_SPLIT, B_ONEPASS, B_ONEPASS_GW, B_ONEPASS_EDGE, B_ONEPASS_EDGE_GW)
+
+
+class LayerPlan(NamedTuple):
+    fwd: str            # forward arm (F_*)
+    K: Optional[int]    # input width (None: gather first layer)
+    N: int
+    store_y: bool       # the forward stores the layer's raw output
+    pooled: str         # pooled epilogue fused into the forward product: "" | "raw" (plain rows) | "rows" (per 16-row block)
+    bwd: str            # backward arm (B_*); "" where no backward can happen
+    count: int          # what the arm's launches are sized by: one-pass groups / weight-gradient splits
+
+
+class StackPlan(NamedTuple):
+    """every decision of one FusedMLPStack, taken once by plan_stack() before the first launch"""
+    virt: bool          # arithmetic first layer: never stored, rebuilt from three offsets per row
+    rows: bool          # the compacted row set is kept
+    direct: bool        # [Q | Ctr] first layer on an input without gradient (pcops_edge_first_*)
+    edge_rows: bool     # ... whose edge rows the forward stores AND the one-pass backward of the layer above reduces
+    need_dx: bool       # the stack's input takes a gradient
+    tail_fold: bool     # TAIL_FOLD as the forward found it
+    layers: Tuple[LayerPlan, ...]
+
+    @property
+    def pool_top(self):
+        return self.layers[-1].bwd == B_TOP
+
+
+def plan_stack(*, R, S, K0, widths, pool, training, need_grad, need_dx, sync, w_aligned, has_b, geom=None, present=(),
+               a0_contiguous=True, rows=False):
+    """The StackPlan of a stack: no side effect, no launch.
+    R rows in groups of S; K0: width of a dense input; pool: the bits of FusedMLPStack.apply; need_grad / need_dx: a
+    backward can happen / reaches the input (the backward arms are only planned for one that can happen); sync: SyncBN;
+    w_aligned[l] / has_b[l]: layer l's weight lies at a 16-byte address / it has a bias;
+    geom = (B, Nsrc, M) of a gather first layer and present: which of "a0", "ctr", "xyz", "wxyz", "bias" it is given;
+    rows: a compacted row set is given.  Reads the module flags and the library's shape queries, here and nowhere later."""
+    lib = _lib.load()
+    L, C1 = len(widths), widths[0]
+    identity, qc, direct, pool = bool(pool & 2), bool(pool & 4), bool(pool & 8), bool(pool & 1)
+    gather = geom is not None
+    direct = gather and qc and direct
+    # a first layer with only the coordinate term is ARITHMETIC in three offsets per row: it is never stored, the
+    # next layer and the whole backward rebuild it from off4 (16 bytes per row instead of 4 C1)
+    # (with SyncBN, or a backward through eval-mode BN, the layer is materialised: its gradient shortcut assumes
+    # rank-local batch statistics)
+    virt = (gather and "a0" not in present and "ctr" not in present and "wxyz" in present
+            and (L >= 3 or (L == 2 and not pool)) and not sync and (training or not need_grad)
+            and bool(lib.pcops_mlp_xyz_supported(R, C1, widths[1])))
+    # (a stored coordinate-only first layer has no compacted backward: plain rows)
+    rows = rows and not (gather and "a0" not in present and not virt)
+    edge_rows = False
+    layers = []
+    for l, N in enumerate(widths):
+        K = widths[l - 1] if l else K0
+        top = pool and l == L - 1
+        store_y, pooled, bwd, count = True, "", "", 0
+        # the layer's one-pass backward (the bandwidth-bound narrow layers: data and weight gradient in ONE pass over
+        # Y / Yprev): what the shape allows, and what this weight's address allows
+        onepass = int(need_grad and BWD_FUSED and l > 0 and lib.pcops_mlp_bwd_fused_groups(R, K, N, S if top else 0, int(top)))
+        if l == 0 and gather:
+            B, Nsrc, M = geom
+            if qc:
+                fwd = F_QC
+            elif (identity and CLOUD_BIAS and set(present) == {"a0", "ctr"} and not rows and M == 1 and Nsrc == S
+                    and a0_contiguous and lib.pcops_cloud_bias_supported(R, S, C1)):
+                fwd = F_CLOUD       # whole clouds in their own order: Y = Q + Ctr[cloud] as one streaming pass
+            else:
+                fwd, store_y = F_GATHER, not virt
+            if need_grad:
+                shortcut = "a0" in present and need_dx and identity and not top     # idx = 0..n-1: dQ = dY row for row
+                bwd = (B_XYZ_FIRST if virt else B_EDGE_FIRST if direct else B_QC if qc
+                       else B_CLOUD if (fwd == F_CLOUD and not top) else B_SCATTER_ID if shortcut else B_SCATTER)
+        else:
+            xyz_prev = virt and l == 1          # the layer below is the arithmetic first layer
+            algebraic = False                   # pcops.h "algebraic backward of a pooled top layer": never reads Y
+            if xyz_prev:
+                fwd = F_XYZ
+            elif rows and top and l > 0 and FUSE_POOL_ROWS and lib.pcops_mlp_gemm_fwd_pool_rows_supported(R, K, N):
+                # compacted rows: the epilogue emits the extremum of every 16-row block, a small pass picks per group
+                # (the narrow layers the one-pass backward takes stay there: it reads Y once for both gradients)
+                fwd, pooled = F_POOL_ROWS, "rows"
+                algebraic = bool(need_grad and POOL_TOP and POOL_TOP_ROWS and S >= 64 and N >= 2 * K and has_b[l]
+                                 and not onepass and lib.pcops_mlp_pool_top_rows_supported(R, K, N, S))
+                store_y = not algebraic
+            elif rows:
+                fwd = F_ROWS
+            elif top and lib.pcops_mlp_gemm_fwd_pool_supported(R, K, N, S):
+                # neighbourhood max fused into the GEMM epilogue.  The activation itself is only stored when a backward
+                # will read it: not for a forward without gradient, not when the layer takes the algebraic backward
+                fwd, pooled = F_POOL, "raw"
+                algebraic = bool(need_grad and POOL_TOP and S >= 64 and N >= 2 * K and has_b[l]
+                                 and lib.pcops_mlp_pool_top_supported(R, K, N, S))
+                store_y = need_grad and not algebraic
+            else:
+                fwd = F_GEMM
+            if algebraic:
+                bwd, count = B_TOP, lib.pcops_mlp_wgrad_splits(R, K, K)
+            elif onepass and w_aligned[l]:
+                use_edge = (direct and top and l == 1 and EDGE_DIRECT_FUSED
+                            and lib.pcops_mlp_bwd_fused_edge_groups(R, K, N, S, 0) == onepass)
+                # pooled layer on uncompacted rows: the weight gradient in its Gram form (pcops.h, round 6).  The query
+                # asked is the one of the launcher that runs: the edge forms take fewer group sizes (S % 32 != 0)
+                gw = (top and not rows and not xyz_prev and
+                      (lib.pcops_mlp_bwd_fused_edge_groups(R, K, N, S, 1) if use_edge
+                       else lib.pcops_mlp_bwd_fused_gw_groups(R, K, N, S)) == onepass)
+                edge_rows = edge_rows or use_edge
+                bwd = ((B_ONEPASS_EDGE_GW if gw else B_ONEPASS_EDGE) if use_edge else B_ONEPASS_GW if gw
+                       else B_ONEPASS_XYZ if xyz_prev else B_ONEPASS)
+                count = onepass
+            elif need_grad:
+                bwd, count = (B_SPLIT_XYZ if xyz_prev else B_SPLIT), lib.pcops_mlp_wgrad_splits(R, K, N)
+        layers.append(LayerPlan(fwd, K, N, bool(store_y), pooled, bwd, int(count)))
+    for l, lp in enumerate(layers):     # an arm that reads layer l's Y exists only where the forward stores it
+        reads = (lp.bwd in _READS_Y or (l + 1 < L and layers[l + 1].bwd in _READS_Y_BELOW)
+                 or (need_grad and not pool and l == L - 1))
+        assert lp.store_y or not reads, (l, layers)
+    return StackPlan(bool(virt), bool(rows), direct, bool(edge_rows), bool(need_dx), TAIL_FOLD, tuple(layers))
+
+
+# what a FusedMLPStack node keeps for its backward (tests/mlp_ref.py and tests/decisions.py read it too)
+StackSaved = namedtuple("StackSaved", "a0 ctr idx xyz new_xyz wxyz bias Ys means rstds scales shifts Ws gammas argmax ysel "
+                                      "off4 xyzw mom")
+
+
+def _bn_forward(bn, N, R, P, part, piv, *, training, sync, need_grad, hyper, vecs, ws):
+    """(scale, shift, mean, rstd) of one BatchNorm from the statistics partials of its producer: finalize (with the
+    SyncBN exchange) in training, the moving statistics' coefficients otherwise.  bn = (gamma, beta, moving mean, moving
+    variance), hyper = (eps, decay, unbiased moving variance)"""
+    (gamma, beta, mm, mv), (eps, decay, unbiased) = bn, hyper
+    scale, shift = vecs.take(N), vecs.take(N)
+    mean = rstd = None
+    if training:
+        mean, rstd = vecs.take(N), vecs.take(N)
+        Pf, Rf, piv_fin = P, R, piv
+        if sync:        # SyncBN: the statistics of the global batch (the rank's pivot taken out before the exchange)
+            part, Rf = _dist.allreduce_stat_partials(part, R, mm if piv is not None else None)
+            Pf, piv_fin = part.shape[0], None
+        _lib.call("pcops_mlp_bn_finalize", Pf, N, Rf, part.data_ptr(), piv_fin, ws.data_ptr(), gamma.data_ptr(),
+                  beta.data_ptr(), float(eps), float(decay), int(unbiased), mm.data_ptr(), mv.data_ptr(),
+                  mean.data_ptr(), rstd.data_ptr(), scale.data_ptr(), shift.data_ptr())
+    else:
+        _lib.call("pcops_mlp_bn_eval_coeffs", N, gamma.data_ptr(), beta.data_ptr(), mm.data_ptr(),
+                  mv.data_ptr(), float(eps), scale.data_ptr(), shift.data_ptr())
+        if need_grad:   # backward through frozen statistics: y_bn = scale*y + shift with constants
+            mean, rstd = mm.detach().clone(), torch.rsqrt(mv.detach() + float(eps))
+    return scale, shift, mean, rstd
+
+
+def _bn_backward(N, R, P, part, gamma, mean, rstd, *, training, sync, vecs, ws):
+    """(dgamma, dbeta, p, q, t) of one BatchNorm from the statistics partials of the masked gradient: dY = p G + q Y + t"""
+    dev = part.device
+    dgamma, dbeta = _f32(N, dev), _f32(N, dev)
+    p, q, t = vecs.take(N), vecs.take(N), vecs.take(N)
+    _lib.call("pcops_mlp_bn_bwd_coeffs", P, N, R, part.data_ptr(), ws.data_ptr(), gamma.data_ptr(),
+              mean.data_ptr(), rstd.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(),
+              p.data_ptr(), q.data_ptr(), t.data_ptr())
+    if sync:
+        # SyncBN: dgamma / dbeta stay rank-local sums (the gradient all-reduce adds the ranks up); the
+        # dY = p G + q Y + t coefficients come from the sums over the GLOBAL batch
+        gpart, Rg = _dist.allreduce_stat_partials(part, R)
+        junk = _f32(2 * N, dev)
+        _lib.call("pcops_mlp_bn_bwd_coeffs", gpart.shape[0], N, Rg, gpart.data_ptr(), ws.data_ptr(), gamma.data_ptr(),
+                  mean.data_ptr(), rstd.data_ptr(), junk.data_ptr(), junk[N:].data_ptr(),
+                  p.data_ptr(), q.data_ptr(), t.data_ptr())
+    if not training:    # frozen statistics: no mean / variance terms in the BN backward
+        q.zero_()
+        t.zero_()
+    return dgamma, dbeta, p, q, t
+
+
 class FusedMLPStack(torch.autograd.Function):
     """apply(a0, ctr, idx, xyz, new_xyz, wxyz, bias, S, pool, training, decay, eps, unbiased_moving_var, rows, L, *per_layer)
 
@@ -63,497 +261,488 @@ class FusedMLPStack(torch.autograd.Function):
     dense first layer : a0 = x2d (R, K0); ctr .. bias = None
     gather first layer: idx (B, M, S) int32 and any of a0 = Q (B, N, C1), ctr (B, M, C1),
                         xyz (B, N, 3) + new_xyz (B, M, 3) + wxyz (3, C1), bias (C1);  R = B*M*S
+    pool: bit 0 the max over the groups; bit 1 a gather stack whose idx is 0..n-1 per cloud (group_all: scatter = reshape);
+          bit 2 a0 is the (B, N, 2 C1) product [Q | Ctr] of ONE GEMM (pcops.h "[Q | Ctr] forms"); bit 3 with bit 2, an
+          input that needs no gradient (DGCNN's T-Net on the raw cloud): xyz = the (B, N, 3) input, wxyz = the layer's
+          (6, C1) weight, bias = its bias -- their gradients come from ONE streaming pass over the masked gradient
+          (pcops.h pcops_edge_first_*), a0 gets none and no scatter runs
     per_layer (6 each): weights (K,N), biases (N), gamma, beta, moving_mean, moving_var -- the first two are None
     for a gather first layer.  Returns (R//S, C_L) if pool else (R, C_L)."""
 
     @staticmethod
     def forward(ctx, a0, ctr, idx, xyz, new_xyz, wxyz, bias, S, pool, training, decay, eps, unbiased, rows, L, *tensors):
-        lib = _lib.load()
-        rref = rows.ref if rows is not None else None
-        identity = bool(int(pool) & 2)      # gather stack whose idx is 0..n-1 per cloud (group_all): scatter = reshape
-        qc = bool(int(pool) & 4)            # a0 is the (B, N, 2 C1) product [Q | Ctr] of ONE GEMM (pcops.h "[Q | Ctr] forms")
-        # qc with an input that needs no gradient (DGCNN's T-Net on the raw cloud): xyz = the (B, N, 3) input, wxyz = the
-        # layer's (6, C1) weight, bias = its bias -- their gradients come from ONE streaming pass over the masked gradient
-        # (pcops.h pcops_edge_first_*), a0 gets none and no scatter runs
-        direct = bool(int(pool) & 8)
-        pool = bool(int(pool) & 1)
         gather = idx is not None
         need_grad = any(ctx.needs_input_grad)
         sync = training and _dist.sync_bn_active()
         dev = idx.device if gather else a0.device
         layers = [tensors[6 * i:6 * i + 6] for i in range(L)]
+        widths = [l[2].shape[0] for l in layers]
+        Ws = [w.detach().reshape(-1, w.shape[-1]) if w is not None else None for w, *_ in layers]
+        geom = K0 = None
         if gather:
             B, M, _ = idx.shape
-            Nsrc = a0.shape[1] if a0 is not None else xyz.shape[1]
-            C1 = layers[0][2].shape[0]
-            R, K0 = B * M * S, None
-            if qc:
-                assert ctr is None and rows is None and M == Nsrc and new_xyz is None
-                assert direct or (xyz is None and wxyz is None and bias is None)
-                assert not direct or (xyz is not None and wxyz is not None and tuple(wxyz.shape) == (6, C1) and L >= 2
-                                      and not ctx.needs_input_grad[0])
-                assert a0.shape[2] == 2 * C1 and a0.is_contiguous()
+            geom = (B, a0.shape[1] if a0 is not None else xyz.shape[1], M)
+            R = B * M * S
         else:
             R, K0 = a0.shape
-        Ys, means, rstds, scales, shifts, Ws = [], [], [], [], [], []
-        src, ld, sc_prev, sh_prev, K = a0, K0, None, None, K0
-        vecs = _VecArena([l[2].shape[0] for l in layers], 4, dev)
-        ws = _workspace(max(l[2].shape[0] for l in layers), dev) if training else None
-        pooled_raw = pooled_parts = None
-        pool_top = False          # the pooled top layer takes the algebraic backward: decided ONCE, here (the forward
-        #                           drops Y on that decision, so the backward must not come to a different one)
-        # a first layer with only the coordinate term is ARITHMETIC in three offsets per row: it is never stored, the
-        # next layer and the whole backward rebuild it from off4 (16 bytes per row instead of 4 C1)
-        # (with SyncBN, or a backward through eval-mode BN, the layer is materialised: its gradient shortcut assumes
-        # rank-local batch statistics)
-        virt = (gather and a0 is None and ctr is None and wxyz is not None and (L >= 3 or (L == 2 and not pool))
-                and not sync and (training or not need_grad)
-                and bool(lib.pcops_mlp_xyz_supported(R, C1, layers[1][0].shape[-1])))
-        if rows is not None and gather and a0 is None and not virt:
-            rows = rref = None          # a stored coordinate-only first layer has no compacted backward: plain rows
-        off4 = xyzw = mom = None
-        if virt:
-            off4 = _f32((R, 4), dev)
-            mom = _f32((lib.pcops_sa_gather_stats_rows(B * M), 9), dev) if training else None
-            xyzw = torch.cat([wxyz.detach(), (bias.detach() if bias is not None
-                                              else torch.zeros(C1, dtype=torch.float32, device=dev)).view(1, C1)]).contiguous()
-        for li, (w, b, gamma, beta, mm, mv) in enumerate(layers):
+        operands = (a0, ctr, idx, xyz, new_xyz, wxyz, bias)
+        plan = plan_stack(R=R, S=S, K0=K0, widths=widths, pool=int(pool), training=training, need_grad=need_grad,
+                          need_dx=ctx.needs_input_grad[0], sync=sync,
+                          w_aligned=[W is not None and W.data_ptr() % 16 == 0 for W in Ws],
+                          has_b=[l[1] is not None for l in layers], geom=geom,
+                          present=[n for n, v in (("a0", a0), ("ctr", ctr), ("xyz", xyz), ("wxyz", wxyz), ("bias", bias))
+                                   if v is not None],
+                          a0_contiguous=a0 is None or a0.is_contiguous(), rows=rows is not None)
+        identity, pool = bool(int(pool) & 2), bool(int(pool) & 1)
+        if plan.layers[0].fwd == F_QC:
+            C1 = widths[0]
+            assert ctr is None and rows is None and M == geom[1] and new_xyz is None
+            assert plan.direct or (xyz is None and wxyz is None and bias is None)
+            assert not plan.direct or (xyz is not None and wxyz is not None and tuple(wxyz.shape) == (6, C1) and L >= 2
+                                       and not ctx.needs_input_grad[0])
+            assert a0.shape[2] == 2 * C1 and a0.is_contiguous()
+        if not plan.rows:
+            rows = None
+        up = _Up(operands, geom, S, R, dev, training, rows)
+        if plan.virt:
+            up.off4 = _f32((R, 4), dev)
+            up.mom = _f32((_lib.load().pcops_sa_gather_stats_rows(geom[0] * geom[2]), 9), dev) if training else None
+            b0 = bias.detach() if bias is not None else torch.zeros(widths[0], dtype=torch.float32, device=dev)
+            up.xyzw = torch.cat([wxyz.detach(), b0.view(1, -1)]).contiguous()
+        Ys, means, rstds, scales, shifts = [], [], [], [], []
+        vecs = _VecArena(widths, 4, dev)
+        ws = _workspace(max(widths), dev) if training else None
+        pooled_bufs = None
+        for li, lp in enumerate(plan.layers):
+            w, b, gamma, beta, mm, mv = layers[li]
             # forward statistics are shifted moments around the layer's moving mean (pcops.h pcops_mlp_gemm_fwd): the
             # producer and pcops_mlp_bn_finalize get the same pivot; finalize reads it before it updates the buffer
             piv = mm.data_ptr() if (training and STAT_PIVOT) else None
-            if li == 0 and gather and qc:
-                N = C1
-                Y = _f32((R, N), dev)
-                P = lib.pcops_sa_gather_fwd_stats_rows(B, Nsrc, M, S, N, 1, 1, 0, 0)
-                part = _f32((P, 2, N), dev) if training else None
-                _lib.call("pcops_sa_gather_fwd_ld", B, Nsrc, M, S, N, a0.data_ptr(), 2 * N, a0.data_ptr() + 4 * N, 2 * N,
-                          idx.data_ptr(), Y.data_ptr(), _p(part), piv)
-                if direct and need_grad:      # the 27 moments of the edge features, for E^T Y1 in the backward
-                    mom = _f32((lib.pcops_edge_first_rows(), 27), dev)
-                    # ... and, where the layer above takes the one-pass backward, the edge rows themselves (32 bytes each):
-                    # E^T Gm is then reduced inside that kernel and the masked gradient is never written
-                    N1 = layers[1][0].shape[-1]
-                    if (EDGE_DIRECT_FUSED and BWD_FUSED and L == 2 and pool
-                            and lib.pcops_mlp_bwd_fused_edge_groups(R, N, N1, S, 0)):
-                        ctx.edge_rows = _f32((R, 8), dev)
-                    _lib.call("pcops_edge_first_moments", B, Nsrc, M, S, xyz.data_ptr(), idx.data_ptr(), mom.data_ptr(),
-                              _p(getattr(ctx, "edge_rows", None)))
-                W2 = None
-            elif (li == 0 and gather and identity and CLOUD_BIAS and a0 is not None and ctr is not None and xyz is None
-                    and wxyz is None and bias is None and rows is None and M == 1 and Nsrc == S and a0.is_contiguous()
-                    and lib.pcops_cloud_bias_supported(R, S, C1)):
-                # whole clouds in their own order: Y = Q + Ctr[cloud] as one streaming pass (pcops.h pcops_cloud_bias_*)
-                N = C1
-                Y = _f32((R, N), dev)
-                P = lib.pcops_cloud_bias_rows(R)
-                part = _f32((P, 2, N), dev) if training else None
-                _lib.call("pcops_cloud_bias_fwd", R, S, N, a0.data_ptr(), ctr.data_ptr(), Y.data_ptr(), _p(part), piv)
-                W2 = None
-                ctx.cloud_bias = True
-            elif li == 0 and gather:
-                N = C1
-                Y = None if virt else _f32((R, N), dev)
-                other = wxyz is not None or bias is not None or off4 is not None
-                P = lib.pcops_sa_gather_fwd_stats_rows(B, Nsrc, M, S, N, int(a0 is not None), int(ctr is not None),
-                                                        int(other), int(rref is not None))
-                part = _f32((P, 2, N), dev) if training else None
-                _lib.call("pcops_sa_gather_fwd_rows", B, Nsrc, M, S, N, _p(a0), _p(ctr), _p(xyz), _p(new_xyz),
-                          _p(wxyz), _p(bias), idx.data_ptr(), _p(Y), _p(off4), _p(part), piv, _p(mom), rref)
-                W2 = None
+            Y = _f32((R, lp.N), dev) if lp.store_y else None
+            if lp.K is None:
+                P, part = _fwd_first(up, lp, Y, piv)
+                if plan.direct and need_grad:
+                    _fwd_edge_moments(up, plan.edge_rows)
             else:
-                N = w.shape[-1]
-                W2 = w.detach().reshape(-1, N)
-                assert W2.shape[0] == K and W2.is_contiguous()
-                pool_rows = (rows is not None and pool and li == L - 1 and sc_prev is not None and ld == K
-                             and not (li == 1 and virt) and FUSE_POOL_ROWS
-                             and bool(lib.pcops_mlp_gemm_fwd_pool_rows_supported(R, K, N)))
-                if pool_rows:
-                    # the algebraic backward over compacted rows never reads the activation: it is not stored (nor allocated)
-                    pool_top = need_grad and _pool_top_ok(lib, R, K, N, S, li, gather, K0, rows, False, b is not None)
-                Y = None if (pool_rows and pool_top) else _f32((R, N), dev)
-                P = lib.pcops_mlp_stats_rows(R)
-                part = _f32((P, 2, N), dev) if training else None
-                if li == 1 and virt:
-                    _lib.call("pcops_mlp_gemm_fwd_xyz_rows", R, K, N, off4.data_ptr(), xyzw.data_ptr(), sc_prev.data_ptr(),
-                              sh_prev.data_ptr(), W2.data_ptr(), b.data_ptr(), Y.data_ptr(), _p(part), piv, rref)
-                elif pool_rows:
-                    # compacted rows: the epilogue emits the extremum of every 16-row block (a block lies inside one
-                    # group), a small pass picks per group afterwards
-                    nbk = rows.blocks.shape[0]
-                    pooled_parts = (_f32((nbk, N), dev), torch.empty((nbk, N), dtype=torch.uint8, device=dev))
-                    _lib.call("pcops_mlp_gemm_fwd_pool_rows", R, K, N, src.data_ptr(), ld, sc_prev.data_ptr(),
-                              sh_prev.data_ptr(), W2.data_ptr(), b.data_ptr(), gamma.data_ptr(), _p(Y),
-                              _p(part), piv, pooled_parts[0].data_ptr(), pooled_parts[1].data_ptr(), rref)
-                elif rows is not None:
-                    # compacted rows without the fused epilogue: the max over the groups is its own pass below
-                    _lib.call("pcops_mlp_gemm_fwd_rows", R, K, N, src.data_ptr(), ld, _p(sc_prev), _p(sh_prev),
-                              W2.data_ptr(), b.data_ptr(), Y.data_ptr(), _p(part), piv, rref)
-                elif (pool and li == L - 1 and ld == K and lib.pcops_mlp_gemm_fwd_pool_supported(R, K, N, S)
-                        and (sc_prev is not None or li == 0)):
-                    # neighbourhood max fused into the GEMM epilogue (raw extrema; resolved after the statistics).
-                    # The activation itself is only stored when a backward will read it: not for a forward without
-                    # gradient, not when the layer takes the algebraic backward
-                    G = R // S
-                    pooled_raw = (_f32((G, N), dev), torch.empty((G, N), dtype=torch.uint8, device=dev))
-                    pool_top = need_grad and _pool_top_ok(lib, R, K, N, S, li, gather, K0, rows, virt and li == 1,
-                                                          b is not None)
-                    if not need_grad or pool_top:
-                        Y = None
-                    _lib.call("pcops_mlp_gemm_fwd_pool", R, K, N, S, src.data_ptr(), ld, _p(sc_prev),
-                              _p(sh_prev), W2.data_ptr(), b.data_ptr(), gamma.data_ptr(), _p(Y),
-                              _p(part), piv, pooled_raw[0].data_ptr(), pooled_raw[1].data_ptr())
-                else:
-                    _lib.call("pcops_mlp_gemm_fwd", R, K, N, src.data_ptr(), ld, _p(sc_prev), _p(sh_prev),
-                              W2.data_ptr(), b.data_ptr(), Y.data_ptr(), _p(part), piv)
-            scale, shift = vecs.take(N), vecs.take(N)
-            if training:
-                mean, rstd = vecs.take(N), vecs.take(N)
-                Pf, Rf, piv_fin = P, R, piv
-                if sync:        # SyncBN: the statistics of the global batch (the rank's pivot taken out before the exchange)
-                    part, Rf = _dist.allreduce_stat_partials(part, R, mm if piv is not None else None)
-                    Pf, piv_fin = part.shape[0], None
-                _lib.call("pcops_mlp_bn_finalize", Pf, N, Rf, part.data_ptr(), piv_fin, ws.data_ptr(), gamma.data_ptr(),
-                          beta.data_ptr(), float(eps), float(decay), int(unbiased), mm.data_ptr(), mv.data_ptr(),
-                          mean.data_ptr(), rstd.data_ptr(), scale.data_ptr(), shift.data_ptr())
-                means.append(mean)
-                rstds.append(rstd)
-            else:
-                _lib.call("pcops_mlp_bn_eval_coeffs", N, gamma.data_ptr(), beta.data_ptr(), mm.data_ptr(),
-                          mv.data_ptr(), float(eps), scale.data_ptr(), shift.data_ptr())
-                if need_grad:   # backward through frozen statistics: y_bn = scale*y + shift with constants
-                    means.append(mm.detach().clone())
-                    rstds.append(torch.rsqrt(mv.detach() + float(eps)))
-            Ys.append(Y)
-            scales.append(scale)
-            shifts.append(shift)
-            Ws.append(W2)
-            src, ld, sc_prev, sh_prev, K = Y, N, scale, shift, N
-
-        C = K
-        argmax = ysel = None
-        if pool:
-            G = R // S
-            out = _f32((G, C), dev)
-            if pooled_parts is not None:
-                argmax = torch.empty((G, C), dtype=torch.uint8, device=dev)
-                ysel = _f32((G, C), dev)
-                _lib.call("pcops_mlp_pool_combine_rows", G, C, pooled_parts[0].data_ptr(), pooled_parts[1].data_ptr(),
-                          layers[-1][2].data_ptr(), scales[-1].data_ptr(), shifts[-1].data_ptr(), rref,
-                          out.data_ptr(), argmax.data_ptr(), ysel.data_ptr())
-            elif pooled_raw is not None:
-                ysel, argmax = pooled_raw
-                _lib.call("pcops_mlp_pool_select", G, C, ysel.data_ptr(), scales[-1].data_ptr(),
-                          shifts[-1].data_ptr(), out.data_ptr())
-            else:
-                argmax = torch.empty((G, C), dtype=torch.uint8, device=dev) if (training or need_grad) else None
-                ysel = _f32((G, C), dev) if (training or need_grad) else None
-                if rows is not None:
-                    _lib.call("pcops_mlp_bn_relu_maxpool_rows", G, C, Ys[-1].data_ptr(), scales[-1].data_ptr(),
-                              shifts[-1].data_ptr(), rref, out.data_ptr(), _p(argmax), _p(ysel))
-                else:
-                    _lib.call("pcops_mlp_bn_relu_maxpool", G, S, C, Ys[-1].data_ptr(), scales[-1].data_ptr(),
-                              shifts[-1].data_ptr(), out.data_ptr(), _p(argmax), _p(ysel))
-        else:
-            out = _f32((R, C), dev)
-            _lib.call("pcops_mlp_bn_relu_apply", R, C, Ys[-1].data_ptr(), scales[-1].data_ptr(),
-                      shifts[-1].data_ptr(), out.data_ptr())
+                assert Ws[li].shape[0] == lp.K and Ws[li].is_contiguous()
+                prev = (Ys[-1], scales[-1], shifts[-1]) if li else (a0, None, None)
+                P, part, pooled_bufs = _fwd_product(up, lp, Y, piv, prev, Ws[li], b, gamma)
+            scale, shift, mean, rstd = _bn_forward((gamma, beta, mm, mv), lp.N, R, P, part, piv, training=training, sync=sync,
+                                                   need_grad=need_grad, hyper=(eps, decay, unbiased), vecs=vecs, ws=ws)
+            for lst, v in ((Ys, Y), (scales, scale), (shifts, shift), (means, mean), (rstds, rstd)):
+                lst.append(v)
+        out, argmax, ysel = _fwd_output(up, plan.layers[-1], (Ys[-1], scales[-1], shifts[-1]), layers[-1][2], pooled_bufs,
+                                        pool=pool, keep=training or need_grad)
         if training or need_grad:
-            ctx.saved = (a0, ctr, idx, xyz, new_xyz, wxyz, bias, Ys, means, rstds, scales, shifts, Ws,
-                         [l[2] for l in layers], argmax, ysel, off4, xyzw, mom)
+            ctx.saved = StackSaved(a0, ctr, idx, xyz, new_xyz, wxyz, bias, Ys, means, rstds, scales, shifts, Ws,
+                                   [l[2] for l in layers], argmax, ysel, up.off4, up.xyzw, up.mom)
+            ctx.plan = plan
             ctx.biases = [l[1] for l in layers]
+            ctx.edge_rows = up.edge_rows
             ctx.meta = (S, pool, L, R, K0, gather, identity, bool(training), bool(sync))
-            ctx.qc = qc
-            ctx.direct = gather and qc and direct
+            ctx.direct = plan.direct
             ctx.rows = rows
-            ctx.pool_top = pool_top
+            ctx.pool_top = plan.pool_top
             if TRACE is not None:
                 TRACE.append(ctx)
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
-        lib = _lib.load()
-        (a0, ctr, idx, xyz, new_xyz, wxyz, bias, Ys, means, rstds, scales, shifts, Ws, gammas, argmax, ysel, off4,
-         xyzw, mom) = ctx.saved
-        xstats = None
-        virt = off4 is not None
-        widths = [g.shape[0] for g in gammas]
+        sv, plan = ctx.saved, ctx.plan
         S, pool, L, R, K0, gather, identity, training, sync = ctx.meta
-        rows = ctx.rows
-        rref = rows.ref if rows is not None else None
         dev = grad_out.device
-        grad_out = grad_out.contiguous()
-        grads = [None] * (6 * L)
-        d0 = d1 = dwxyz = dbias = None
-
-        # ---- top of the stack: statistics of the masked upstream gradient
-        C = widths[-1]
+        widths = [lp.N for lp in plan.layers]
+        dn = _Down(ctx, grad_out.contiguous())
         ws = _workspace(max(widths), dev)
         vecs = _VecArena(widths, 3, dev)
-        if pool:
-            G = R // S
-            P = lib.pcops_mlp_bwd_pool_stats_rows(G)
-            part = _f32((P, 2, C), dev)
-            # gmask = the pooled gradient times the ReLU mask at the pooled rows: what the data / weight gradient kernels
-            # place at the arg-max rows (pcops.h, pcops_mlp_pool_bwd_stats)
-            gmask = _f32((G, C), dev)
-            _lib.call("pcops_mlp_pool_bwd_stats", G, C, grad_out.data_ptr(), ysel.data_ptr(),
-                      scales[-1].data_ptr(), shifts[-1].data_ptr(), part.data_ptr(), gmask.data_ptr())
-            Gm = None
-        else:
-            P = lib.pcops_mlp_bwd_stats_rows(R)
-            part = _f32((P, 2, C), dev)
-            Gm = _f32((R, C), dev)
-            _lib.call("pcops_mlp_relu_mask_stats", R, C, grad_out.data_ptr(), Ys[-1].data_ptr(),
-                      scales[-1].data_ptr(), shifts[-1].data_ptr(), Gm.data_ptr(), part.data_ptr())
-
+        _bwd_output(dn, pool, widths[-1])
+        first = (None, None, None, None)        # d0, d1, dwxyz, dbias of a gather first layer
         for l in range(L - 1, -1, -1):
-            N = widths[l]
-            dgamma, dbeta = _f32(N, dev), _f32(N, dev)
-            p, q, t = vecs.take(N), vecs.take(N), vecs.take(N)
-            _lib.call("pcops_mlp_bn_bwd_coeffs", P, N, R, part.data_ptr(), ws.data_ptr(), gammas[l].data_ptr(),
-                      means[l].data_ptr(), rstds[l].data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(),
-                      p.data_ptr(), q.data_ptr(), t.data_ptr())
-            if sync:
-                # SyncBN: dgamma / dbeta stay rank-local sums (the gradient all-reduce adds the ranks up); the
-                # dY = p G + q Y + t coefficients come from the sums over the GLOBAL batch
-                gpart, Rg = _dist.allreduce_stat_partials(part, R)
-                junk = _f32(2 * N, dev)
-                _lib.call("pcops_mlp_bn_bwd_coeffs", gpart.shape[0], N, Rg, gpart.data_ptr(), ws.data_ptr(), gammas[l].data_ptr(),
-                          means[l].data_ptr(), rstds[l].data_ptr(), junk.data_ptr(), junk[N:].data_ptr(),
-                          p.data_ptr(), q.data_ptr(), t.data_ptr())
-            if not training:    # frozen statistics: no mean / variance terms in the BN backward
-                q.zero_()
-                t.zero_()
-            grads[6 * l + 2] = dgamma
-            grads[6 * l + 3] = dbeta
-            pooled = pool and l == L - 1
-            gp = gmask.data_ptr() if pooled else None
-            am = argmax.data_ptr() if pooled else None
-            psc = scales[l].data_ptr() if pooled else None
-            psh = shifts[l].data_ptr() if pooled else None
-            Gptr = None if (pooled or Gm is None) else Gm.data_ptr()
-
-            if l == 0 and gather and virt:
-                # arithmetic first layer: its gradients are linear in sums the layer above already produced
-                dwxyz = _f32((3, N), dev)
-                dbias = _f32(N, dev) if bias is not None else None
-                _lib.call("pcops_xyz_first_layer_grads", xstats.shape[0], xstats.data_ptr(), mom.shape[0], mom.data_ptr(),
-                          N, wxyz.data_ptr(), _p(bias), p.data_ptr(), q.data_ptr(), t.data_ptr(), dbeta.data_ptr(),
-                          means[0].data_ptr(), R, dwxyz.data_ptr(), _p(dbias))
-                break
-            if l == 0 and gather and getattr(ctx, "direct", False):
-                # the input needs no gradient: dW (6, C1) / db straight from E^T Gm and the edge moments -- no scatter
-                B, M, _ = idx.shape
-                if xstats is not None:        # reduced by the one-pass backward of the layer above
-                    wpart, P1 = xstats, xstats.shape[0]
-                else:
-                    P1 = lib.pcops_edge_first_rows()
-                    wpart = _f32((P1, 6, N), dev)
-                    _lib.call("pcops_edge_first_wgrad", B, a0.shape[1], M, S, N, Gptr, xyz.data_ptr(), idx.data_ptr(),
-                              wpart.data_ptr())
-                dwxyz = _f32((6, N), dev)
-                dbias = _f32(N, dev) if bias is not None else None
-                _lib.call("pcops_edge_first_layer_grads", P1, wpart.data_ptr(), mom.shape[0], mom.data_ptr(), N,
-                          wxyz.data_ptr(), _p(bias), p.data_ptr(), q.data_ptr(), t.data_ptr(), dbeta.data_ptr(),
-                          means[0].data_ptr(), R, dwxyz.data_ptr(), _p(dbias))
-                break
-            if l == 0 and gather and getattr(ctx, "qc", False):
-                # [Q | Ctr] form: dQ and dCtr are the column halves of ONE (B, N, 2 C1) gradient
-                B, M, _ = idx.shape
-                Nsrc = a0.shape[1]
-                d0 = _f32((B, Nsrc, 2 * N), dev)
-                wsp = torch.empty(int(lib.pcops_sa_scatter_workspace_bytes(B, Nsrc, M, S)) // 4, dtype=torch.int32, device=dev)
-                _lib.call("pcops_sa_scatter_bwd_ld", B, Nsrc, M, S, N, Gptr, p.data_ptr(), q.data_ptr(), t.data_ptr(),
-                          idx.data_ptr(), a0.data_ptr(), 2 * N, a0.data_ptr() + 4 * N, 2 * N, d0.data_ptr(), 2 * N,
-                          d0.data_ptr() + 4 * N, 2 * N, wsp.data_ptr())
-                break
-            if l == 0 and gather and getattr(ctx, "cloud_bias", False) and Gptr is not None:
-                B, M, _ = idx.shape
-                d0 = _f32((B, a0.shape[1], N), dev) if ctx.needs_input_grad[0] else None
-                d1 = _f32((B, M, N), dev)
-                scratch = _f32((lib.pcops_cloud_bias_rows(R), N), dev)
-                _lib.call("pcops_cloud_bias_bwd", R, S, N, Gptr, Ys[0].data_ptr(), p.data_ptr(), q.data_ptr(), t.data_ptr(),
-                          _p(d0), d1.data_ptr(), scratch.data_ptr())
-                break
-            if l == 0 and gather:
-                B, M, _ = idx.shape
-                Nsrc = a0.shape[1] if a0 is not None else xyz.shape[1]
-                d0 = _f32((B, Nsrc, N), dev) if (a0 is not None and ctx.needs_input_grad[0]) else None
-                d1 = _f32((B, M, N), dev) if ctr is not None else None
-                dwxyz = _f32((3, N), dev) if wxyz is not None else None
-                dbias = _f32(N, dev) if bias is not None else None
-                wpart = _f32(lib.pcops_sa_scatter_rows(B, M) * 4 * N, dev) if (wxyz is not None or bias is not None) else None
-                wsp = None
-                d0_out = d0
-                if d0 is not None and identity and not pooled:
-                    # idx = 0..n-1: the scatter-add is the identity map, dQ = dY row for row
-                    if TAIL_FOLD and N % 4 == 0:
-                        d0_out = _f32((B, Nsrc, N), dev)
-                        _lib.call("pcops_mlp_dy_apply", B * Nsrc, N, Gm.data_ptr(), Ys[0].data_ptr(), p.data_ptr(),
-                                  q.data_ptr(), t.data_ptr(), d0_out.data_ptr())
-                    else:
-                        d0_out = torch.addcmul(t[:N], Gm, p[:N]).addcmul_(Ys[0], q[:N]).view(B, Nsrc, N)
-                    d0 = None                # the kernel below then only reduces dWxyz / dbias / dCtr
-                if d0 is not None:   # gather formulation over an inverse index
-                    wsp = torch.empty(int(lib.pcops_sa_scatter_workspace_bytes(B, Nsrc, M, S)) // 4,
-                                      dtype=torch.int32, device=dev)
-                _lib.call("pcops_sa_scatter_bwd_rows", B, Nsrc, M, S, N, Gptr, _p(Ys[0]), p.data_ptr(),
-                          q.data_ptr(), t.data_ptr(), gp, am, psc, psh, idx.data_ptr(),
-                          _p(xyz) if wxyz is not None else None, _p(new_xyz) if wxyz is not None else None,
-                          _p(d0), _p(d1), _p(wpart), _p(dwxyz), _p(dbias), _p(a0), _p(ctr), _p(wxyz), _p(bias),
-                          _p(wsp), rref)
-                d0 = d0_out
-                break
-
-            K = Ws[l].shape[0]
-            xyz_prev = virt and l == 1          # the layer below is the arithmetic first layer (never stored)
-            if pooled and ctx.pool_top:
-                # algebraic form (pcops.h "algebraic backward of a pooled top layer"): K x K products instead of K x N
-                prev = (Ys[l - 1], scales[l - 1], shifts[l - 1]) if l > 0 else (a0, None, None)
-                Gm, part = _pool_top_backward(R, K, N, S, Ws[l], ctx.biases[l].detach(), p, q, t, grad_out, ysel,
-                                              argmax, scales[l], shifts[l], prev[0], prev[1], prev[2], grads, l, dev,
-                                              l > 0 or ctx.needs_input_grad[0], rows)
-                P = lib.pcops_mlp_stats_rows(R)
-                if l == 0:
-                    d0 = Gm
-                continue
-            fused_groups = 0
-            if BWD_FUSED and l > 0 and Ws[l].data_ptr() % 16 == 0:
-                # the bandwidth-bound narrow layers: data and weight gradient in ONE pass over Y / Yprev
-                fused_groups = lib.pcops_mlp_bwd_fused_groups(R, K, N, S if pooled else 0, 1 if pooled else 0)
-            if fused_groups:
-                edge_rows = getattr(ctx, "edge_rows", None) if (l == 1 and pooled and getattr(ctx, "direct", False)) else None
-                if edge_rows is not None and lib.pcops_mlp_bwd_fused_edge_groups(R, K, N, S, 0) != fused_groups:
-                    edge_rows = None
-                # pooled layer on uncompacted rows: the weight gradient in its Gram form (pcops.h, round 6) -- a K x K
-                # product on the matrix pipe + the arg rows as vector work instead of the K x N product.  The query asked
-                # is the one of the launcher that runs: the edge forms take fewer group sizes (S % 32 != 0)
-                gw = (pooled and rows is None and not xyz_prev and
-                      (lib.pcops_mlp_bwd_fused_edge_groups(R, K, N, S, 1) if edge_rows is not None
-                       else lib.pcops_mlp_bwd_fused_gw_groups(R, K, N, S)) == fused_groups)
-                scratch = _f32(fused_groups * (K * N + N + ((K * K + K) if gw else 0)), dev)
-                dW, db = _f32((K, N), dev), _f32(N, dev)
-                P = fused_groups
-                part = _f32((P, 2, K), dev)
-                bl = ctx.biases[l]
-                if edge_rows is not None:   # the first EdgeConv layer below, input without gradient: E^T Gm reduced in the kernel
-                    xstats = _f32((P, 6, K), dev)
-                    if gw:
-                        _lib.call("pcops_mlp_bwd_fused_edge_gw", R, K, N, Ys[0].data_ptr(), scales[0].data_ptr(),
-                                  shifts[0].data_ptr(), Ys[l].data_ptr(), p.data_ptr(), q.data_ptr(), t.data_ptr(), gp, am, S,
-                                  Ws[l].data_ptr(), _p(bl), scratch.data_ptr(), dW.data_ptr(), db.data_ptr(), part.data_ptr(),
-                                  edge_rows.data_ptr(), xstats.data_ptr())
-                    else:
-                        _lib.call("pcops_mlp_bwd_fused_edge", R, K, N, Ys[0].data_ptr(), scales[0].data_ptr(),
-                                  shifts[0].data_ptr(), Ys[l].data_ptr(), p.data_ptr(), q.data_ptr(), t.data_ptr(), gp, am, S,
-                                  Ws[l].data_ptr(), scratch.data_ptr(), dW.data_ptr(), db.data_ptr(), part.data_ptr(),
-                                  edge_rows.data_ptr(), xstats.data_ptr())
-                    grads[6 * l + 0] = dW
-                    grads[6 * l + 1] = db
-                    Gm = None
-                    continue
-                if gw:
-                    Gprev = _f32((R, K), dev)
-                    _lib.call("pcops_mlp_bwd_fused_gw", R, K, N, Ys[l - 1].data_ptr(), scales[l - 1].data_ptr(),
-                              shifts[l - 1].data_ptr(), Ys[l].data_ptr(), p.data_ptr(), q.data_ptr(), t.data_ptr(),
-                              gp, am, S, Ws[l].data_ptr(), _p(bl), scratch.data_ptr(), dW.data_ptr(), db.data_ptr(),
-                              Gprev.data_ptr(), part.data_ptr())
-                    grads[6 * l + 0] = dW
-                    grads[6 * l + 1] = db
-                    Gm = Gprev
-                    continue
-                if xyz_prev:     # the arithmetic first layer below: its masked gradient is reduced, never written
-                    xstats = _f32((P, 3, K), dev)
-                    _lib.call("pcops_mlp_bwd_fused_xyz_rows", R, K, N, off4.data_ptr(), xyzw.data_ptr(),
-                              scales[0].data_ptr(), shifts[0].data_ptr(), Gptr, Ys[l].data_ptr(), p.data_ptr(),
-                              q.data_ptr(), t.data_ptr(), gp, am, S, Ws[l].data_ptr(), scratch.data_ptr(),
-                              dW.data_ptr(), db.data_ptr(), part.data_ptr(), xstats.data_ptr(), rref)
-                    grads[6 * l + 0] = dW
-                    grads[6 * l + 1] = db
-                    Gm = None
-                    continue
-                Gprev = _f32((R, K), dev)
-                _lib.call("pcops_mlp_bwd_fused_rows", R, K, N, Ys[l - 1].data_ptr(), scales[l - 1].data_ptr(),
-                          shifts[l - 1].data_ptr(), Gptr, Ys[l].data_ptr(), p.data_ptr(), q.data_ptr(), t.data_ptr(),
-                          gp, am, S, Ws[l].data_ptr(), scratch.data_ptr(), dW.data_ptr(), db.data_ptr(),
-                          Gprev.data_ptr(), part.data_ptr(), rref)
-                grads[6 * l + 0] = dW
-                grads[6 * l + 1] = db
-                Gm = Gprev
-                continue
-            if l == 0:
-                src, ld, asc, ash = a0, K0, None, None
-            elif not xyz_prev:
-                src, ld, asc, ash = Ys[l - 1], Ys[l - 1].shape[1], scales[l - 1].data_ptr(), shifts[l - 1].data_ptr()
-            splits = lib.pcops_mlp_wgrad_splits(R, K, N)
-            scratch = _f32(splits * (K * N + N), dev)
-            dW, db = _f32((K, N), dev), _f32(N, dev)
-            if xyz_prev:
-                _lib.call("pcops_mlp_wgrad_xyz_rows", R, K, N, off4.data_ptr(), xyzw.data_ptr(), scales[0].data_ptr(),
-                          shifts[0].data_ptr(), Gptr, Ys[l].data_ptr(), p.data_ptr(), q.data_ptr(), t.data_ptr(), gp, am,
-                          S, psc, psh, scratch.data_ptr(), dW.data_ptr(), db.data_ptr(), rref)
+            lp = plan.layers[l]
+            dgamma, dbeta, p, q, t = _bn_backward(lp.N, R, dn.P, dn.part, sv.gammas[l], sv.means[l], sv.rstds[l],
+                                                  training=training, sync=sync, vecs=vecs, ws=ws)
+            dn.grads[6 * l + 2] = dgamma
+            dn.grads[6 * l + 3] = dbeta
+            top = pool and l == L - 1
+            if lp.bwd == B_XYZ_FIRST:
+                first = _bwd_xyz_first(dn, lp.N, p, q, t, dbeta)
+            elif lp.bwd == B_EDGE_FIRST:
+                first = _bwd_edge_first(dn, lp.N, p, q, t, dbeta)
+            elif lp.bwd == B_QC:
+                first = _bwd_qc_scatter(dn, lp.N, p, q, t)
+            elif lp.bwd == B_CLOUD:
+                first = _bwd_cloud_bias(dn, lp.N, p, q, t)
+            elif lp.bwd in (B_SCATTER, B_SCATTER_ID):
+                first = _bwd_scatter(dn, lp, p, q, t, top)
+            elif lp.bwd == B_TOP:
+                _pool_top_backward(dn, l, lp, p, q, t)
+            elif lp.bwd in _ONEPASS:
+                _bwd_onepass(dn, l, lp, p, q, t, top)
             else:
-                _lib.call("pcops_mlp_wgrad_rows", R, K, N, src.data_ptr(), ld, asc, ash, Gptr, Ys[l].data_ptr(),
-                          p.data_ptr(), q.data_ptr(), t.data_ptr(), gp, am, S, psc, psh, scratch.data_ptr(),
-                          dW.data_ptr(), db.data_ptr(), rref)
-            grads[6 * l + 0] = dW
-            grads[6 * l + 1] = db
-            if l > 0 or ctx.needs_input_grad[0]:
-                Wt = _f32((N, K), dev)
-                _lib.call("pcops_mlp_transpose", K, N, Ws[l].data_ptr(), Wt.data_ptr())
-                Gprev = None if xyz_prev else _f32((R, K), dev)
-                if xyz_prev:     # the first layer's masked gradient is reduced in the epilogue, never written
-                    P = lib.pcops_mlp_stats_rows(R)
-                    part = _f32((P, 2, K), dev)
-                    xstats = _f32((P, 3, K), dev)
-                    _lib.call("pcops_mlp_gemm_dgrad_xyz_rows", R, N, K, Gptr, Ys[l].data_ptr(), p.data_ptr(), q.data_ptr(),
-                              t.data_ptr(), gp, am, S, psc, psh, Wt.data_ptr(), off4.data_ptr(), xyzw.data_ptr(),
-                              scales[0].data_ptr(), shifts[0].data_ptr(), None, part.data_ptr(), xstats.data_ptr(),
-                              rref)
-                elif l > 0:
-                    P = lib.pcops_mlp_stats_rows(R)
-                    part = _f32((P, 2, K), dev)
-                    _lib.call("pcops_mlp_gemm_dgrad_rows", R, N, K, Gptr, Ys[l].data_ptr(), p.data_ptr(), q.data_ptr(),
-                              t.data_ptr(), gp, am, S, psc, psh, Wt.data_ptr(), Ys[l - 1].data_ptr(),
-                              scales[l - 1].data_ptr(), shifts[l - 1].data_ptr(), Gprev.data_ptr(),
-                              part.data_ptr(), rref)
-                else:
-                    _lib.call("pcops_mlp_gemm_dgrad", R, N, K, Gptr, Ys[l].data_ptr(), p.data_ptr(), q.data_ptr(),
-                              t.data_ptr(), gp, am, S, psc, psh, Wt.data_ptr(), None, None, None,
-                              Gprev.data_ptr(), None)
-                    d0 = Gprev
-                Gm = Gprev
-
-        out = [d0 if ctx.needs_input_grad[0] else None, d1, None, None, None, dwxyz, dbias,
+                _bwd_split(dn, l, lp, p, q, t, top)
+        d0, d1, dwxyz, dbias = first if gather else (dn.Gm, None, None, None)
+        out = [d0 if plan.need_dx else None, d1, None, None, None, dwxyz, dbias,
                None, None, None, None, None, None, None, None]
         for i in range(L):
-            out.extend(grads[6 * i:6 * i + 4])
+            out.extend(dn.grads[6 * i:6 * i + 4])
             out.extend([None, None])
         return tuple(out)
 
 
-def _pool_top_ok(lib, R, K, N, S, l, gather, K0, rows, xyz_prev, has_bias):
-    """the pooled top layer l takes the algebraic backward (pcops.h): K x K products instead of K x N, no use of Y"""
-    if rows is not None:        # compacted rows: the *_rows forms, one answer from the library (PCOPS_POOL_TOP_ROWS=0: never)
-        # (the narrow layers the one-pass backward takes stay there: it reads Y once for both gradients)
-        return bool(POOL_TOP and POOL_TOP_ROWS and not xyz_prev and S >= 64 and N >= 2 * K and l > 0 and has_bias
-                    and not (BWD_FUSED and lib.pcops_mlp_bwd_fused_groups(R, K, N, S, 1))
-                    and lib.pcops_mlp_pool_top_rows_supported(R, K, N, S))
-    return bool(POOL_TOP and not xyz_prev and S >= 64 and N >= 2 * K
-                and (l > 0 or (not gather and K0 == K)) and has_bias
-                and lib.pcops_mlp_pool_top_supported(R, K, N, S))
+class _Up:
+    """what the forward arms of one stack share: its operands and geometry, and the side buffers of the first layer"""
+    __slots__ = ("a0", "ctr", "idx", "xyz", "new_xyz", "wxyz", "bias", "geom", "S", "R", "dev", "training", "rows", "rref",
+                 "off4", "xyzw", "mom", "edge_rows")
+
+    def __init__(self, operands, geom, S, R, dev, training, rows):
+        self.a0, self.ctr, self.idx, self.xyz, self.new_xyz, self.wxyz, self.bias = operands
+        self.geom, self.S, self.R, self.dev, self.training, self.rows = geom, S, R, dev, training, rows
+        self.rref = rows.ref if rows is not None else None
+        self.off4 = self.xyzw = self.mom = self.edge_rows = None
 
 
-def _pool_top_backward(R, K, N, S, W, b, p, q, t, grad_out, ysel, argmax, sc, sh, Yprev, psc, psh, grads, l, dev,
-                       need_dx=True, rows=None):
-    """dW, db (into grads) and the masked data gradient + its statistics of a pooled top layer, from the Kp x Kp
-    products of pcops.h's algebraic form.  Returns (Gprev, stats_partial).  rows: the stack's compacted row set (R stays
-    the uncompacted count: it sizes the buffers and is the M of the closing sums)."""
+def _fwd_first(up, lp, Y, piv):
+    """the gather first layer in the plan's form; returns (P, the statistics partials)"""
     lib = _lib.load()
-    rref = rows.ref if rows is not None else None
+    (B, Nsrc, M), S, N, a0 = up.geom, up.S, lp.N, up.a0
+    if lp.fwd == F_QC:
+        P = lib.pcops_sa_gather_fwd_stats_rows(B, Nsrc, M, S, N, 1, 1, 0, 0)
+        part = _f32((P, 2, N), up.dev) if up.training else None
+        _lib.call("pcops_sa_gather_fwd_ld", B, Nsrc, M, S, N, a0.data_ptr(), 2 * N, a0.data_ptr() + 4 * N, 2 * N,
+                  up.idx.data_ptr(), Y.data_ptr(), _p(part), piv)
+    elif lp.fwd == F_CLOUD:     # pcops.h pcops_cloud_bias_*
+        P = lib.pcops_cloud_bias_rows(up.R)
+        part = _f32((P, 2, N), up.dev) if up.training else None
+        _lib.call("pcops_cloud_bias_fwd", up.R, S, N, a0.data_ptr(), up.ctr.data_ptr(), Y.data_ptr(), _p(part), piv)
+    else:
+        other = up.wxyz is not None or up.bias is not None or up.off4 is not None
+        P = lib.pcops_sa_gather_fwd_stats_rows(B, Nsrc, M, S, N, int(a0 is not None), int(up.ctr is not None),
+                                                int(other), int(up.rref is not None))
+        part = _f32((P, 2, N), up.dev) if up.training else None
+        _lib.call("pcops_sa_gather_fwd_rows", B, Nsrc, M, S, N, _p(a0), _p(up.ctr), _p(up.xyz), _p(up.new_xyz),
+                  _p(up.wxyz), _p(up.bias), up.idx.data_ptr(), _p(Y), _p(up.off4), _p(part), piv, _p(up.mom), up.rref)
+    return P, part
+
+
+def _fwd_edge_moments(up, store_rows):
+    """the 27 moments of the edge features, for E^T Y1 in the backward of a direct first layer ... and, where the layer
+    above takes the one-pass backward, the edge rows themselves (32 bytes each): E^T Gm is then reduced inside that
+    kernel and the masked gradient is never written"""
+    B, Nsrc, M = up.geom
+    up.mom = _f32((_lib.load().pcops_edge_first_rows(), 27), up.dev)
+    up.edge_rows = _f32((up.R, 8), up.dev) if store_rows else None
+    _lib.call("pcops_edge_first_moments", B, Nsrc, M, up.S, up.xyz.data_ptr(), up.idx.data_ptr(), up.mom.data_ptr(),
+              _p(up.edge_rows))
+
+
+def _fwd_product(up, lp, Y, piv, prev, W, b, gamma):
+    """Y = relu(bn(prev)) W + b in the plan's form; prev = (src, scale, shift) of the layer below (the plain input:
+    (a0, None, None)).  Returns (P, the statistics partials, the buffers of a pooled epilogue or None)"""
+    R, K, N, dev = up.R, lp.K, lp.N, up.dev
+    src, sc, sh = prev
+    P = _lib.load().pcops_mlp_stats_rows(R)
+    part = _f32((P, 2, N), dev) if up.training else None
+    bufs = None
+    if lp.fwd == F_XYZ:
+        _lib.call("pcops_mlp_gemm_fwd_xyz_rows", R, K, N, up.off4.data_ptr(), up.xyzw.data_ptr(), sc.data_ptr(),
+                  sh.data_ptr(), W.data_ptr(), b.data_ptr(), Y.data_ptr(), _p(part), piv, up.rref)
+    elif lp.fwd == F_POOL_ROWS:
+        nbk = up.rows.blocks.shape[0]
+        bufs = (_f32((nbk, N), dev), torch.empty((nbk, N), dtype=torch.uint8, device=dev))
+        _lib.call("pcops_mlp_gemm_fwd_pool_rows", R, K, N, src.data_ptr(), K, sc.data_ptr(),
+                  sh.data_ptr(), W.data_ptr(), b.data_ptr(), gamma.data_ptr(), _p(Y),
+                  _p(part), piv, bufs[0].data_ptr(), bufs[1].data_ptr(), up.rref)
+    elif lp.fwd == F_ROWS:
+        # compacted rows without the fused epilogue: the max over the groups is its own pass
+        _lib.call("pcops_mlp_gemm_fwd_rows", R, K, N, src.data_ptr(), K, _p(sc), _p(sh),
+                  W.data_ptr(), b.data_ptr(), Y.data_ptr(), _p(part), piv, up.rref)
+    elif lp.fwd == F_POOL:      # raw extrema; resolved after the statistics
+        G = R // up.S
+        bufs = (_f32((G, N), dev), torch.empty((G, N), dtype=torch.uint8, device=dev))
+        _lib.call("pcops_mlp_gemm_fwd_pool", R, K, N, up.S, src.data_ptr(), K, _p(sc),
+                  _p(sh), W.data_ptr(), b.data_ptr(), gamma.data_ptr(), _p(Y),
+                  _p(part), piv, bufs[0].data_ptr(), bufs[1].data_ptr())
+    else:
+        _lib.call("pcops_mlp_gemm_fwd", R, K, N, src.data_ptr(), K, _p(sc), _p(sh),
+                  W.data_ptr(), b.data_ptr(), Y.data_ptr(), _p(part), piv)
+    return P, part, bufs
+
+
+def _fwd_output(up, lp, top, gamma, bufs, *, pool, keep):
+    """BN + ReLU (+ the max over the groups) of the top layer lp, top = its (Y, scale, shift); keep: a backward may need the
+    pooled rows.  Returns (out, argmax, ysel)"""
+    R, S, C, dev = up.R, up.S, lp.N, up.dev
+    Y, scale, shift = top
+    if not pool:
+        out = _f32((R, C), dev)
+        _lib.call("pcops_mlp_bn_relu_apply", R, C, Y.data_ptr(), scale.data_ptr(), shift.data_ptr(), out.data_ptr())
+        return out, None, None
+    G = R // S
+    out = _f32((G, C), dev)
+    if lp.pooled == "rows":
+        argmax = torch.empty((G, C), dtype=torch.uint8, device=dev)
+        ysel = _f32((G, C), dev)
+        _lib.call("pcops_mlp_pool_combine_rows", G, C, bufs[0].data_ptr(), bufs[1].data_ptr(),
+                  gamma.data_ptr(), scale.data_ptr(), shift.data_ptr(), up.rref,
+                  out.data_ptr(), argmax.data_ptr(), ysel.data_ptr())
+    elif lp.pooled == "raw":
+        ysel, argmax = bufs
+        _lib.call("pcops_mlp_pool_select", G, C, ysel.data_ptr(), scale.data_ptr(), shift.data_ptr(), out.data_ptr())
+    else:
+        argmax = torch.empty((G, C), dtype=torch.uint8, device=dev) if keep else None
+        ysel = _f32((G, C), dev) if keep else None
+        if up.rows is not None:
+            _lib.call("pcops_mlp_bn_relu_maxpool_rows", G, C, Y.data_ptr(), scale.data_ptr(),
+                      shift.data_ptr(), up.rref, out.data_ptr(), _p(argmax), _p(ysel))
+        else:
+            _lib.call("pcops_mlp_bn_relu_maxpool", G, S, C, Y.data_ptr(), scale.data_ptr(),
+                      shift.data_ptr(), out.data_ptr(), _p(argmax), _p(ysel))
+    return out, argmax, ysel
+
+
+class _Down:
+    """what a backward pass carries down the stack: the node's records, and per step the masked gradient Gm of the layer's
+    output with the partials (P, part) of its statistics, the reduced first-layer sums xstats, the parameter gradients"""
+    __slots__ = ("sv", "plan", "biases", "edge_rows", "rows", "rref", "R", "S", "dev", "grad_out", "grads", "gmask", "Gm",
+                 "P", "part", "xstats")
+
+    def __init__(self, ctx, grad_out):
+        self.sv, self.plan, self.biases, self.edge_rows, self.rows = ctx.saved, ctx.plan, ctx.biases, ctx.edge_rows, ctx.rows
+        self.rref = self.rows.ref if self.rows is not None else None
+        self.S, self.R, self.dev, self.grad_out = ctx.meta[0], ctx.meta[3], grad_out.device, grad_out
+        self.grads = [None] * (6 * len(self.plan.layers))
+        self.gmask = self.Gm = self.part = self.xstats = None
+        self.P = 0
+
+    def pool_ptrs(self, l, top):
+        """(gmask, argmax, scale, shift) of the pooled layer for the kernels that place the pooled gradient at the arg-max
+        rows themselves; four None for any other layer"""
+        if not top:
+            return None, None, None, None
+        return self.gmask.data_ptr(), self.sv.argmax.data_ptr(), self.sv.scales[l].data_ptr(), self.sv.shifts[l].data_ptr()
+
+
+def _bwd_output(dn, pool, C):
+    """top of the stack: statistics of the masked upstream gradient"""
+    lib = _lib.load()
+    sv, R, dev = dn.sv, dn.R, dn.dev
+    if pool:
+        G = R // dn.S
+        dn.P = lib.pcops_mlp_bwd_pool_stats_rows(G)
+        dn.part = _f32((dn.P, 2, C), dev)
+        # gmask = the pooled gradient times the ReLU mask at the pooled rows: what the data / weight gradient kernels
+        # place at the arg-max rows (pcops.h, pcops_mlp_pool_bwd_stats)
+        dn.gmask = _f32((G, C), dev)
+        _lib.call("pcops_mlp_pool_bwd_stats", G, C, dn.grad_out.data_ptr(), sv.ysel.data_ptr(),
+                  sv.scales[-1].data_ptr(), sv.shifts[-1].data_ptr(), dn.part.data_ptr(), dn.gmask.data_ptr())
+    else:
+        dn.P = lib.pcops_mlp_bwd_stats_rows(R)
+        dn.part = _f32((dn.P, 2, C), dev)
+        dn.Gm = _f32((R, C), dev)
+        _lib.call("pcops_mlp_relu_mask_stats", R, C, dn.grad_out.data_ptr(), sv.Ys[-1].data_ptr(),
+                  sv.scales[-1].data_ptr(), sv.shifts[-1].data_ptr(), dn.Gm.data_ptr(), dn.part.data_ptr())
+
+
+# ---- backward arms of a gather first layer: each returns (d0, d1, dwxyz, dbias)
+def _bwd_xyz_first(dn, N, p, q, t, dbeta):
+    """arithmetic first layer: its gradients are linear in sums the layer above already produced"""
+    sv, dev = dn.sv, dn.dev
+    dwxyz = _f32((3, N), dev)
+    dbias = _f32(N, dev) if sv.bias is not None else None
+    _lib.call("pcops_xyz_first_layer_grads", dn.xstats.shape[0], dn.xstats.data_ptr(), sv.mom.shape[0], sv.mom.data_ptr(),
+              N, sv.wxyz.data_ptr(), _p(sv.bias), p.data_ptr(), q.data_ptr(), t.data_ptr(), dbeta.data_ptr(),
+              sv.means[0].data_ptr(), dn.R, dwxyz.data_ptr(), _p(dbias))
+    return None, None, dwxyz, dbias
+
+
+def _bwd_edge_first(dn, N, p, q, t, dbeta):
+    """the input needs no gradient: dW (6, C1) / db straight from E^T Gm and the edge moments -- no scatter"""
+    sv, dev = dn.sv, dn.dev
+    if dn.plan.edge_rows:       # reduced by the one-pass backward of the layer above
+        wpart, P1 = dn.xstats, dn.xstats.shape[0]
+    else:
+        B, M, _ = sv.idx.shape
+        P1 = _lib.load().pcops_edge_first_rows()
+        wpart = _f32((P1, 6, N), dev)
+        _lib.call("pcops_edge_first_wgrad", B, sv.a0.shape[1], M, dn.S, N, _p(dn.Gm), sv.xyz.data_ptr(), sv.idx.data_ptr(),
+                  wpart.data_ptr())
+    dwxyz = _f32((6, N), dev)
+    dbias = _f32(N, dev) if sv.bias is not None else None
+    _lib.call("pcops_edge_first_layer_grads", P1, wpart.data_ptr(), sv.mom.shape[0], sv.mom.data_ptr(), N,
+              sv.wxyz.data_ptr(), _p(sv.bias), p.data_ptr(), q.data_ptr(), t.data_ptr(), dbeta.data_ptr(),
+              sv.means[0].data_ptr(), dn.R, dwxyz.data_ptr(), _p(dbias))
+    return None, None, dwxyz, dbias
+
+
+def _bwd_qc_scatter(dn, N, p, q, t):
+    """[Q | Ctr] form: dQ and dCtr are the column halves of ONE (B, N, 2 C1) gradient"""
+    lib = _lib.load()
+    sv, dev, S = dn.sv, dn.dev, dn.S
+    a0 = sv.a0
+    B, M, _ = sv.idx.shape
+    Nsrc = a0.shape[1]
+    d0 = _f32((B, Nsrc, 2 * N), dev)
+    wsp = torch.empty(int(lib.pcops_sa_scatter_workspace_bytes(B, Nsrc, M, S)) // 4, dtype=torch.int32, device=dev)
+    _lib.call("pcops_sa_scatter_bwd_ld", B, Nsrc, M, S, N, _p(dn.Gm), p.data_ptr(), q.data_ptr(), t.data_ptr(),
+              sv.idx.data_ptr(), a0.data_ptr(), 2 * N, a0.data_ptr() + 4 * N, 2 * N, d0.data_ptr(), 2 * N,
+              d0.data_ptr() + 4 * N, 2 * N, wsp.data_ptr())
+    return d0, None, None, None
+
+
+def _bwd_cloud_bias(dn, N, p, q, t):
+    sv, dev, R = dn.sv, dn.dev, dn.R
+    B, M, _ = sv.idx.shape
+    d0 = _f32((B, sv.a0.shape[1], N), dev) if dn.plan.need_dx else None
+    d1 = _f32((B, M, N), dev)
+    scratch = _f32((_lib.load().pcops_cloud_bias_rows(R), N), dev)
+    _lib.call("pcops_cloud_bias_bwd", R, dn.S, N, dn.Gm.data_ptr(), sv.Ys[0].data_ptr(), p.data_ptr(), q.data_ptr(),
+              t.data_ptr(), _p(d0), d1.data_ptr(), scratch.data_ptr())
+    return d0, d1, None, None
+
+
+def _bwd_scatter(dn, lp, p, q, t, top):
+    """the generic scatter-add of the gather first layer (B_SCATTER_ID: with dQ = dY row for row in front of it)"""
+    lib = _lib.load()
+    sv, dev, S, N = dn.sv, dn.dev, dn.S, lp.N
+    a0, ctr, wxyz, bias, Gm = sv.a0, sv.ctr, sv.wxyz, sv.bias, dn.Gm
+    gp, am, psc, psh = dn.pool_ptrs(0, top)
+    B, M, _ = sv.idx.shape
+    Nsrc = a0.shape[1] if a0 is not None else sv.xyz.shape[1]
+    d0 = _f32((B, Nsrc, N), dev) if (a0 is not None and dn.plan.need_dx) else None
+    d1 = _f32((B, M, N), dev) if ctr is not None else None
+    dwxyz = _f32((3, N), dev) if wxyz is not None else None
+    dbias = _f32(N, dev) if bias is not None else None
+    wpart = _f32(lib.pcops_sa_scatter_rows(B, M) * 4 * N, dev) if (wxyz is not None or bias is not None) else None
+    wsp = None
+    d0_out = d0
+    if lp.bwd == B_SCATTER_ID:
+        # idx = 0..n-1: the scatter-add is the identity map, dQ = dY row for row
+        if dn.plan.tail_fold and N % 4 == 0:
+            d0_out = _f32((B, Nsrc, N), dev)
+            _lib.call("pcops_mlp_dy_apply", B * Nsrc, N, Gm.data_ptr(), sv.Ys[0].data_ptr(), p.data_ptr(),
+                      q.data_ptr(), t.data_ptr(), d0_out.data_ptr())
+        else:
+            d0_out = torch.addcmul(t[:N], Gm, p[:N]).addcmul_(sv.Ys[0], q[:N]).view(B, Nsrc, N)
+        d0 = None                # the kernel below then only reduces dWxyz / dbias / dCtr
+    if d0 is not None:   # gather formulation over an inverse index
+        wsp = torch.empty(int(lib.pcops_sa_scatter_workspace_bytes(B, Nsrc, M, S)) // 4,
+                          dtype=torch.int32, device=dev)
+    _lib.call("pcops_sa_scatter_bwd_rows", B, Nsrc, M, S, N, _p(Gm), _p(sv.Ys[0]), p.data_ptr(),
+              q.data_ptr(), t.data_ptr(), gp, am, psc, psh, sv.idx.data_ptr(),
+              _p(sv.xyz) if wxyz is not None else None, _p(sv.new_xyz) if wxyz is not None else None,
+              _p(d0), _p(d1), _p(wpart), _p(dwxyz), _p(dbias), _p(a0), _p(ctr), _p(wxyz), _p(bias),
+              _p(wsp), dn.rref)
+    return d0_out, d1, dwxyz, dbias
+
+
+# ---- backward arms of a product layer l: dW, db into dn.grads; Gm, (P, part) and xstats of the layer below into dn
+def _bwd_onepass(dn, l, lp, p, q, t, top):
+    """data and weight gradient in ONE pass over Y / Yprev, in the plan's form"""
+    sv, dev, R, S = dn.sv, dn.dev, dn.R, dn.S
+    K, N, groups, arm = lp.K, lp.N, lp.count, lp.bwd
+    gp, am, _, _ = dn.pool_ptrs(l, top)
+    gw = arm in (B_ONEPASS_GW, B_ONEPASS_EDGE_GW)
+    scratch = _f32(groups * (K * N + N + ((K * K + K) if gw else 0)), dev)
+    dW, db = _f32((K, N), dev), _f32(N, dev)
+    part = _f32((groups, 2, K), dev)
+    bl, W, Y, Gptr = dn.biases[l], sv.Ws[l], sv.Ys[l], _p(dn.Gm)
+    Gprev = None
+    if arm in (B_ONEPASS_EDGE, B_ONEPASS_EDGE_GW):
+        # the first EdgeConv layer below, input without gradient: E^T Gm reduced in the kernel
+        dn.xstats = _f32((groups, 6, K), dev)
+        if gw:
+            _lib.call("pcops_mlp_bwd_fused_edge_gw", R, K, N, sv.Ys[0].data_ptr(), sv.scales[0].data_ptr(),
+                      sv.shifts[0].data_ptr(), Y.data_ptr(), p.data_ptr(), q.data_ptr(), t.data_ptr(), gp, am, S,
+                      W.data_ptr(), _p(bl), scratch.data_ptr(), dW.data_ptr(), db.data_ptr(), part.data_ptr(),
+                      dn.edge_rows.data_ptr(), dn.xstats.data_ptr())
+        else:
+            _lib.call("pcops_mlp_bwd_fused_edge", R, K, N, sv.Ys[0].data_ptr(), sv.scales[0].data_ptr(),
+                      sv.shifts[0].data_ptr(), Y.data_ptr(), p.data_ptr(), q.data_ptr(), t.data_ptr(), gp, am, S,
+                      W.data_ptr(), scratch.data_ptr(), dW.data_ptr(), db.data_ptr(), part.data_ptr(),
+                      dn.edge_rows.data_ptr(), dn.xstats.data_ptr())
+    elif arm == B_ONEPASS_GW:
+        Gprev = _f32((R, K), dev)
+        _lib.call("pcops_mlp_bwd_fused_gw", R, K, N, sv.Ys[l - 1].data_ptr(), sv.scales[l - 1].data_ptr(),
+                  sv.shifts[l - 1].data_ptr(), Y.data_ptr(), p.data_ptr(), q.data_ptr(), t.data_ptr(),
+                  gp, am, S, W.data_ptr(), _p(bl), scratch.data_ptr(), dW.data_ptr(), db.data_ptr(),
+                  Gprev.data_ptr(), part.data_ptr())
+    elif arm == B_ONEPASS_XYZ:      # the arithmetic first layer below: its masked gradient is reduced, never written
+        dn.xstats = _f32((groups, 3, K), dev)
+        _lib.call("pcops_mlp_bwd_fused_xyz_rows", R, K, N, sv.off4.data_ptr(), sv.xyzw.data_ptr(),
+                  sv.scales[0].data_ptr(), sv.shifts[0].data_ptr(), Gptr, Y.data_ptr(), p.data_ptr(),
+                  q.data_ptr(), t.data_ptr(), gp, am, S, W.data_ptr(), scratch.data_ptr(),
+                  dW.data_ptr(), db.data_ptr(), part.data_ptr(), dn.xstats.data_ptr(), dn.rref)
+    else:
+        Gprev = _f32((R, K), dev)
+        _lib.call("pcops_mlp_bwd_fused_rows", R, K, N, sv.Ys[l - 1].data_ptr(), sv.scales[l - 1].data_ptr(),
+                  sv.shifts[l - 1].data_ptr(), Gptr, Y.data_ptr(), p.data_ptr(), q.data_ptr(), t.data_ptr(),
+                  gp, am, S, W.data_ptr(), scratch.data_ptr(), dW.data_ptr(), db.data_ptr(),
+                  Gprev.data_ptr(), part.data_ptr(), dn.rref)
+    dn.grads[6 * l + 0] = dW
+    dn.grads[6 * l + 1] = db
+    dn.Gm, dn.P, dn.part = Gprev, groups, part
+
+
+def _bwd_split(dn, l, lp, p, q, t, top):
+    """weight gradient, then (where something below takes one) the data gradient, as separate products"""
+    lib = _lib.load()
+    sv, dev, R, S = dn.sv, dn.dev, dn.R, dn.S
+    K, N, Gptr, Y, rref = lp.K, lp.N, _p(dn.Gm), sv.Ys[l], dn.rref
+    gp, am, psc, psh = dn.pool_ptrs(l, top)
+    xyz_prev = lp.bwd == B_SPLIT_XYZ
+    scratch = _f32(lp.count * (K * N + N), dev)
+    dW, db = _f32((K, N), dev), _f32(N, dev)
+    if xyz_prev:
+        _lib.call("pcops_mlp_wgrad_xyz_rows", R, K, N, sv.off4.data_ptr(), sv.xyzw.data_ptr(), sv.scales[0].data_ptr(),
+                  sv.shifts[0].data_ptr(), Gptr, Y.data_ptr(), p.data_ptr(), q.data_ptr(), t.data_ptr(), gp, am,
+                  S, psc, psh, scratch.data_ptr(), dW.data_ptr(), db.data_ptr(), rref)
+    else:
+        src, asc, ash = (sv.Ys[l - 1], sv.scales[l - 1].data_ptr(), sv.shifts[l - 1].data_ptr()) if l else (sv.a0, None, None)
+        _lib.call("pcops_mlp_wgrad_rows", R, K, N, src.data_ptr(), K, asc, ash, Gptr, Y.data_ptr(),
+                  p.data_ptr(), q.data_ptr(), t.data_ptr(), gp, am, S, psc, psh, scratch.data_ptr(),
+                  dW.data_ptr(), db.data_ptr(), rref)
+    dn.grads[6 * l + 0] = dW
+    dn.grads[6 * l + 1] = db
+    if l == 0 and not dn.plan.need_dx:
+        return
     Wt = _f32((N, K), dev)
-    if TAIL_FOLD:       # W^T, W diag(q) and q.b + t out of one launch
+    _lib.call("pcops_mlp_transpose", K, N, sv.Ws[l].data_ptr(), Wt.data_ptr())
+    Gprev = None if xyz_prev else _f32((R, K), dev)
+    if l > 0:
+        dn.P = lib.pcops_mlp_stats_rows(R)
+        dn.part = _f32((dn.P, 2, K), dev)
+    if xyz_prev:     # the first layer's masked gradient is reduced in the epilogue, never written
+        dn.xstats = _f32((dn.P, 3, K), dev)
+        _lib.call("pcops_mlp_gemm_dgrad_xyz_rows", R, N, K, Gptr, Y.data_ptr(), p.data_ptr(), q.data_ptr(),
+                  t.data_ptr(), gp, am, S, psc, psh, Wt.data_ptr(), sv.off4.data_ptr(), sv.xyzw.data_ptr(),
+                  sv.scales[0].data_ptr(), sv.shifts[0].data_ptr(), None, dn.part.data_ptr(), dn.xstats.data_ptr(),
+                  rref)
+    elif l > 0:
+        _lib.call("pcops_mlp_gemm_dgrad_rows", R, N, K, Gptr, Y.data_ptr(), p.data_ptr(), q.data_ptr(),
+                  t.data_ptr(), gp, am, S, psc, psh, Wt.data_ptr(), sv.Ys[l - 1].data_ptr(),
+                  sv.scales[l - 1].data_ptr(), sv.shifts[l - 1].data_ptr(), Gprev.data_ptr(),
+                  dn.part.data_ptr(), rref)
+    else:
+        _lib.call("pcops_mlp_gemm_dgrad", R, N, K, Gptr, Y.data_ptr(), p.data_ptr(), q.data_ptr(),
+                  t.data_ptr(), gp, am, S, psc, psh, Wt.data_ptr(), None, None, None,
+                  Gprev.data_ptr(), None)
+    dn.Gm = Gprev
+
+
+def _pool_top_backward(dn, l, lp, p, q, t):
+    """algebraic form of a pooled top layer (pcops.h "algebraic backward of a pooled top layer"): dW, db and the masked
+    data gradient + its statistics from K x K products instead of K x N, without the layer's Y.  On a compacted row set
+    R stays the uncompacted count: it sizes the buffers and is the M of the closing sums."""
+    lib = _lib.load()
+    sv, dev, R, S, rows, rref = dn.sv, dn.dev, dn.R, dn.S, dn.rows, dn.rref
+    K, N, fold = lp.K, lp.N, dn.plan.tail_fold
+    W, b, grad_out = sv.Ws[l], dn.biases[l].detach(), dn.grad_out
+    ysel, argmax, sc, sh = sv.ysel, sv.argmax, sv.scales[l], sv.shifts[l]
+    Yprev, psc, psh = (sv.Ys[l - 1], sv.scales[l - 1], sv.shifts[l - 1]) if l > 0 else (sv.a0, None, None)
+    need_dx = l > 0 or dn.plan.need_dx
+    Wt = _f32((N, K), dev)
+    if fold:            # W^T, W diag(q) and q.b + t out of one launch
         Wq, u = _f32((K, N), dev), _f32(N, dev)
         v = _f32(K, dev) if need_dx else None           # ... and v = W u
         _lib.call("pcops_mlp_pool_top_prep", K, N, W.data_ptr(), b.data_ptr(), q.data_ptr(), t.data_ptr(), Wt.data_ptr(),
@@ -565,8 +754,7 @@ def _pool_top_backward(R, K, N, S, W, b, p, q, t, grad_out, ysel, argmax, sc, sh
     Gprev = part = None
     # the Gram matrix of the input first: with it the layer's two K-sized products (W diag(q) W^T for the data gradient, gram W diag(q)
     # for the weight gradient) are independent of everything else and leave in ONE launch
-    splits = lib.pcops_mlp_wgrad_splits(R, K, K)
-    scratch = _f32(splits * (K * K + K), dev)
+    scratch = _f32(lp.count * (K * K + K), dev)
     gram, xsum = _f32((K, K), dev), _f32(K, dev)
     if rows is not None:        # X^T diag(w) X and X^T w
         _lib.call("pcops_mlp_gram_rows", R, K, Yprev.data_ptr(), K, _p(psc), _p(psh), scratch.data_ptr(),
@@ -575,7 +763,7 @@ def _pool_top_backward(R, K, N, S, W, b, p, q, t, grad_out, ysel, argmax, sc, sh
         _lib.call("pcops_mlp_gram", R, K, Yprev.data_ptr(), K, _p(psc), _p(psh), scratch.data_ptr(),
                   gram.data_ptr(), xsum.data_ptr())
     dW = _f32((K, N), dev)
-    paired = TAIL_FOLD and need_dx
+    paired = fold and need_dx
     if paired:
         Mq = _f32((K, K), dev)
         _lib.small_gemm_pair((K, N, K, Wq.data_ptr(), N, 0, Wt.data_ptr(), K, 0, None, Mq.data_ptr(), K, None),
@@ -584,7 +772,7 @@ def _pool_top_backward(R, K, N, S, W, b, p, q, t, grad_out, ysel, argmax, sc, sh
         if not paired:
             Mq = _f32((K, K), dev)
             _lib.call("pcops_small_gemm", K, N, K, Wq.data_ptr(), N, Wt.data_ptr(), K, Mq.data_ptr(), K)
-        if not TAIL_FOLD:
+        if not fold:
             v = _f32(K, dev)
             _lib.call("pcops_small_gemm", 1, N, K, u.data_ptr(), N, Wt.data_ptr(), K, v.data_ptr(), K)
         G = R // S
@@ -618,18 +806,18 @@ def _pool_top_backward(R, K, N, S, W, b, p, q, t, grad_out, ysel, argmax, sc, sh
                   Ssp.data_ptr(), cfsum.data_ptr())
     if not paired:
         _lib.call("pcops_small_gemm", K, K, N, gram.data_ptr(), K, Wq.data_ptr(), N, dW.data_ptr(), N)
-    if TAIL_FOLD:       # (dW + Ssp) + xsum u^T in place, db = (cfsum + q.(xsum^T W + R b)) + R t: one launch for eleven
+    if fold:            # (dW + Ssp) + xsum u^T in place, db = (cfsum + q.(xsum^T W + R b)) + R t: one launch for eleven
         db = _f32(N, dev)
         _lib.call("pcops_mlp_pool_top_finish", K, N, R, dW.data_ptr(), Ssp.data_ptr(), xsum.data_ptr(), u.data_ptr(),
                   cfsum.data_ptr(), q.data_ptr(), W.data_ptr(), b.data_ptr(), t.data_ptr(), db.data_ptr())
-        grads[6 * l + 0] = dW
-        grads[6 * l + 1] = db
+        dn.grads[6 * l + 0] = dW
+        dn.grads[6 * l + 1] = db
     else:
         xw = _f32(N, dev)
         _lib.call("pcops_small_gemm", 1, K, N, xsum.data_ptr(), K, W.data_ptr(), N, xw.data_ptr(), N)
-        grads[6 * l + 0] = torch.addr(dW.add_(Ssp), xsum, u)
-        grads[6 * l + 1] = cfsum + q[:N] * (xw + float(R) * b) + float(R) * t[:N]
-    return Gprev, part
+        dn.grads[6 * l + 0] = torch.addr(dW.add_(Ssp), xsum, u)
+        dn.grads[6 * l + 1] = cfsum + q[:N] * (xw + float(R) * b) + float(R) * t[:N]
+    dn.Gm, dn.P, dn.part = Gprev, lib.pcops_mlp_stats_rows(R), part
 
 
 class _SmallLinear(torch.autograd.Function):
@@ -944,6 +1132,9 @@ def _row_stride(g):
     return int(ld) if (ld >= g.shape[-1] and ld % 4 == 0) else None
 
 
+PoolSaved = namedtuple("PoolSaved", "Q Ctr idx gamma SQ arg ysel mean rstd scale shift")      # ... an EdgeConvPool node
+
+
 class EdgeConvPool(torch.autograd.Function):
     """apply(Q, Ctr, idx, gamma, beta, mm, mv, training, decay, eps, unbiased[, cat, col]) -> (B*M, C)
     [cat (a CatBuffer over (B, M, C_total)) and col: the output is ALSO stored as columns col..col+C of cat.buf, and a second
@@ -975,25 +1166,9 @@ class EdgeConvPool(torch.autograd.Function):
         else:
             _lib.call("pcops_edge_pool_fwd", B, Nsrc, M, S, C, Q.data_ptr(), Ctr.data_ptr(), idx.data_ptr(),
                       gamma.data_ptr(), SQ.data_ptr(), qsel.data_ptr(), arg.data_ptr(), _p(part), piv0)
-        vecs = _VecArena([C], 4, dev)
-        scale, shift = vecs.take(C), vecs.take(C)
-        mean = rstd = None
-        if training:
-            mean, rstd = vecs.take(C), vecs.take(C)
-            ws = _workspace(C, dev)
-            Pf, Rf, piv_fin = P, G * S, (mm.data_ptr() if STAT_PIVOT else None)
-            if sync:
-                part, Rf = _dist.allreduce_stat_partials(part, G * S, mm if STAT_PIVOT else None)
-                Pf, piv_fin = part.shape[0], None
-            _lib.call("pcops_mlp_bn_finalize", Pf, C, Rf, part.data_ptr(), piv_fin,
-                      ws.data_ptr(), gamma.data_ptr(),
-                      beta.data_ptr(), float(eps), float(decay), int(unbiased), mm.data_ptr(), mv.data_ptr(),
-                      mean.data_ptr(), rstd.data_ptr(), scale.data_ptr(), shift.data_ptr())
-        else:
-            _lib.call("pcops_mlp_bn_eval_coeffs", C, gamma.data_ptr(), beta.data_ptr(), mm.data_ptr(), mv.data_ptr(),
-                      float(eps), scale.data_ptr(), shift.data_ptr())
-            if need_grad:
-                mean, rstd = mm.detach().clone(), torch.rsqrt(mv.detach() + float(eps))
+        scale, shift, mean, rstd = _bn_forward((gamma, beta, mm, mv), C, G * S, P, part, piv0, training=training, sync=sync,
+                                               need_grad=need_grad, hyper=(eps, decay, unbiased),
+                                               vecs=_VecArena([C], 4, dev), ws=_workspace(C, dev) if training else None)
         out = _f32((G, C), dev)
         ysel = _f32((G, C), dev) if (training or need_grad) else None
         sl = None
@@ -1008,8 +1183,8 @@ class EdgeConvPool(torch.autograd.Function):
             _lib.call("pcops_edge_pool_out", G, C, qsel.data_ptr(), Ctr.data_ptr(), scale.data_ptr(), shift.data_ptr(),
                       out.data_ptr(), _p(ysel))
         if training or need_grad:
-            ctx.saved = (Q, Ctr, idx, gamma, SQ, arg, ysel, mean, rstd, scale, shift)
-            ctx.flags = (bool(training), bool(sync))
+            ctx.saved = PoolSaved(Q, Ctr, idx, gamma, SQ, arg, ysel, mean, rstd, scale, shift)
+            ctx.flags = (bool(training), bool(sync), TAIL_FOLD)
             if TRACE is not None:
                 TRACE.append(ctx)
         ctx.nout = 2 if sl is not None else 1
@@ -1023,10 +1198,10 @@ class EdgeConvPool(torch.autograd.Function):
         assert given, "EdgeConvPool.backward without any gradient"
         # two pieces, or one that is a column block of a wider tensor: added / gathered inside the statistics pass below
         lds_ = [_row_stride(g) for g in given]
-        fold = TAIL_FOLD and all(l is not None for l in lds_) and (len(given) == 2 or lds_[0] != given[0].shape[-1])
+        training, sync, tail_fold = ctx.flags
+        fold = tail_fold and all(l is not None for l in lds_) and (len(given) == 2 or lds_[0] != given[0].shape[-1])
         grad_out = None if fold else (given[0] if len(given) == 1 else given[0] + given[1])
         Q, Ctr, idx, gamma, SQ, arg, ysel, mean, rstd, scale, shift = ctx.saved
-        training, sync = ctx.flags
         B, M, S = idx.shape
         qc = Ctr is None
         Nsrc, C = Q.shape[1], (Q.shape[2] // 2 if qc else Q.shape[2])
@@ -1043,22 +1218,8 @@ class EdgeConvPool(torch.autograd.Function):
             grad_out = grad_out.contiguous()
             _lib.call("pcops_mlp_pool_bwd_stats", G, C, grad_out.data_ptr(), ysel.data_ptr(), scale.data_ptr(),
                       shift.data_ptr(), part.data_ptr(), None)
-        vecs = _VecArena([C], 3, dev)
-        p, q, t = vecs.take(C), vecs.take(C), vecs.take(C)
-        dgamma, dbeta = _f32(C, dev), _f32(C, dev)
-        ws = _workspace(C, dev)
-        _lib.call("pcops_mlp_bn_bwd_coeffs", P, C, G * S, part.data_ptr(), ws.data_ptr(), gamma.data_ptr(),
-                  mean.data_ptr(), rstd.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), p.data_ptr(), q.data_ptr(),
-                  t.data_ptr())
-        if sync:        # see FusedMLPStack.backward
-            gpart, Rg = _dist.allreduce_stat_partials(part, G * S)
-            junk = _f32(2 * C, dev)
-            _lib.call("pcops_mlp_bn_bwd_coeffs", gpart.shape[0], C, Rg, gpart.data_ptr(), ws.data_ptr(), gamma.data_ptr(),
-                      mean.data_ptr(), rstd.data_ptr(), junk.data_ptr(), junk[C:].data_ptr(), p.data_ptr(),
-                      q.data_ptr(), t.data_ptr())
-        if not training:
-            q.zero_()
-            t.zero_()
+        dgamma, dbeta, p, q, t = _bn_backward(C, G * S, P, part, gamma, mean, rstd, training=training, sync=sync,
+                                              vecs=_VecArena([C], 3, dev), ws=_workspace(C, dev))
         wsp = torch.empty(int(lib.pcops_sa_scatter_workspace_bytes(B, Nsrc, M, S)) // 4, dtype=torch.int32, device=dev)
         if qc:          # dQ and dCtr: the column halves of ONE gradient of the [Q | Ctr] product
             dQC = _f32((B, Nsrc, 2 * C), dev)

@@ -94,15 +94,15 @@ class Recorder:
                     D.pool[scope] = (arg.reshape(-1, c).to(self.device), (out.reshape(-1, c) > 0).to(self.device))
                     D.relu.pop(scope, None)                   # pooled layer: the pool decision stands for its ReLU
                 last = None
-            elif len(e.saved) == 11:                          # EdgeConvPool node: one pooled layer
-                _Q, _Ctr, _idx, gamma, _SQ, arg, ysel, _mean, _rstd, scale, shift = e.saved
+            elif type(e.saved).__name__ == "PoolSaved":       # EdgeConvPool node: one pooled layer
+                gamma, arg, ysel, scale, shift = e.saved.gamma, e.saved.arg, e.saved.ysel, e.saved.scale, e.saved.shift
                 c = arg.shape[1]
                 active = (ysel.double() * scale[:c].double() + shift[:c].double()) > 0
                 D.pool[_scope_of(self.names[gamma.data_ptr()])] = (arg.long().to(self.device), active.to(self.device))
                 last = None
             else:                                             # FusedMLPStack node
                 masks, argmax = MR.node_pattern(e, virtual_first_layer=True)
-                gammas, scales, shifts, ysel = e.saved[13], e.saved[10], e.saved[11], e.saved[15]
+                gammas, scales, shifts, ysel = e.saved.gammas, e.saved.scales, e.saved.shifts, e.saved.ysel
                 S, pool, L = e.meta[:3]
                 for l, g in enumerate(gammas):
                     scope = _scope_of(self.names[g.data_ptr()])

@@ -35,17 +35,17 @@ def node_pattern(node, virtual_first_layer=False):
     """fused_pattern() of a given FusedMLPStack / EdgeConvPool autograd node.  virtual_first_layer: also rebuild the
     mask of an arithmetic first layer that is never stored (fused_mlp `virt`: y = fma(dz, w2, fma(dy, w1, fma(dx, w0,
     b))) from the centred offsets the node keeps -- csrc/mlp.hip xyz_y) instead of returning None for it."""
-    if len(node.saved) == 11:           # EdgeConvPool: ONE pooled layer, only the arg-max row is a discrete decision
-        return [None], node.saved[5]
-    Ys, scales, shifts, argmax = node.saved[7], node.saved[10], node.saved[11], node.saved[14]
-    off4, xyzw = node.saved[16], node.saved[17]
+    sv = node.saved
+    if type(sv).__name__ == "PoolSaved":    # EdgeConvPool: ONE pooled layer, only the arg-max row is a discrete decision
+        return [None], sv.arg
+    Ys, scales, shifts, argmax, off4, xyzw = sv.Ys, sv.scales, sv.shifts, sv.argmax, sv.off4, sv.xyzw
     expand = None
     rows = getattr(node, "rows", None)
     if rows is not None:
         # compacted rows: the stack ran on 16 * ceil(cnt / 16) rows per group.  Map every row (g, s) of the full
         # (b, m, S) layout to the compacted row that computed it: s itself while it exists, row 0 of the group (whose
         # copy it is) beyond -- then the masks below line up with the uncompacted float64 reference
-        idx = node.saved[2]
+        idx = sv.idx
         S = idx.shape[2]
         bs = rows.block_start.long()
         first = bs[:-1] * 16
