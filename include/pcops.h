@@ -957,6 +957,41 @@ int pcops_group_norm_relu_bwd(int b, int n, int c, int groups, const float *dout
                               const float *gamma, const float *mean, const float *rstd, float *dx, float *dgamma,
                               float *dbeta, void *workspace, pcops_stream_t stream);
 
+/* ------------------------------------------------------------------ 3DmFV-Net (csrc/mfv.hip)
+ * The 3DmFV representation (3DmFV-Net/utils/tf_util.py:578-652, get_3dmfv): points (b, n, 3) against a fixed mixture of k
+ * diagonal Gaussians w (k), mu (k, 3), sigma (k, 3) -- sigma is the STANDARD DEVIATION.  Per (point, Gaussian)
+ * Q = w N(x) / sum_k w N(x), z = (x - mu) / sigma; per Gaussian over the points max, sum of Q - w and max, min, sum per
+ * axis of Q z and of Q (z^2 - 1); scaled by 1 / (n sqrt(w)) resp. 1 / (n sqrt(2 w)), power-normalised sign(x) sqrt|x| and
+ * L2-normalised over the Gaussians per (cloud, row) as x / sqrt(max(sum x^2, 1e-12)).  fv (b, 20, k) in the reference's row
+ * order: d_pi max, sum; d_mu max xyz, min xyz, sum xyz; d_sigma max xyz, min xyz, sum xyz.  voxel_major != 0 writes
+ * (k, b, 20) instead: the voxel-major activation the convolutions below take (Gaussian index = voxel index).
+ * Nothing of n k elements is written to memory; chunk partials (512 points) go to pcops_fv3d_workspace_bytes(b, n, k) bytes
+ * of caller-owned workspace and are folded in ascending chunk order: no float atomics, bit-identical run to run.
+ * Supported: n >= 1, 1 <= k <= 512, b <= 65535, b n 3 < 2^31; PCOPS_ERR_UNSUPPORTED outside, before any launch. */
+unsigned long long pcops_fv3d_workspace_bytes(int b, int n, int k);
+int pcops_fv3d_fwd(int b, int n, int k, int voxel_major, const float *points, const float *w, const float *mu,
+                   const float *sigma, float *fv, void *workspace, pcops_stream_t stream);
+
+/* 3-D convolution with k^3 taps, k in {3, 5}, stride 1, SAME padding, on a cubic grid of r^3 voxels (r <= 8).  Activations
+ * are VOXEL-MAJOR: x (r^3, b, cin), y (r^3, b, cout), voxel index (i r + j) r + l; w (k, k, k, cin, cout) as in the reference
+ * (tf_util.py:290), bias (cout) or NULL.  y[v] = bias + sum over the taps t with v + t inside the grid of x[v + t] w[t]: one
+ * dense fp32 MFMA product per in-grid tap; no expanded operand exists and no matrix instruction is spent on padding.
+ * dgrad: dx (r^3, b, cin) through the forward kernel on the mirrored, transposed weights, which one small launch writes
+ * into pcops_conv3d_dgrad_workspace_bytes bytes of workspace.  wgrad: dw (k, k, k, cin, cout), dbias (cout) or NULL; the rows
+ * of a tap are split pcops_conv3d_wgrad_splits ways (1, 2, 4, 8 or 16) and the partials added in ascending order through
+ * pcops_conv3d_wgrad_workspace_bytes bytes (0 with one split: direct store, workspace may be NULL).  Every output is written
+ * whole; no float atomics.  Supported: cin, cout multiples of 16 up to 512, r^3 b max(cin, cout) < 2^31;
+ * PCOPS_ERR_UNSUPPORTED outside, before any launch. */
+int pcops_conv3d_fwd(int b, int r, int k, int cin, int cout, const float *x, const float *w, const float *bias, float *y,
+                     pcops_stream_t stream);
+unsigned long long pcops_conv3d_dgrad_workspace_bytes(int b, int r, int k, int cin, int cout);
+int pcops_conv3d_dgrad(int b, int r, int k, int cin, int cout, const float *w, const float *dy, float *dx, void *workspace,
+                       pcops_stream_t stream);
+int pcops_conv3d_wgrad_splits(int b, int r, int k, int cin, int cout);
+unsigned long long pcops_conv3d_wgrad_workspace_bytes(int b, int r, int k, int cin, int cout);
+int pcops_conv3d_wgrad(int b, int r, int k, int cin, int cout, const float *x, const float *dy, float *dw, float *dbias,
+                       void *workspace, pcops_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

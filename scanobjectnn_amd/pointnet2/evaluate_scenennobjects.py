@@ -146,7 +146,7 @@ def eval_partseg_one_epoch(net, data, parts, batch_size, num_classes=6, device="
 
 # ---- the command line of `pointnet2/evaluate_scenennobjects.py` ----------------------------------------------------
 def parse_args(argv=None):
-    from .train import MODELS, _flag
+    from .train import MODELS, _flag, add_model_flags
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     p.add_argument("--gpu", type=int, default=0, help="GPU to use (:27)")
     p.add_argument("--model", default="pointnet2_cls_ssg", choices=sorted(MODELS))            # :28
@@ -167,6 +167,7 @@ def parse_args(argv=None):
     p.add_argument("--shape_names", default="", help="text file with one class name per line (default: the 15 "
                    "ScanObjectNN names; the reference reads ../training_data/shape_names_*.txt, :57-62)")
     p.add_argument("--synthetic_clouds", type=int, default=256)
+    add_model_flags(p)
     return p.parse_args(argv)
 
 
@@ -209,7 +210,7 @@ def load_test_set(args):
 
 def evaluate(args):
     from ..graph import Model
-    from .train import MODELS
+    from .train import MODELS, model_fn
     if not torch.cuda.is_available() or not 0 <= args.gpu < torch.cuda.device_count():
         raise RuntimeError("--gpu %d: no such device (%d visible)" % (args.gpu, torch.cuda.device_count()))
     dev = torch.device("cuda", args.gpu)
@@ -233,7 +234,7 @@ def evaluate(args):
     rng = np.random.RandomState(0)                 # `np.random.seed(0)` (:66): the same two shuffles as the reference
     data, labels = load_test_set(args)
     kw = {"num_class": args.num_class} if args.num_class != 15 else {}
-    net = Model(mod.get_model, device=dev, seed=0, **kw).build(torch.zeros((2, args.num_point, 3), device=dev))
+    net = Model(model_fn(mod, args, dev), device=dev, seed=0, **kw).build(torch.zeros((2, args.num_point, 3), device=dev))
     info = restore(net, args.model_path)
     log_string("Model restored. (%s, %d variables)" % (info["format"], info["loaded"]))
     if isinstance(data, list):

@@ -35,7 +35,23 @@ MODELS = {"pointnet2_cls_ssg": "scanobjectnn_amd.pointnet2.pointnet2_cls_ssg",
           "pointnet2_cls_msg": "scanobjectnn_amd.pointnet2.pointnet2_cls_msg",
           "pointnet2_cls_partseg": "scanobjectnn_amd.pointnet2.pointnet2_cls_partseg",
           "dgcnn": "scanobjectnn_amd.dgcnn.dgcnn", "dgcnn_bga": "scanobjectnn_amd.dgcnn.dgcnn_bga",
-          "spidercnn_cls_xyz": "scanobjectnn_amd.spidercnn.spidercnn_cls_xyz"}
+          "spidercnn_cls_xyz": "scanobjectnn_amd.spidercnn.spidercnn_cls_xyz",
+          "3dmfv_net_cls": "scanobjectnn_amd.mfv3d.mfv3d_net_cls"}
+
+
+def add_model_flags(p):
+    """flags of one family that the trainer and the evaluation share (3DmFV-Net/train.py:49-54)"""
+    p.add_argument("--weight_decay", type=float, default=0.0,
+                   help="3dmfv_net_cls: handed to the FC layers as in the reference, whose loss never adds the collected terms")
+    p.add_argument("--gmm_type", default="grid", help="3dmfv_net_cls: grid (learn, the EM mixture, is out of scope and raises)")
+    p.add_argument("--num_gaussians", type=int, default=5, help="3dmfv_net_cls: grid subdivisions per axis (5: 125 Gaussians)")
+    p.add_argument("--gmm_variance", type=float, default=0.04, help="3dmfv_net_cls: variance of every grid Gaussian")
+
+
+def model_fn(mod, args, dev):
+    """the get_model(point_cloud, is_training, bn_decay, **kw) graph.Model takes: the module's own, or what the module
+    binds from the flags (3DmFV-Net: the mixture is an input of its get_model)"""
+    return mod.model_fn(args, dev) if hasattr(mod, "model_fn") else mod.get_model
 
 
 def _flag(v):
@@ -78,6 +94,7 @@ def parse_args(argv=None):
     p.add_argument("--no_augment", action="store_true", help="skip rotate + jitter (tests / debugging)")
     p.add_argument("--deterministic", action="store_true",
                    help="bit-reproducible backward passes: ordered owner sums instead of float atomics (slower)")
+    add_model_flags(p)
     return p.parse_args(argv)
 
 
@@ -169,7 +186,7 @@ def train(args):
 
     example = torch.zeros((2, args.num_point, 3), device=dev)
     kw = {"num_class": args.num_class} if args.num_class != 15 else {}
-    net = Model(mod.get_model, device=dev, seed=args.seed, **kw).build(example)
+    net = Model(model_fn(mod, args, dev), device=dev, seed=args.seed, **kw).build(example)
     fp = TU.FlatParams(net).enable_overlap(world)        # N > 1: gradient ranges travel while the backward pass runs
     D.broadcast_(fp.flat)
     opt = TU.make_optimizer(args.optimizer, fp, args.momentum)
@@ -186,7 +203,9 @@ def train(args):
         for b in range(nb):
             sl = slice(b * args.batch_size + lo, b * args.batch_size + hi)
             x = cur[sl]
-            if not args.no_augment:
+            if not args.no_augment and hasattr(mod, "augment"):       # a family with its own augmentation (3DmFV-Net)
+                x = mod.augment(x, generator=gen)
+            elif not args.no_augment:
                 x = provider.jitter_point_cloud(provider.rotate_point_cloud(x, generator=gen), generator=gen)
             x = x.contiguous()
             y = lab[sl]

@@ -79,6 +79,30 @@ def random_scale_point_cloud(batch_data, scale_low=0.8, scale_high=1.25, generat
     return _ret(x * s, np_in)
 
 
+def scale_point_cloud(batch_data, smin=0.66, smax=1.5, generator=None, scales=None):
+    """an independent scale factor per axis and cloud, U(smin, smax) (3DmFV-Net/provider.py:111-130).  scales: (B,3) the
+    factors instead of fresh draws"""
+    x, np_in = _as_tensor(batch_data)
+    if scales is not None:
+        s = torch.as_tensor(scales, dtype=x.dtype, device=x.device).reshape(x.shape[0], 1, 3)
+    else:
+        gdev = generator.device if generator is not None else x.device
+        s = torch.rand(x.shape[0], 1, 3, generator=generator, device=gdev, dtype=x.dtype).to(x.device) * (smax - smin) + smin
+    return _ret(x * s, np_in)
+
+
+def translate_point_cloud(batch_data, tval=0.2, generator=None, translation=None):
+    """one translation per cloud, U(-tval, tval) per axis (3DmFV-Net/provider.py:55-70).  translation: (B,3) the offsets
+    instead of fresh draws"""
+    x, np_in = _as_tensor(batch_data)
+    if translation is not None:
+        t = torch.as_tensor(translation, dtype=x.dtype, device=x.device).reshape(x.shape[0], 1, 3)
+    else:
+        gdev = generator.device if generator is not None else x.device
+        t = (torch.rand(x.shape[0], 1, 3, generator=generator, device=gdev, dtype=x.dtype).to(x.device) * 2 - 1) * tval
+    return _ret(x + t, np_in)
+
+
 def shift_point_cloud(batch_data, shift_range=0.1, generator=None):
     x, np_in = _as_tensor(batch_data)
     gdev = generator.device if generator is not None else x.device
