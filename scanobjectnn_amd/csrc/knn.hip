@@ -320,7 +320,10 @@ __global__ __launch_bounds__(256, 2) void knn_mfma_kernel(int n, int c, int k, c
 #pragma unroll
             for (int w = 0; w < (KL + 1) / 2; ++w) seed_ok = seed_ok && (theirs != mine[w]);
         }
-        seed_ok = seed_ok && (__shfl_xor((int)seed_ok, 32, 64) != 0);
+        // (the exchange runs in EVERY lane, outside the short-circuit: as `seed_ok && __shfl_xor(...)` a lane that had found
+        // its own half of the row invalid skipped the shuffle, its partner read an inactive lane and went on trusting the row)
+        const int partner_ok = __shfl_xor((int)seed_ok, 32, 64);
+        seed_ok = seed_ok && (partner_ok != 0);
         for (int s = half; s < k && qin; s += 2) {
             int j = sd[s];
             j = j < 0 ? 0 : (j >= n ? n - 1 : j);                           // (address safety only; such a row is rejected above)
@@ -586,7 +589,8 @@ __global__ __launch_bounds__(512, 2) void knn_f16_kernel(int n, int k, const flo
 #pragma unroll
             for (int w = 0; w < (KL + 1) / 2; ++w) seed_ok = seed_ok && (theirs != mine[w]);
         }
-        seed_ok = seed_ok && (__shfl_xor((int)seed_ok, 32, 64) != 0);
+        const int partner_ok = __shfl_xor((int)seed_ok, 32, 64);            // in every lane (see knn_mfma_kernel)
+        seed_ok = seed_ok && (partner_ok != 0);
         float worst = 0.f, smax = 0.f;
 #pragma unroll 1
         for (int u = 0; u < (KL + 1) / 2; ++u) {
