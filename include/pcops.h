@@ -80,7 +80,9 @@ int pcops_abi_version(void);
  *   PCOPS_OPT_POOL_TOP_ROWS_PIPELINED  0 / 1 (default): pcops_mlp_pool_top_wsparse_rows over compacted rows software-pipelined (the
  *                                      next group's rows and coefficients in flight under this group's sums, double-buffered LDS
  *                                      image, 16-byte LDS reads); same sums in the same order.  pcops_mlp_pool_top_addend_rows
- *                                      keeps its one form under either value
+ *                                      takes its wave-per-group kernel (a row's hits as ballots, the next row's W^T reads in
+ *                                      flight) at every supported shape -- Kp = 64 / 128, S <= 64 and S <= 128; same rows, same
+ *                                      rowmap, the former kernel's bits (DESIGN.md sections 4.21, 4.23).  0: the former kernels
  * pcops_set_option returns the PREVIOUS value (>= 0) or PCOPS_ERR_BAD_ARGUMENT.  The environment variables of rounds 3-4
  * (PCOPS_GEMM_BF3, PCOPS_WGRAD_BF3, PCOPS_BWD_FUSED_DX3, PCOPS_KNN_F16; round 6: PCOPS_DGRAD_BF3, PCOPS_BWD_FUSED_GW; later: PCOPS_GRAM_BF3, PCOPS_POOL_TOP_ROWS_PIPE) only seed the initial values (test overrides). */
 typedef enum pcops_option {
@@ -802,7 +804,9 @@ int pcops_mlp_bn_relu_maxpool_rows(long long G, int C, const float *Y, const flo
  * pcops_mlp_pool_top_wsparse_rows takes a scratch of pcops_mlp_pool_top_wsparse_rows_partial(Kp, N) floats in front of
  * the row set.  pcops_mlp_gram_rows: gram = X^T diag(w) X, xsum = X^T w (partial as pcops_mlp_gram).
  * pcops_mlp_pool_top_rows_supported is the ONE answer a caller asks for all four (S % 16 == 0, S <= 128, Kp = 64 / 128,
- * N <= 256, the addend within the 32-bit offset of its bounds check).  Sums in a fixed order (deterministic). */
+ * N <= 256, the addend within the 32-bit offset of its bounds check).  Sums in a fixed order (deterministic).
+ * pcops_mlp_pool_top_addend_rows itself takes any M: the floor on M in that answer belongs to the Gram pass and the dense
+ * products. */
 int pcops_mlp_pool_top_rows_supported(int M, int Kp, int N, int S);
 unsigned long long pcops_mlp_pool_top_wsparse_rows_partial(int Kp, int N);
 int pcops_mlp_pool_top_addend_rows(int M, int Kp, int N, int S, const float *gout, const float *ysel,

@@ -5172,7 +5172,8 @@ __global__ __launch_bounds__(256) void pool_top_wsparse_kernel(long long G, int 
 //   pool_top_wsparse_rows_kernel  group-major: a group's rows of X (contiguous in the compacted stack) staged once
 // The row of slot (g, a) is 16 block_start[g] + a; argmax is the row-in-group in compacted numbering.  Sums in a fixed order.
 //
-// addend: a quarter of the workgroup (256 threads = the C <= 256 channels) owns one group per round.  The channels that
+// addend (PCOPS_OPT_POOL_TOP_ROWS_PIPELINED = 0; 1 takes pool_top_addend_rows_pipe_kernel below): a quarter of the workgroup
+// (256 threads = the C <= 256 channels) owns one group per round.  The channels that
 // picked row r are a C-bit mask in LDS (integer OR: the result does not depend on the order); KP / 4 lanes per row then add
 // cf[c] Wt[c][:] over the set bits in ascending channel order and write the row ONCE.  The addend is indexed by the
 // compacted row itself (slot = row), rowmap [row] = row or -1.
@@ -5245,6 +5246,172 @@ __global__ __launch_bounds__(1024) void pool_top_addend_rows_kernel(int G, int C
             if (any) *reinterpret_cast<float4 *>(&addend[ri * KP + 4 * q]) = acc;
             if (q == 0) rowmap[ri] = any ? (int)ri : -1;
         }
+    }
+}
+
+// addend, software-pipelined (PCOPS_OPT_POOL_TOP_ROWS_PIPELINED = 1): a WAVE owns a group, so nothing of the walk crosses a wave
+// and the loop holds no barrier at all (one __syncthreads behind the staging of W^T).  Lane l keeps the coefficient and the
+// arg-max row of the channels l, l + 64, l + 128, l + 192 in registers; the channels that picked row r are then the ballots
+// of (row == r), one 64-bit scalar per 64 channels, bit order = channel order -- no mask in LDS, no atomic, nothing to zero.
+// The 64 lanes hold one row (KP / 64 floats each): the hit sequence is wave-uniform, so the bit scan, the loop control and the
+// coefficient (v_readlane) are scalar work and a hit costs the vector pipe an address, a read and one fmaf (v_pk_fma at KP = 128).
+// Pipeline: the first hit of each 64-channel word is a SLOT -- the four W^T reads of row r + 1 are issued (named register
+// sets A / B, the loop written two rows per trip) before the fmaf of row r.  An empty word's bit scan gives -1: its slot
+// reads the row in FRONT of the word's first channel (W^T is staged behind one spare row for word 0) and the coefficient of
+// lane 63, without a select (scalar instructions issue once in four cycles per SIMD: they, not the vector pipe, set this
+// kernel's pace), and its fmaf is skipped by a wave-uniform branch.  A word's second and later hits (256 channels spread
+// over the group's rows: 0.6 per row at the SSG shape) follow in a plain loop.  Per row and column the fmaf chain is the
+// former kernel's: the row's hits in ascending channel order from 0 -- the same bits.  The next group's (gout, ysel, arg)
+// are requested before this group's rows, the block_start pair of the group after it one trip earlier.
+template <int KP, int MAXR>
+__global__ __launch_bounds__(1024) void pool_top_addend_rows_pipe_kernel(int G, int C, const float *__restrict__ gout,
+                                                                         const float *__restrict__ ysel,
+                                                                         const unsigned char *__restrict__ arg,
+                                                                         const float *__restrict__ sc, const float *__restrict__ sh,
+                                                                         const float *__restrict__ p, const float *__restrict__ Wt,
+                                                                         const int *__restrict__ block_start,
+                                                                         float *__restrict__ addend, int *__restrict__ rowmap) {
+    constexpr int VEC = KP / 64, NW = 4;              // floats of a row per lane; 64-channel words (C <= 256)
+    static_assert(VEC == 1 || VEC == 2, "a row is one or two floats per lane");
+    static_assert(MAXR == 64 || MAXR == 128, "lane l answers for the rows l and l + 64 of a group");
+    typedef float rowv_t __attribute__((ext_vector_type(VEC)));
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    float *Ws = lds + KP;                             // [C][KP] behind one spare row ("channel -1": read, never used)
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);       // wave-uniform: the group index stays scalar
+    for (int e = tid; e < C * (KP / 4); e += 1024)
+        reinterpret_cast<float4 *>(Ws)[e] = reinterpret_cast<const float4 *>(Wt)[e];
+    if (tid < KP) lds[tid] = 0.f;
+    float scc[NW], shc[NW], pc[NW];
+#pragma unroll
+    for (int k = 0; k < NW; ++k) {
+        const int c = lane + 64 * k;
+        scc[k] = c < C ? sc[c] : 0.f; shc[k] = c < C ? sh[c] : 0.f; pc[k] = c < C ? p[c] : 0.f;
+    }
+    __syncthreads();                                  // W^T is there; the only barrier
+    // the group in flight: its raw triples (the coefficient is formed at use) and its rows
+    float fy[NW], fg[NW];
+    int fa[NW], fbase = 0, fn = 0;
+    int nb0 = 0, nb1 = 0;                             // block_start pair of the group fetch() takes next (scalar loads)
+    auto pair = [&](long long g) {
+        if (g < G) { nb0 = block_start[g]; nb1 = block_start[g + 1]; }
+    };
+    auto fetch = [&](long long g) {
+        fbase = 0; fn = 0;
+        if (g < G) {
+            fbase = kBlk * nb0;
+            fn = kBlk * (nb1 - nb0);
+            fn = fn < MAXR ? fn : MAXR;
+        }
+#pragma unroll
+        for (int k = 0; k < NW; ++k) {
+            const int c = lane + 64 * k;
+            fy[k] = 0.f; fg[k] = 0.f; fa[k] = 0;
+            if (g < G && c < C) {
+                const long long e = g * C + c;
+                fy[k] = ysel[e]; fg[k] = gout[e]; fa[k] = arg[e];
+            }
+        }
+    };
+    const long long stride = (long long)gridDim.x * 16;
+    long long g = (long long)blockIdx.x * 16 + wave;
+    // s_ff1_i32_b64: the lowest set bit, -1 for an empty word (__builtin_ctzll leaves that case undefined)
+    auto ff1 = [](unsigned long long m) {
+        int l;
+        asm("s_ff1_i32_b64 %0, %1" : "=s"(l) : "s"(m));
+        return l;
+    };
+    // one scalar instruction each (as C++ the mask is built with a 64-bit shift and, for the hit rows, kept in vector registers)
+    auto bit_clear = [](unsigned long long &m, int l) { asm("s_bitset0_b64 %0, %1" : "+s"(m) : "s"(l)); };
+    auto bit_set = [](unsigned long long &m, int l) { asm("s_bitset1_b64 %0, %1" : "+s"(m) : "s"(l)); };
+    // lane l's bytes of the row in front of word k's first channel: slot address = wbase[k] + (bit + 1) * KP * 4
+    // (signed: word 0's base is -KP * 4 bytes from Ws, the spare row)
+    int wbase[NW];
+#pragma unroll
+    for (int k = 0; k < NW; ++k) wbase[k] = ((64 * k - 1) * KP + VEC * lane) * 4;
+    auto wrow = [&](int k, int l) {
+        return *reinterpret_cast<const rowv_t *>(reinterpret_cast<const char *>(Ws) + (wbase[k] + (l + 1) * (KP * 4)));
+    };
+    pair(g);
+    fetch(g);
+    pair(g + stride);
+    for (; g < G; g += stride) {
+        int t0 = 0, t1 = 0;                           // the pair of the group after the next: requested here, waited for in
+        if (g + 2 * stride < G) {                     // front of the row loop, whose lgkmcnt waits then count LDS reads only
+            t0 = block_start[g + 2 * stride];
+            t1 = block_start[g + 2 * stride + 1];
+        }
+        float cfv[NW];
+        int rowv[NW];                                 // the row a channel adds to; -1: none (no coefficient, or beyond the group)
+#pragma unroll
+        for (int k = 0; k < NW; ++k) {
+            cfv[k] = fmaf(fy[k], scc[k], shc[k]) > 0.f ? pc[k] * fg[k] : 0.f;
+            rowv[k] = (cfv[k] != 0.f && fa[k] < fn) ? fa[k] : -1;
+        }
+        const int base = fbase, nrows = fn;
+        fetch(g + stride);                            // the next group's coefficients fly under this group's rows
+        nb0 = t0; nb1 = t1;
+        asm volatile("" ::"s"(nb0), "s"(nb1));
+        // a register set: per word the hits, the first of them (-1: none), its W^T read and its coefficient
+        struct Set {
+            rowv_t w[NW];
+            float cf[NW];
+            unsigned long long m[NW];
+            int l[NW];
+        };
+        auto coef = [&](int k, int l) {
+            return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, cfv[k]), l));
+        };
+        auto issue = [&](int r, Set &s) {
+#pragma unroll
+            for (int k = 0; k < NW; ++k) {
+                s.m[k] = __ballot(rowv[k] == r);
+                s.l[k] = ff1(s.m[k]);
+                s.cf[k] = coef(k, s.l[k]);
+                s.w[k] = wrow(k, s.l[k]);
+            }
+        };
+        unsigned long long anylo = 0ull, anyhi = 0ull; // the rows of the group with a hit (scalar)
+        // the addend within a 32-bit byte offset: checked by the launcher
+        char *const dst = reinterpret_cast<char *>(addend) + VEC * 4 * lane;
+        auto finish = [&](int r, const Set &s) {
+            rowv_t acc = 0.f;
+            bool any = false;
+#pragma unroll
+            for (int k = 0; k < NW; ++k) {
+                if (s.l[k] >= 0) {
+                    asm volatile("" ::: "memory");    // a branch, not a select: an empty slot costs the vector pipe nothing
+                    any = true;
+#pragma unroll
+                    for (int i = 0; i < VEC; ++i) acc[i] = fmaf(s.cf[k], s.w[k][i], acc[i]);
+                    unsigned long long mm = s.m[k];
+                    bit_clear(mm, s.l[k]);
+                    while (mm) {
+                        const int l = ff1(mm);
+                        bit_clear(mm, l);
+                        const float cw = coef(k, l);
+                        const rowv_t wt = wrow(k, l);
+#pragma unroll
+                        for (int i = 0; i < VEC; ++i) acc[i] = fmaf(cw, wt[i], acc[i]);
+                    }
+                }
+            }
+            if (any) {
+                *reinterpret_cast<rowv_t *>(dst + (unsigned)(base + r) * (unsigned)(KP * 4)) = acc;
+                if (MAXR == 64 || r < 64) bit_set(anylo, r); else bit_set(anyhi, r - 64);
+            }
+        };
+        Set A, B;
+        issue(0, A);
+        for (int r = 0; r < nrows; r += 2) {
+            issue(r + 1, B);                          // a row beyond the group has no hit: dead channels carry row -1
+            finish(r, A);
+            issue(r + 2, A);
+            if (r + 1 < nrows) finish(r + 1, B);
+        }
+        // rowmap [row] = row or -1 for every row of the group: lane l writes row l (and l + 64)
+        if (lane < nrows) rowmap[(long long)base + lane] = (anylo >> lane) & 1ull ? base + lane : -1;
+        if (MAXR > 64 && lane + 64 < nrows) rowmap[(long long)base + lane + 64] = (anyhi >> lane) & 1ull ? base + lane + 64 : -1;
     }
 }
 
@@ -6581,12 +6748,17 @@ int pcops_mlp_pool_top_wsparse(int M, int Kp, int N, int S, const float *gout, c
 /* ---- the four algebraic entry points over COMPACTED rows (pcops.h): rows == NULL is the entry point without the suffix */
 static const int kTopRowsWs = 512;        // workgroups (= partial copies) of pool_top_wsparse_rows_kernel
 
+// what the two addend kernels over compacted rows need of the shape (the addend is indexed by the compacted row: at most M
+// rows of Kp floats behind a 32-bit offset); pcops_mlp_pool_top_rows_supported adds what the other three calls need
+static bool addend_rows_shape_ok(int M, int Kp, int N, int S) {
+    return S % kBlk == 0 && S <= 128 && (Kp == 64 || Kp == 128) && N <= 256 && N % 32 == 0 &&
+           (long long)M * Kp * 4 < (long long)kOOB;
+}
+
 int pcops_mlp_pool_top_rows_supported(int M, int Kp, int N, int S) {
     if (!pcops_mlp_pool_top_supported(M, Kp, N, S)) return 0;
-    if (M < 65536 || S % kBlk != 0 || S > 128 || (Kp != 64 && Kp != 128) || N > 256 || N % 32 != 0) return 0;
-    if (!gram_full_groups(M, Kp, Kp, nullptr)) return 0;
-    // the addend is indexed by the compacted row: at most M rows of Kp floats behind a 32-bit buffer offset
-    return (long long)M * Kp * 4 < (long long)kOOB ? 1 : 0;
+    if (M < 65536 || !addend_rows_shape_ok(M, Kp, N, S)) return 0;
+    return gram_full_groups(M, Kp, Kp, nullptr) ? 1 : 0;
 }
 
 unsigned long long pcops_mlp_pool_top_wsparse_rows_partial(int Kp, int N) {
@@ -6603,14 +6775,24 @@ int pcops_mlp_pool_top_addend_rows(int M, int Kp, int N, int S, const float *gou
     PCOPS_REQUIRE_PTR(pool_shift); PCOPS_REQUIRE_PTR(p); PCOPS_REQUIRE_PTR(Wt); PCOPS_REQUIRE_PTR(addend);
     PCOPS_REQUIRE_PTR(rowmap);
     { const int rrc = rows_ok(rows); if (rrc) return rrc; }
-    if (!pcops_mlp_pool_top_rows_supported(M, Kp, N, S)) return PCOPS_ERR_UNSUPPORTED;
+    // this call's own share of pcops_mlp_pool_top_rows_supported: the floor on M there belongs to the Gram pass and the dense
+    // products, the addend kernels take any number of groups
+    if (!addend_rows_shape_ok(M, Kp, N, S)) return PCOPS_ERR_UNSUPPORTED;
     if (reinterpret_cast<uintptr_t>(Wt) & 15 || reinterpret_cast<uintptr_t>(addend) & 15) return PCOPS_ERR_UNSUPPORTED;
     const int G = M / S;
     const size_t lds = ((size_t)N * Kp + 4 * 256 + 4 * 128 * 8) * sizeof(float);
     const int grid = (G + 3) / 4 < 256 ? (G + 3) / 4 : 256;
     hipStream_t st = as_stream(stream);
+    // PCOPS_OPT_POOL_TOP_ROWS_PIPELINED = 1 (default): the wave-per-group kernel (both widths, S <= 64 and S <= 128; a wave takes
+    // a group, 16 groups per workgroup and round).  Only W^T lives in LDS, behind one spare row.  Same rows, same rowmap, same bits.
+    const bool piped = pcops_get_option(PCOPS_OPT_POOL_TOP_ROWS_PIPELINED) != 0;
+    const size_t lds_pipe = (size_t)(N + 1) * Kp * sizeof(float);     // one spare row in front
+    const int grid_pipe = (G + 15) / 16 < 256 ? (G + 15) / 16 : 256;
     return pcops_dispatch<64, 128>(Kp, PCOPS_ERR_UNSUPPORTED, [&](auto kp_) {
-        return pcops_launch_lds(pool_top_addend_rows_kernel<decltype(kp_)::value>, dim3(grid), dim3(1024), lds, 160 * 1024, st, G, N,
+        constexpr int KP = decltype(kp_)::value;
+        auto kern = !piped ? pool_top_addend_rows_kernel<KP>
+                  : S <= 64 ? pool_top_addend_rows_pipe_kernel<KP, 64> : pool_top_addend_rows_pipe_kernel<KP, 128>;
+        return pcops_launch_lds(kern, dim3(piped ? grid_pipe : grid), dim3(1024), piped ? lds_pipe : lds, 160 * 1024, st, G, N,
                                 gout, ysel, argmax, pool_scale, pool_shift, p, Wt, rows->block_start, addend, rowmap);
     });
 }

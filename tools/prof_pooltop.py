@@ -1,7 +1,8 @@
 """Per-call HIP-event timings of the algebraic top-layer backward (fused_mlp._pool_top_backward) against the plain
-dgrad + wgrad it replaces, at the benchmark shapes; then SA2's compacted case: pcops_mlp_gram_rows and
-pcops_mlp_pool_top_wsparse_rows alone, HIP events around the entry point, under both values of PCOPS_OPT_GRAM_SPLIT_BF16 /
-PCOPS_OPT_POOL_TOP_ROWS_PIPELINED.  python tools/prof_pooltop.py [--rows-only]"""
+dgrad + wgrad it replaces, at the benchmark shapes; then SA2's compacted case: pcops_mlp_gram_rows,
+pcops_mlp_pool_top_wsparse_rows and pcops_mlp_pool_top_addend_rows alone, HIP events around the entry point, under both
+values of PCOPS_OPT_GRAM_SPLIT_BF16 / PCOPS_OPT_POOL_TOP_ROWS_PIPELINED (DESIGN.md sections 4.21, 4.23).
+python tools/prof_pooltop.py [--rows-only]"""
 import collections
 import os
 import sys
@@ -84,6 +85,13 @@ def rows_case(reps=20):
                   sc.data_ptr(), sh.data_ptr(), p.data_ptr(), Yprev.data_ptr(), psc.data_ptr(), psh.data_ptr(),
                   Ssp.data_ptr(), cfsum.data_ptr(), wpart.data_ptr(), rows.ref)
 
+    Wt = (torch.randn(N, Kp, generator=g) / N ** 0.5).to(DEV)
+    addend, rowmap = torch.empty(R, Kp, device=DEV), torch.empty(R, dtype=torch.int32, device=DEV)
+
+    def addend_call():
+        _lib.call("pcops_mlp_pool_top_addend_rows", R, Kp, N, S, gout.data_ptr(), ysel.data_ptr(), arg8.data_ptr(),
+                  sc.data_ptr(), sh.data_ptr(), p.data_ptr(), Wt.data_ptr(), addend.data_ptr(), rowmap.data_ptr(), rows.ref)
+
     def timeit(f):
         for _ in range(3):
             f()
@@ -100,7 +108,8 @@ def rows_case(reps=20):
         return ts[0], ts[len(ts) // 2], ts[-1]
 
     for label, option, f in (("gram_rows (gram + partial sum + mirror)", _lib.OPT_GRAM_SPLIT_BF16, gram_call),
-                             ("wsparse_rows (walk + partial sum)", _lib.OPT_POOL_TOP_ROWS_PIPELINED, ws_call)):
+                             ("wsparse_rows (walk + partial sum)", _lib.OPT_POOL_TOP_ROWS_PIPELINED, ws_call),
+                             ("addend_rows", _lib.OPT_POOL_TOP_ROWS_PIPELINED, addend_call)):
         prev = _lib.get_option(option)
         try:
             for value in (0, 1, 0, 1):
