@@ -996,6 +996,40 @@ unsigned long long pcops_conv3d_wgrad_workspace_bytes(int b, int r, int k, int c
 int pcops_conv3d_wgrad(int b, int r, int k, int cin, int cout, const float *x, const float *dy, float *dw, float *dbias,
                        void *workspace, pcops_stream_t stream);
 
+/* ------------------------------------------------------------------ X-Conv contraction of PointCNN (csrc/xconv.hip)
+ * The gather, the concat, the product with the X-transform and the depthwise (1, K) half of the separable convolution of
+ * one X-Conv layer (PointCNN/pointcnn.py:28-44) in one launch.  b clouds of n points, p representative points per cloud,
+ * k neighbours each, c = c1 + c2 channels, depth multiplier dm:
+ *   lifted (b, p, k, c1)   the features lifted from the local coordinates (nn_fts_from_pts)
+ *   fts    (b, n, c2)      the previous layer's features, idx (b, p, k) int32 in [0, n) per cloud; both NULL with c2 == 0
+ *                          (the first layer)
+ *   X      (b, p, k, k)    the X-transform, row k' column k
+ *   wd     (k, c, dm)      the depthwise kernel [1, k, c, dm] of fts_conv
+ *   Fin[q,j,:] = concat(lifted[q,j,:], fts[idx[q,j],:])
+ *   out (b, p, c dm)       out[q, ch dm + m] = sum_k' wd[k',ch,m] sum_j X[q,k',j] Fin[q,j,ch]     (TF's channel order)
+ * Neither Fin nor X Fin is written to memory: one wave forms the 16 x 16 tile of a point and 16 channels with fp32 MFMA
+ * (k zero-padded to 16) and contracts it over k' in registers.
+ * dgrad: dX (b, p, k, k), dlifted (b, p, k, c1) and dfts_grouped (b, p, k, c2) -- the gradient of the GATHERED rows, NULL
+ * when not wanted or c2 == 0; the caller scatters it with pcops_group_point_grad / pcops_scatter_rows_sorted.
+ * wgrad: dwd (k, c, dm), X Fin recomputed.  The b p points are cut into pcops_xconv_wgrad_splits contiguous ranges (a power
+ * of two up to 64, whole 16-point steps, at least 16 points each); with more than one, the partial sums go to
+ * pcops_xconv_wgrad_workspace_bytes bytes of caller-owned workspace (0 with one split: direct store, workspace may be NULL)
+ * and are added in ascending order.  Every output is written whole; every sum is taken in a fixed order with no float
+ * atomics, so two calls give the same bits whatever pcops_set_deterministic says.
+ * Supported (pcops_xconv_supported): 1 <= k <= 16, c1 >= 1, c2 >= 0, 1 <= dm <= 4, c dm <= 960 (16 rows of wd in LDS);
+ * b p k max(c dm, k) < 2^31 and b n c2 < 2^31.  PCOPS_ERR_UNSUPPORTED outside, before any launch and any pointer check. */
+int pcops_xconv_supported(int k, int c1, int c2, int dm);
+int pcops_xconv_fwd(int b, int n, int p, int k, int c1, int c2, int dm, const float *lifted, const float *fts,
+                    const int *idx, const float *X, const float *wd, float *out, pcops_stream_t stream);
+int pcops_xconv_dgrad(int b, int n, int p, int k, int c1, int c2, int dm, const float *lifted, const float *fts,
+                      const int *idx, const float *X, const float *wd, const float *dout, float *dX, float *dlifted,
+                      float *dfts_grouped, pcops_stream_t stream);
+int pcops_xconv_wgrad_splits(int b, int n, int p, int k, int c1, int c2, int dm);
+unsigned long long pcops_xconv_wgrad_workspace_bytes(int b, int n, int p, int k, int c1, int c2, int dm);
+int pcops_xconv_wgrad(int b, int n, int p, int k, int c1, int c2, int dm, const float *lifted, const float *fts,
+                      const int *idx, const float *X, const float *dout, float *dwd, void *workspace,
+                      pcops_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

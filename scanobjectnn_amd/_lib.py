@@ -251,6 +251,17 @@ def scatter_rows_sorted(idx, src, ndst, div=1, w=None, out=None, c=None, ld=None
     return out
 
 
+def scatter_grouped(dfg, idx, n):
+    """dfeat (B,N,C) = the scatter-add of dfeat_grouped (B,M,k,C) through idx (B,M,k) (pcops_group_point_grad's
+    contract; the ordered owner walk in deterministic mode).  Shared by the SpiderConv and X-Conv backward passes."""
+    b, m, k, c = dfg.shape
+    if deterministic():
+        return scatter_rows_sorted(idx.view(b, m * k), dfg.view(b, m * k, c), n)
+    out = torch.empty((b, n, c), dtype=torch.float32, device=dfg.device)
+    call("pcops_group_point_grad", b, n, c, m, k, dfg.data_ptr(), idx.data_ptr(), out.data_ptr())
+    return out
+
+
 _SYNC_EVERY_CALL = os.environ.get("PCOPS_SYNC", "0") == "1"
 _hooks = []  # profiling hooks: callables (name, phase, args) with phase in {"pre", "post"}
 

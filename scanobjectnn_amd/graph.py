@@ -111,6 +111,21 @@ def xavier_initializer():
     return init
 
 
+def glorot_normal_initializer():
+    """tf.glorot_normal_initializer() = variance_scaling(1.0, 'fan_avg', 'normal'): a normal of stddev
+    sqrt(2/(fan_in+fan_out)) truncated at two standard deviations; fans as in xavier_initializer (for a depthwise
+    kernel [kh,kw,cin,multiplier] that reads fan_in = kh kw cin, fan_out = kh kw multiplier -- DESIGN.md section 7)."""
+    def init(t, gen):
+        shape = t.shape
+        rf = 1
+        for s in shape[:-2]:
+            rf *= s
+        fan_in, fan_out = shape[-2] * rf, shape[-1] * rf
+        std = math.sqrt(2.0 / (fan_in + fan_out))
+        torch.nn.init.trunc_normal_(t, mean=0.0, std=std, a=-2 * std, b=2 * std, generator=gen)
+    return init
+
+
 def truncated_normal_initializer(stddev):
     def init(t, gen):
         torch.nn.init.trunc_normal_(t, mean=0.0, std=stddev, a=-2 * stddev, b=2 * stddev, generator=gen)

@@ -1,0 +1,55 @@
+"""Settings of the PointCNN classifier -- the numbers of `PointCNN/pointcnn_cls/modelnet_x3_l4.py` as a plain namespace.
+`as_setting` takes any object with the same attributes, so tests build much smaller ones."""
+import math
+from types import SimpleNamespace
+
+_XCONV = ('K', 'D', 'P', 'C', 'links')
+_FC = ('C', 'dropout_rate')
+REQUIRED = ('xconv_params', 'fc_params', 'with_global', 'sampling', 'with_X_transformation', 'sorting_method')
+DEFAULTS = dict(num_class=15, sample_num=1024, batch_size=32, num_epochs=400, learning_rate_base=0.01, decay_steps=8000,
+                decay_rate=0.5, learning_rate_min=1e-6, weight_decay=1e-5, jitter=0.0, jitter_val=0.0,
+                rotation_range=[0, math.pi, 0, 'u'], rotation_range_val=[0, 0, 0, 'u'], rotation_order='rxyz',
+                scaling_range=[0.1, 0.1, 0.1, 'g'], scaling_range_val=[0, 0, 0, 'u'], optimizer='adam', epsilon=1e-2,
+                data_dim=6, use_extra_features=False)
+
+
+def xconv_params(rows):
+    return [dict(zip(_XCONV, r)) for r in rows]
+
+
+def fc_params(rows):
+    return [dict(zip(_FC, r)) for r in rows]
+
+
+def make(**kw):
+    """a setting: DEFAULTS (the trainer's numbers of modelnet_x3_l4) overridden by kw"""
+    return as_setting(SimpleNamespace(**dict(DEFAULTS, **kw)))
+
+
+def as_setting(obj):
+    """`obj` itself after checking that it carries what the trunk reads; trainer numbers it lacks come from DEFAULTS"""
+    missing = [a for a in REQUIRED if not hasattr(obj, a)]
+    if missing:
+        raise AttributeError("PointCNN setting lacks %s" % ", ".join(missing))
+    for k, v in DEFAULTS.items():
+        if not hasattr(obj, k):
+            setattr(obj, k, v)
+    return obj
+
+
+_x = 3
+modelnet_x3_l4 = make(
+    xconv_params=xconv_params([(8, 1, -1, 16 * _x, []),
+                               (12, 2, 384, 32 * _x, []),
+                               (16, 2, 128, 64 * _x, []),
+                               (16, 3, 128, 128 * _x, [])]),
+    fc_params=fc_params([(128 * _x, 0.0), (64 * _x, 0.8)]),
+    with_global=True, sampling='random', with_X_transformation=True, sorting_method=None)
+
+SETTINGS = {"modelnet_x3_l4": modelnet_x3_l4}
+
+
+def get(name):
+    if name not in SETTINGS:
+        raise KeyError("--setting %s: known settings are %s" % (name, ", ".join(sorted(SETTINGS))))
+    return SETTINGS[name]

@@ -72,19 +72,24 @@ def model_loss(mod, logits, labels, end_points):
 
 
 @torch.no_grad()
-def eval_one_epoch(net, data, labels, batch_size, num_votes=1, device="cuda:0", num_classes=NUM_CLASSES, loss_fn=None):
+def eval_one_epoch(net, data, labels, batch_size, num_votes=1, device="cuda:0", num_classes=NUM_CLASSES, loss_fn=None,
+                   scores_fn=None):
     """net: graph.Model of a classifier get_model; data (K,N,3), labels (K,).  Whole batches only (like the
     reference: num_batches = K // BATCH_SIZE).  loss_fn(logits, labels, end_points) -> scalar: the reference's
     per-vote loss, averaged over the votes and weighted by the batch size (`:187,198`) -> "mean_loss".  A model that
-    returns bare logits passes end_points = None."""
+    returns bare logits passes end_points = None.  scores_fn: the model module's optional class_scores hook, applied
+    to every vote's logits before the votes are summed (PointCNN: the softmax summed over the points); None: identity."""
     preds, seen = [], []
+    if scores_fn is None:
+        scores_fn = lambda logits: logits                              # noqa: E731
     labels = _host(labels)
     loss_sum = 0.0
     for b in range(data.shape[0] // batch_size):
         pts = torch.as_tensor(data[b * batch_size:(b + 1) * batch_size], dtype=torch.float32, device=device)
         lab_b = np.asarray(labels[b * batch_size:(b + 1) * batch_size])
         if loss_fn is None:
-            logits = vote_logits(lambda p: split_output(net(p.contiguous(), is_training=False))[0], pts, num_votes)
+            logits = vote_logits(lambda p: scores_fn(split_output(net(p.contiguous(), is_training=False))[0]), pts,
+                                 num_votes)
         else:
             y = torch.as_tensor(lab_b.astype(np.int64), device=device)
             losses = []
@@ -92,7 +97,7 @@ def eval_one_epoch(net, data, labels, batch_size, num_votes=1, device="cuda:0", 
             def predict(p):
                 out, end_points = split_output(net(p.contiguous(), is_training=False))
                 losses.append(loss_fn(out, y, end_points))
-                return out
+                return scores_fn(out)
             logits = vote_logits(predict, pts, num_votes)
             loss_sum += float(torch.stack(losses).sum()) * batch_size / float(num_votes)
         preds.append(logits.argmax(dim=1).cpu().numpy())
@@ -243,7 +248,8 @@ def evaluate(args):
         cur, lab = data_utils.get_current_data_h5(data, labels, args.num_point, rng=rng)  # :159
     lab = np.squeeze(lab)
     ev = eval_one_epoch(net, cur, lab, args.batch_size, num_votes=args.num_votes, device=dev,
-                        num_classes=args.num_class, loss_fn=lambda out, y, ep: model_loss(mod, out, y, ep))
+                        num_classes=args.num_class, loss_fn=lambda out, y, ep: model_loss(mod, out, y, ep),
+                        scores_fn=getattr(mod, "class_scores", None))
     with open(os.path.join(args.dump_dir, "pred_label.txt"), "w") as fout:                 # :209
         for p, l in zip(ev["pred"], ev["label"]):
             fout.write("%s, %s\n" % (names[p], names[l]))

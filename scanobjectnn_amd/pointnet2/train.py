@@ -36,7 +36,11 @@ MODELS = {"pointnet2_cls_ssg": "scanobjectnn_amd.pointnet2.pointnet2_cls_ssg",
           "pointnet2_cls_partseg": "scanobjectnn_amd.pointnet2.pointnet2_cls_partseg",
           "dgcnn": "scanobjectnn_amd.dgcnn.dgcnn", "dgcnn_bga": "scanobjectnn_amd.dgcnn.dgcnn_bga",
           "spidercnn_cls_xyz": "scanobjectnn_amd.spidercnn.spidercnn_cls_xyz",
-          "3dmfv_net_cls": "scanobjectnn_amd.mfv3d.mfv3d_net_cls"}
+          "3dmfv_net_cls": "scanobjectnn_amd.mfv3d.mfv3d_net_cls",
+          "pointcnn_cls": "scanobjectnn_amd.pointcnn.pointcnn_cls"}
+# flags a model may take from its own setting when the command line leaves them out (the module's flag_defaults);
+# for every other model these are the defaults
+FLAG_DEFAULTS = {"max_epoch": 250, "batch_size": 16, "learning_rate": 0.001, "decay_step": 200000, "decay_rate": 0.7}
 
 
 def add_model_flags(p):
@@ -46,6 +50,7 @@ def add_model_flags(p):
     p.add_argument("--gmm_type", default="grid", help="3dmfv_net_cls: grid (learn, the EM mixture, is out of scope and raises)")
     p.add_argument("--num_gaussians", type=int, default=5, help="3dmfv_net_cls: grid subdivisions per axis (5: 125 Gaussians)")
     p.add_argument("--gmm_variance", type=float, default=0.04, help="3dmfv_net_cls: variance of every grid Gaussian")
+    p.add_argument("--setting", default="modelnet_x3_l4", help="pointcnn_cls: the setting (PointCNN/train.py:41)")
 
 
 def model_fn(mod, args, dev):
@@ -76,13 +81,13 @@ def parse_args(argv=None):
     p.add_argument("--center_data", type=_flag, default=True, help="subtract every cloud's centroid (:32)")
     p.add_argument("--num_class", type=int, default=15)             # :33
     p.add_argument("--num_point", type=int, default=1024)           # :38
-    p.add_argument("--max_epoch", type=int, default=250)            # :39
-    p.add_argument("--batch_size", type=int, default=16, help="GLOBAL batch, split over the ranks")
-    p.add_argument("--learning_rate", type=float, default=0.001)
+    p.add_argument("--max_epoch", type=int, default=None, help="[250]")             # :39
+    p.add_argument("--batch_size", type=int, default=None, help="GLOBAL batch, split over the ranks [16]")
+    p.add_argument("--learning_rate", type=float, default=None, help="[0.001]")
     p.add_argument("--momentum", type=float, default=0.9)           # :41
     p.add_argument("--optimizer", default="adam", choices=["adam", "momentum"])   # :42
-    p.add_argument("--decay_step", type=int, default=200000)
-    p.add_argument("--decay_rate", type=float, default=0.7)
+    p.add_argument("--decay_step", type=int, default=None, help="[200000]")
+    p.add_argument("--decay_rate", type=float, default=None, help="[0.7]")
     p.add_argument("--normal", action="store_true", help="accepted for CLI compatibility (:46); the reference never reads it")
     p.add_argument("--seg_weight", type=float, default=0.5)         # train_seg.py:35 (typed properly)
     p.add_argument("--train_file", default="")
@@ -95,7 +100,13 @@ def parse_args(argv=None):
     p.add_argument("--deterministic", action="store_true",
                    help="bit-reproducible backward passes: ordered owner sums instead of float atomics (slower)")
     add_model_flags(p)
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    mod = importlib.import_module(MODELS[args.model])
+    own = mod.flag_defaults(args) if hasattr(mod, "flag_defaults") else {}
+    for name, default in FLAG_DEFAULTS.items():
+        if getattr(args, name) is None:
+            setattr(args, name, own.get(name, default))
+    return args
 
 
 def _load(path, with_mask, num, n_pts, seed, args):
@@ -189,7 +200,10 @@ def train(args):
     net = Model(model_fn(mod, args, dev), device=dev, seed=args.seed, **kw).build(example)
     fp = TU.FlatParams(net).enable_overlap(world)        # N > 1: gradient ranges travel while the backward pass runs
     D.broadcast_(fp.flat)
-    opt = TU.make_optimizer(args.optimizer, fp, args.momentum)
+    own = mod.trainer(args) if hasattr(mod, "trainer") else None   # a model with trainer numbers of its own (PointCNN)
+    opt = TU.make_optimizer(args.optimizer, fp, args.momentum, **({"epsilon": own.adam_epsilon} if own else {}))
+    augment = own.augment if own else getattr(mod, "augment", None)
+    scores = getattr(mod, "class_scores", lambda logits: logits)     # what argmax and the votes are taken on
     step = 0
     if rank == 0:
         os.makedirs(args.log_dir, exist_ok=True)
@@ -203,13 +217,16 @@ def train(args):
         for b in range(nb):
             sl = slice(b * args.batch_size + lo, b * args.batch_size + hi)
             x = cur[sl]
-            if not args.no_augment and hasattr(mod, "augment"):       # a family with its own augmentation (3DmFV-Net)
-                x = mod.augment(x, generator=gen)
+            if not args.no_augment and augment is not None:           # a family with its own augmentation (3DmFV-Net)
+                x = augment(x, generator=gen)
             elif not args.no_augment:
                 x = provider.jitter_point_cloud(provider.rotate_point_cloud(x, generator=gen), generator=gen)
             x = x.contiguous()
             y = lab[sl]
-            lr = TU.get_learning_rate(step, args.batch_size, args.learning_rate, args.decay_step, args.decay_rate)
+            if own:                                                   # the model's schedule (PointCNN: in steps) on the same flags
+                lr = own.learning_rate(step)
+            else:
+                lr = TU.get_learning_rate(step, args.batch_size, args.learning_rate, args.decay_step, args.decay_rate)
             bn_decay = TU.get_bn_decay(step, args.batch_size, float(args.decay_step))
             fp.begin_step()
             out = net(x, is_training=True, bn_decay=bn_decay)
@@ -222,7 +239,10 @@ def train(args):
             else:
                 logits, end_points = EV.split_output(out)      # SpiderCNN returns bare logits
                 loss = EV.model_loss(mod, logits, y, end_points)
-            loss.backward()
+            if own:                                                   # minimised, not reported (PointCNN/train.py:171)
+                (loss + own.regularization_loss(net)).backward()
+            else:
+                loss.backward()
             fp.collect_mean(world)
             opt.step(lr)
             step += 1
@@ -232,7 +252,7 @@ def train(args):
                     tot[1] += (out.argmax(dim=2) == m).sum()
                     tot[2] += per_rank * args.num_point
                 else:
-                    tot[1] += (EV.split_output(out)[0].argmax(dim=1) == y).sum()
+                    tot[1] += (scores(EV.split_output(out)[0]).argmax(dim=1) == y).sum()
                     tot[2] += per_rank
         if D.dist.is_initialized() and world > 1:
             D.dist.all_reduce(tot)
@@ -247,7 +267,7 @@ def train(args):
         elif with_mask:
             ev = EV.eval_seg_one_epoch(net, td, tl, tm, per_rank, device=dev)
         else:
-            ev = EV.eval_one_epoch(net, td, tl, per_rank, device=dev, num_classes=args.num_class)
+            ev = EV.eval_one_epoch(net, td, tl, per_rank, device=dev, num_classes=args.num_class, scores_fn=scores)
         rec = {"epoch": epoch, "mean_loss": loss_sum / max(nb, 1), "train_acc": correct / max(seen, 1),
                "eval_acc": ev["accuracy"], "eval_avg_class_acc": ev["avg_class_acc"],
                "clouds_per_s": nb * args.batch_size / (time.time() - t0)}

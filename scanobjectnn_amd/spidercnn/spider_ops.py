@@ -91,15 +91,7 @@ def group_norm_relu_bwd(dout, x, y, gamma, mean, rstd, groups):
     return dx, dgamma, dbeta
 
 
-def scatter_grouped(dfg, idx, n):
-    """dfeat (B,N,C) = the scatter-add of dfeat_grouped (B,N,k,C) through idx (pcops_group_point_grad's contract; the
-    ordered owner walk in deterministic mode)"""
-    b, m, k, c = dfg.shape
-    if _lib.deterministic():
-        return _lib.scatter_rows_sorted(idx.view(b, m * k), dfg.view(b, m * k, c), n)
-    out = torch.empty((b, n, c), dtype=torch.float32, device=dfg.device)
-    _lib.call("pcops_group_point_grad", b, n, c, m, k, dfg.data_ptr(), idx.data_ptr(), out.data_ptr())
-    return out
+scatter_grouped = _lib.scatter_grouped      # (dfeat_grouped (B,N,k,C), idx, n) -> dfeat (B,N,C); shared with X-Conv
 
 
 class SpiderConvFn(torch.autograd.Function):

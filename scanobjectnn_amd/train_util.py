@@ -226,10 +226,11 @@ class TFMomentum:
         self.fp.flat.add_(self.accum, alpha=-lr)
 
 
-def make_optimizer(name, flat, momentum=0.9):
-    """`--optimizer adam|momentum` of the reference trainers (`pointnet2/train.py:41-42,165-168`)"""
+def make_optimizer(name, flat, momentum=0.9, epsilon=1e-8):
+    """`--optimizer adam|momentum` of the reference trainers (`pointnet2/train.py:41-42,165-168`); epsilon: Adam's, for a
+    model whose trainer sets its own (PointCNN: 1e-2)"""
     if name == "adam":
-        return TFAdam(flat)
+        return TFAdam(flat, epsilon=epsilon)
     if name == "momentum":
         return TFMomentum(flat, momentum)
     raise ValueError("optimizer must be 'adam' or 'momentum', got %r" % (name,))
