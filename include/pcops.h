@@ -83,8 +83,13 @@ int pcops_abi_version(void);
  *                                      takes its wave-per-group kernel (a row's hits as ballots, the next row's W^T reads in
  *                                      flight) at every supported shape -- Kp = 64 / 128, S <= 64 and S <= 128; same rows, same
  *                                      rowmap, the former kernel's bits (DESIGN.md sections 4.21, 4.23).  0: the former kernels
+ *   PCOPS_OPT_XCONV_CHANNEL_GROUPS     0 / 1 (default): pcops_xconv_fwd and pcops_xconv_dgrad_ws of more than 256 channels (more than
+ *                                      16 channel tiles) spread the tiles over pcops_xconv_channel_groups workgroups per 16
+ *                                      points, at most 8 tiles each; out, dlifted and dfts_grouped keep the one-group kernel's
+ *                                      bits, dX is the groups' partial sums added in ascending order.
+ *                                      0: one group everywhere.  Seeded by PCOPS_XCONV_GROUPS
  * pcops_set_option returns the PREVIOUS value (>= 0) or PCOPS_ERR_BAD_ARGUMENT.  The environment variables of rounds 3-4
- * (PCOPS_GEMM_BF3, PCOPS_WGRAD_BF3, PCOPS_BWD_FUSED_DX3, PCOPS_KNN_F16; round 6: PCOPS_DGRAD_BF3, PCOPS_BWD_FUSED_GW; later: PCOPS_GRAM_BF3, PCOPS_POOL_TOP_ROWS_PIPE) only seed the initial values (test overrides). */
+ * (PCOPS_GEMM_BF3, PCOPS_WGRAD_BF3, PCOPS_BWD_FUSED_DX3, PCOPS_KNN_F16; round 6: PCOPS_DGRAD_BF3, PCOPS_BWD_FUSED_GW; later: PCOPS_GRAM_BF3, PCOPS_POOL_TOP_ROWS_PIPE, PCOPS_XCONV_GROUPS) only seed the initial values (test overrides). */
 typedef enum pcops_option {
     PCOPS_OPT_GEMM_SPLIT_BF16 = 1,
     PCOPS_OPT_WGRAD_SPLIT_BF16 = 2,
@@ -96,7 +101,8 @@ typedef enum pcops_option {
     PCOPS_OPT_XYZ_STATS_MOMENTS = 8,
     PCOPS_OPT_GRAM_SPLIT_BF16 = 9,
     PCOPS_OPT_POOL_TOP_ROWS_PIPELINED = 10,
-    PCOPS_OPT_COUNT = 11
+    PCOPS_OPT_XCONV_CHANNEL_GROUPS = 11,
+    PCOPS_OPT_COUNT = 12
 } pcops_option;
 int pcops_set_option(int option, int value);
 int pcops_get_option(int option);
@@ -1016,9 +1022,24 @@ int pcops_conv3d_wgrad(int b, int r, int k, int cin, int cout, const float *x, c
  * pcops_xconv_wgrad_workspace_bytes bytes of caller-owned workspace (0 with one split: direct store, workspace may be NULL)
  * and are added in ascending order.  Every output is written whole; every sum is taken in a fixed order with no float
  * atomics, so two calls give the same bits whatever pcops_set_deterministic says.
+ * Channel groups: a wave walks the 16-channel tiles of its point one after the other, so a wide layer (the X-DeConv layers of
+ * pointcnn_seg: up to 576 channels on 4096 points) is a long dependent chain on few waves.  With tiles = ceil(c / 16) > 16
+ * and PCOPS_OPT_XCONV_CHANNEL_GROUPS on, fwd and dgrad_ws launch pcops_xconv_channel_groups = ceil(tiles / 8) workgroups per
+ * 16 points, group g owning the tiles [g t, (g + 1) t), t = ceil(tiles / groups) (no group is empty, none holds more than 8),
+ * and staging only its own columns of wd.  Channels never mix in out, dlifted and dfts_grouped: the same bits as with one group.
+ * dX sums over the channels: with more than one group, group g writes its (b p, k, k) partial sum to slice g of
+ * pcops_xconv_dgrad_workspace_bytes = groups b p k k 4 bytes of caller-owned workspace and one pass adds the slices in
+ * ascending order (0 bytes and workspace NULL with one group, where dgrad_ws launches what dgrad launches).  pcops_xconv_dgrad
+ * itself always runs one group.  c <= 256 is one group whatever the option says; the query answers 0 for a shape the
+ * launchers refuse and for b == 0.
  * Supported (pcops_xconv_supported): 1 <= k <= 16, c1 >= 1, c2 >= 0, 1 <= dm <= 4, c dm <= 960 (16 rows of wd in LDS);
  * b p k max(c dm, k) < 2^31 and b n c2 < 2^31.  PCOPS_ERR_UNSUPPORTED outside, before any launch and any pointer check. */
 int pcops_xconv_supported(int k, int c1, int c2, int dm);
+int pcops_xconv_channel_groups(int b, int n, int p, int k, int c1, int c2, int dm);
+unsigned long long pcops_xconv_dgrad_workspace_bytes(int b, int n, int p, int k, int c1, int c2, int dm);
+int pcops_xconv_dgrad_ws(int b, int n, int p, int k, int c1, int c2, int dm, const float *lifted, const float *fts,
+                         const int *idx, const float *X, const float *wd, const float *dout, float *dX, float *dlifted,
+                         float *dfts_grouped, void *workspace, pcops_stream_t stream);
 int pcops_xconv_fwd(int b, int n, int p, int k, int c1, int c2, int dm, const float *lifted, const float *fts,
                     const int *idx, const float *X, const float *wd, float *out, pcops_stream_t stream);
 int pcops_xconv_dgrad(int b, int n, int p, int k, int c1, int c2, int dm, const float *lifted, const float *fts,

@@ -201,6 +201,7 @@ OPT_SCATTER_QFORM = 7                                            # pcops_sa_scat
 OPT_XYZ_STATS_MOMENTS = 8                                        # pcops_sa_gather_fwd(_rows): arithmetic first layer's statistics
 OPT_GRAM_SPLIT_BF16 = 9                                          # pcops_mlp_gram_rows at Kp == 128: split operands on the bf16 pipe
 OPT_POOL_TOP_ROWS_PIPELINED = 10                                 # pcops_mlp_pool_top_wsparse_rows: software-pipelined kernel
+OPT_XCONV_CHANNEL_GROUPS = 11                                    # pcops_xconv_fwd / _dgrad_ws: channel tiles of a wide layer over the grid
 
 
 def set_option(option, value):

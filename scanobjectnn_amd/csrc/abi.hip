@@ -63,6 +63,7 @@ void options_init() {
         g_options[PCOPS_OPT_XYZ_STATS_MOMENTS].store(env_int("PCOPS_XYZ_STATS_MOMENTS", 0) != 0);
         g_options[PCOPS_OPT_GRAM_SPLIT_BF16].store(env_int("PCOPS_GRAM_BF3", 1) != 0);
         g_options[PCOPS_OPT_POOL_TOP_ROWS_PIPELINED].store(env_int("PCOPS_POOL_TOP_ROWS_PIPE", 1) != 0);
+        g_options[PCOPS_OPT_XCONV_CHANNEL_GROUPS].store(env_int("PCOPS_XCONV_GROUPS", 1) != 0);
         g_options_init.store(1, std::memory_order_release);
     }
     busy.clear(std::memory_order_release);

@@ -20,6 +20,14 @@
 //   dwd[k',ch,m] = sum_q T[q,k',ch] dout[q, ch dm + m]: T recomputed by the forward's MFMA; the lane that holds
 //   T[k',ch] keeps the sum over its points in registers.  Row splits -> workspace -> one fixed-order pass.
 // Every sum is taken in a fixed order; there is no float atomic in this file.
+//
+// Channel groups (WIDE).  A wave walks its point's channel tiles one after the other, each a dependent chain (load, 4 MFMA,
+// shuffle, store), and the launch has one wave per point: a layer of 36 tiles on 4096 points is a long chain on about one
+// wave per SIMD.  The tiles are independent, so with more than kOneGroupTiles of them the forward and the data gradient put
+// them on the grid's y axis: group y owns the tiles [y t, (y + 1) t), t <= kGroupTiles, stages only its own columns of wd
+// (row stride t 16 dm, zero past its last channel) and runs the same arithmetic per element -- out, dlifted and dfts_grouped
+// keep the one-group bits.  dX is a sum over the tiles: group y stores its partial to slice y of a workspace and
+// xconv_reduce_kernel adds the slices in ascending order.  WIDE = false is the one-group kernel as it was.
 #include <algorithm>
 
 #include "common.h"
@@ -35,6 +43,8 @@ constexpr int kMaxCD = 960;      // c dm: 16 rows of it are 61 440 bytes of LDS
 constexpr int kSplitCap = 64;    // weight gradient: row splits (a power of two)
 constexpr int kSplitRows = 16;   // ... each a whole number of 16-point steps
 constexpr int kTargetWGs = 512;
+constexpr int kOneGroupTiles = 16;  // forward / dgrad: up to this many channel tiles (c <= 256) one group walks them all
+constexpr int kGroupTiles = 8;      // ... beyond it ceil(tiles / 8) groups of at most 8 tiles
 
 typedef float f4 __attribute__((ext_vector_type(4)));
 
@@ -47,6 +57,30 @@ __device__ __forceinline__ void stage_wd(const Shape &s, const float *__restrict
     const int len = kKP * s.cd, have = s.K * s.cd;
     for (int e = threadIdx.x; e < len; e += kThreads) wds[e] = e < have ? wd[e] : 0.f;
     __syncthreads();
+}
+
+// the channels [lo, hi) a workgroup owns and the row stride of its wd image in LDS
+struct Slice {
+    int lo, hi, ld;
+};
+
+// WIDE: group blockIdx.y of tpg tiles each; its image is wd[:, lo:hi, :] -> LDS [16][tpg 16 dm], zero past K rows and past hi.
+// Otherwise all of it, staged as above.
+template <int DM, bool WIDE>
+__device__ __forceinline__ Slice stage_slice(const Shape &s, int tpg, const float *__restrict__ wd, float *wds) {
+    if constexpr (!WIDE) {
+        stage_wd(s, wd, wds);
+        return Slice{0, s.c, s.cd};
+    } else {
+        const int lo = min((int)blockIdx.y * tpg * kCT, s.c), hi = min(lo + tpg * kCT, s.c);
+        const int ld = tpg * kCT * DM, have = (hi - lo) * DM;
+        for (int e = threadIdx.x; e < kKP * ld; e += kThreads) {
+            const int row = e / ld, col = e - row * ld;
+            wds[e] = (row < s.K && col < have) ? wd[(size_t)row * s.cd + lo * DM + col] : 0.f;
+        }
+        __syncthreads();
+        return Slice{lo, hi, ld};
+    }
 }
 
 // Fin[q, k, ch], zero outside K x c
@@ -77,13 +111,14 @@ __device__ __forceinline__ f4 xfin_tile(const Shape &s, long long q, int c0, int
 }
 
 // ---------------------------------------------------------------------------------------------------------------- forward
-template <int DM>
-__global__ void __launch_bounds__(kThreads) xconv_fwd_kernel(Shape s, long long P, const float *__restrict__ lifted,
+// grid (ceil(P / 16), groups); tpg: tiles per group (read by WIDE only)
+template <int DM, bool WIDE>
+__global__ void __launch_bounds__(kThreads) xconv_fwd_kernel(Shape s, long long P, int tpg, const float *__restrict__ lifted,
                                                              const float *__restrict__ fts, const int *__restrict__ idx,
                                                              const float *__restrict__ X, const float *__restrict__ wd,
                                                              float *__restrict__ out) {
     extern __shared__ float wds[];
-    stage_wd(s, wd, wds);
+    const Slice sl = stage_slice<DM, WIDE>(s, tpg, wd, wds);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, l15 = lane & 15;
     const long long q0 = (long long)blockIdx.x * kPointsPerWG;
     const long long qend = q0 + kPointsPerWG < P ? q0 + kPointsPerWG : P;
@@ -91,16 +126,16 @@ __global__ void __launch_bounds__(kThreads) xconv_fwd_kernel(Shape s, long long 
         float xa[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) xa[j] = load_x(s, q, l15, 4 * j + g, X);
-        for (int c0 = 0; c0 < s.c; c0 += kCT) {
+        for (int c0 = sl.lo; c0 < sl.hi; c0 += kCT) {
             const f4 t = xfin_tile(s, q, c0, g, l15, xa, lifted, fts, idx);
             const int ch = c0 + l15;
-            const bool ok = ch < s.c;
+            const bool ok = ch < sl.hi;
 #pragma unroll
             for (int m = 0; m < DM; ++m) {
                 float v = 0.f;
                 if (ok) {
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) v = fmaf(wds[(4 * g + r) * s.cd + ch * DM + m], t[r], v);
+                    for (int r = 0; r < 4; ++r) v = fmaf(wds[(4 * g + r) * sl.ld + (ch - sl.lo) * DM + m], t[r], v);
                 }
                 v += __shfl_xor(v, 16);
                 v += __shfl_xor(v, 32);
@@ -111,24 +146,27 @@ __global__ void __launch_bounds__(kThreads) xconv_fwd_kernel(Shape s, long long 
 }
 
 // ---------------------------------------------------------------------------------------------------------- data gradient
-// dT[kp][ch] = sum_m wd[kp,ch,m] dout[q, ch dm + m]; zero past c (rows past K are zero in wds)
+// dT[kp][ch] = sum_m wd[kp,ch,m] dout[q, ch dm + m]; zero past the slice (rows past K are zero in wds)
 template <int DM>
-__device__ __forceinline__ float dt_at(const Shape &s, const float *wds, const float *__restrict__ dyq, int kp, int ch) {
-    if (ch >= s.c) return 0.f;
+__device__ __forceinline__ float dt_at(const Slice &sl, const float *wds, const float *__restrict__ dyq, int kp, int ch) {
+    if (ch >= sl.hi) return 0.f;
     float v = 0.f;
 #pragma unroll
-    for (int m = 0; m < DM; ++m) v = fmaf(wds[kp * s.cd + ch * DM + m], dyq[ch * DM + m], v);
+    for (int m = 0; m < DM; ++m) v = fmaf(wds[kp * sl.ld + (ch - sl.lo) * DM + m], dyq[ch * DM + m], v);
     return v;
 }
 
-template <int DM>
-__global__ void __launch_bounds__(kThreads) xconv_dgrad_kernel(Shape s, long long P, const float *__restrict__ lifted,
+// grid (ceil(P / 16), groups).  WIDE: dX is the workspace [groups][P][K][K], group blockIdx.y stores its partial sum to
+// its own slice; dlifted and dfg are per channel and go straight out.
+template <int DM, bool WIDE>
+__global__ void __launch_bounds__(kThreads) xconv_dgrad_kernel(Shape s, long long P, int tpg, const float *__restrict__ lifted,
                                                                const float *__restrict__ fts, const int *__restrict__ idx,
                                                                const float *__restrict__ X, const float *__restrict__ wd,
                                                                const float *__restrict__ dy, float *__restrict__ dX,
                                                                float *__restrict__ dlifted, float *__restrict__ dfg) {
     extern __shared__ float wds[];
-    stage_wd(s, wd, wds);
+    const Slice sl = stage_slice<DM, WIDE>(s, tpg, wd, wds);
+    if constexpr (WIDE) dX += (size_t)blockIdx.y * P * s.K * s.K;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, l15 = lane & 15;
     const long long q0 = (long long)blockIdx.x * kPointsPerWG;
     const long long qend = q0 + kPointsPerWG < P ? q0 + kPointsPerWG : P;
@@ -138,15 +176,15 @@ __global__ void __launch_bounds__(kThreads) xconv_dgrad_kernel(Shape s, long lon
 #pragma unroll
         for (int j = 0; j < 4; ++j) xt[j] = load_x(s, q, 4 * j + g, l15, X);
         f4 accX = {0.f, 0.f, 0.f, 0.f};
-        for (int c0 = 0; c0 < s.c; c0 += kCT) {
+        for (int c0 = sl.lo; c0 < sl.hi; c0 += kCT) {
             // dFin[k = 4 g + reg][ch = c0 + l15] = sum_k' X[k',k] dT[k',ch]
             f4 accF = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int j = 0; j < 4; ++j)
-                accF = __builtin_amdgcn_mfma_f32_16x16x4f32(xt[j], dt_at<DM>(s, wds, dyq, 4 * j + g, c0 + l15), accF, 0,
+                accF = __builtin_amdgcn_mfma_f32_16x16x4f32(xt[j], dt_at<DM>(sl, wds, dyq, 4 * j + g, c0 + l15), accF, 0,
                                                             0, 0);
             const int ch = c0 + l15;
-            if (ch < s.c) {
+            if (ch < sl.hi) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int k = 4 * g + r;
@@ -159,7 +197,7 @@ __global__ void __launch_bounds__(kThreads) xconv_dgrad_kernel(Shape s, long lon
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int chA = c0 + 4 * j + g;
-                accX = __builtin_amdgcn_mfma_f32_16x16x4f32(dt_at<DM>(s, wds, dyq, l15, chA),
+                accX = __builtin_amdgcn_mfma_f32_16x16x4f32(dt_at<DM>(sl, wds, dyq, l15, chA),
                                                             load_fin(s, q, l15, chA, lifted, fts, idx), accX, 0, 0, 0);
             }
         }
@@ -174,7 +212,7 @@ __global__ void __launch_bounds__(kThreads) xconv_dgrad_kernel(Shape s, long lon
 // -------------------------------------------------------------------------------------------------------- weight gradient
 // grid (ceil(c / 16), splits).  Split z takes the points [z chunk, (z + 1) chunk), its four waves every fourth of them in
 // ascending order; the waves' sums are added in wave order through LDS.  With splits > 1 the result goes to
-// ws[z][K][c][dm] (a split without points stores zeros) and xconv_wgrad_reduce_kernel adds the splits in ascending order.
+// ws[z][K][c][dm] (a split without points stores zeros) and xconv_reduce_kernel adds the splits in ascending order.
 template <int DM>
 __global__ void __launch_bounds__(kThreads) xconv_wgrad_kernel(Shape s, long long P, long long chunk,
                                                                const float *__restrict__ lifted,
@@ -226,8 +264,10 @@ __global__ void __launch_bounds__(kThreads) xconv_wgrad_kernel(Shape s, long lon
     }
 }
 
-__global__ void xconv_wgrad_reduce_kernel(int len, int splits, const float *__restrict__ ws, float *__restrict__ out) {
-    const int i = blockIdx.x * kThreads + threadIdx.x;
+// out[i] = ws[0][i] + ws[1][i] + ... in ascending order: the weight gradient's row splits and the data gradient's channel
+// groups of dX
+__global__ void xconv_reduce_kernel(int len, int splits, const float *__restrict__ ws, float *__restrict__ out) {
+    const long long i = (long long)blockIdx.x * kThreads + threadIdx.x;
     if (i >= len) return;
     float v = 0.f;
     for (int z = 0; z < splits; ++z) v += ws[(size_t)z * len + i];
@@ -266,9 +306,52 @@ long long wgrad_chunk(long long P, int splits) {
     return (per + kSplitRows - 1) / kSplitRows * kSplitRows;
 }
 
+// forward / dgrad: one group up to 16 channel tiles (c <= 256), else ceil(tiles / 8); no group is empty and none holds more
+// than 8 tiles for any tile count (tests/test_xdconv_ref_cpu.py walks 1..60)
+int channel_groups(int c) {
+    const int tiles = cdiv(c, kCT);
+    if (tiles <= kOneGroupTiles || pcops_get_option(PCOPS_OPT_XCONV_CHANNEL_GROUPS) == 0) return 1;
+    return cdiv(tiles, kGroupTiles);
+}
+
+int group_tiles(int c, int groups) { return cdiv(cdiv(c, kCT), groups); }
+
+// the data gradient in `groups` channel groups; workspace [groups][P][K][K] with more than one
+int launch_dgrad(const Shape &s, long long P, int dm, int groups, const float *lifted, const float *fts, const int *idx,
+                 const float *X, const float *wd, const float *dout, float *dX, float *dlifted, float *dfg, float *ws,
+                 hipStream_t hs) {
+    return pcops_dispatch<1, 2, 3, 4>(dm, PCOPS_ERR_UNSUPPORTED, [&](auto DM) {
+        constexpr int kDM = decltype(DM)::value;
+        if (groups == 1) {
+            hipLaunchKernelGGL((xconv_dgrad_kernel<kDM, false>), dim3(cdiv(P, kPointsPerWG)), dim3(kThreads),
+                               (size_t)kKP * s.cd * sizeof(float), hs, s, P, 0, lifted, fts, idx, X, wd, dout, dX, dlifted,
+                               dfg);
+        } else {
+            const int tpg = group_tiles(s.c, groups), len = (int)(P * s.K * s.K);
+            hipLaunchKernelGGL((xconv_dgrad_kernel<kDM, true>), dim3(cdiv(P, kPointsPerWG), groups), dim3(kThreads),
+                               (size_t)kKP * tpg * kCT * kDM * sizeof(float), hs, s, P, tpg, lifted, fts, idx, X, wd, dout,
+                               ws, dlifted, dfg);
+            hipLaunchKernelGGL(xconv_reduce_kernel, dim3(cdiv(len, kThreads)), dim3(kThreads), 0, hs, len, groups, ws, dX);
+        }
+        pcops_note_pipe(0);
+        return pcops_launch_status();
+    });
+}
+
 }  // namespace
 
 extern "C" int pcops_xconv_supported(int k, int c1, int c2, int dm) { return supported(k, c1, c2, dm) ? 1 : 0; }
+
+extern "C" int pcops_xconv_channel_groups(int b, int n, int p, int k, int c1, int c2, int dm) {
+    if (check(b, n, p, k, c1, c2, dm) != PCOPS_OK || b == 0) return 0;
+    return channel_groups(c1 + c2);
+}
+
+extern "C" unsigned long long pcops_xconv_dgrad_workspace_bytes(int b, int n, int p, int k, int c1, int c2, int dm) {
+    const int groups = pcops_xconv_channel_groups(b, n, p, k, c1, c2, dm);
+    if (groups <= 1) return 0;
+    return (unsigned long long)groups * b * p * k * k * sizeof(float);
+}
 
 extern "C" int pcops_xconv_fwd(int b, int n, int p, int k, int c1, int c2, int dm, const float *lifted, const float *fts,
                                const int *idx, const float *X, const float *wd, float *out, pcops_stream_t stream) {
@@ -279,10 +362,18 @@ extern "C" int pcops_xconv_fwd(int b, int n, int p, int k, int c1, int c2, int d
     if (c2 > 0) { PCOPS_REQUIRE_PTR(fts); PCOPS_REQUIRE_PTR(idx); }
     const Shape s = make_shape(n, p, k, c1, c2, dm);
     const long long P = (long long)b * p;
-    const size_t lds = (size_t)kKP * s.cd * sizeof(float);
+    const int groups = channel_groups(s.c);
     return pcops_dispatch<1, 2, 3, 4>(dm, PCOPS_ERR_UNSUPPORTED, [&](auto DM) {
-        hipLaunchKernelGGL(xconv_fwd_kernel<decltype(DM)::value>, dim3(cdiv(P, kPointsPerWG)), dim3(kThreads), lds,
-                           as_stream(stream), s, P, lifted, fts, idx, X, wd, out);
+        constexpr int kDM = decltype(DM)::value;
+        if (groups == 1) {
+            hipLaunchKernelGGL((xconv_fwd_kernel<kDM, false>), dim3(cdiv(P, kPointsPerWG)), dim3(kThreads),
+                               (size_t)kKP * s.cd * sizeof(float), as_stream(stream), s, P, 0, lifted, fts, idx, X, wd, out);
+        } else {
+            const int tpg = group_tiles(s.c, groups);
+            hipLaunchKernelGGL((xconv_fwd_kernel<kDM, true>), dim3(cdiv(P, kPointsPerWG), groups), dim3(kThreads),
+                               (size_t)kKP * tpg * kCT * kDM * sizeof(float), as_stream(stream), s, P, tpg, lifted, fts, idx,
+                               X, wd, out);
+        }
         pcops_note_pipe(0);
         return pcops_launch_status();
     });
@@ -297,15 +388,23 @@ extern "C" int pcops_xconv_dgrad(int b, int n, int p, int k, int c1, int c2, int
     PCOPS_REQUIRE_PTR(lifted); PCOPS_REQUIRE_PTR(X); PCOPS_REQUIRE_PTR(wd); PCOPS_REQUIRE_PTR(dout);
     PCOPS_REQUIRE_PTR(dX); PCOPS_REQUIRE_PTR(dlifted);
     if (c2 > 0) { PCOPS_REQUIRE_PTR(fts); PCOPS_REQUIRE_PTR(idx); }
-    const Shape s = make_shape(n, p, k, c1, c2, dm);
-    const long long P = (long long)b * p;
-    const size_t lds = (size_t)kKP * s.cd * sizeof(float);
-    return pcops_dispatch<1, 2, 3, 4>(dm, PCOPS_ERR_UNSUPPORTED, [&](auto DM) {
-        hipLaunchKernelGGL(xconv_dgrad_kernel<decltype(DM)::value>, dim3(cdiv(P, kPointsPerWG)), dim3(kThreads), lds,
-                           as_stream(stream), s, P, lifted, fts, idx, X, wd, dout, dX, dlifted, dfts_grouped);
-        pcops_note_pipe(0);
-        return pcops_launch_status();
-    });
+    return launch_dgrad(make_shape(n, p, k, c1, c2, dm), (long long)b * p, dm, 1, lifted, fts, idx, X, wd, dout, dX, dlifted,
+                        dfts_grouped, nullptr, as_stream(stream));
+}
+
+extern "C" int pcops_xconv_dgrad_ws(int b, int n, int p, int k, int c1, int c2, int dm, const float *lifted,
+                                    const float *fts, const int *idx, const float *X, const float *wd, const float *dout,
+                                    float *dX, float *dlifted, float *dfts_grouped, void *workspace, pcops_stream_t stream) {
+    const int st = check(b, n, p, k, c1, c2, dm);
+    if (st != PCOPS_OK) return st;
+    if (b == 0) return PCOPS_OK;
+    PCOPS_REQUIRE_PTR(lifted); PCOPS_REQUIRE_PTR(X); PCOPS_REQUIRE_PTR(wd); PCOPS_REQUIRE_PTR(dout);
+    PCOPS_REQUIRE_PTR(dX); PCOPS_REQUIRE_PTR(dlifted);
+    if (c2 > 0) { PCOPS_REQUIRE_PTR(fts); PCOPS_REQUIRE_PTR(idx); }
+    const int groups = channel_groups(c1 + c2);
+    if (groups > 1) PCOPS_REQUIRE_PTR(workspace);
+    return launch_dgrad(make_shape(n, p, k, c1, c2, dm), (long long)b * p, dm, groups, lifted, fts, idx, X, wd, dout, dX,
+                        dlifted, dfts_grouped, static_cast<float *>(workspace), as_stream(stream));
 }
 
 extern "C" int pcops_xconv_wgrad_splits(int b, int n, int p, int k, int c1, int c2, int dm) {
@@ -342,7 +441,7 @@ extern "C" int pcops_xconv_wgrad(int b, int n, int p, int k, int c1, int c2, int
         hipLaunchKernelGGL(xconv_wgrad_kernel<decltype(DM)::value>, dim3(cdiv(s.c, kCT), splits), dim3(kThreads), 0, hs, s,
                            P, chunk, lifted, fts, idx, X, dout, splits > 1 ? ws : dwd);
         if (splits > 1)
-            hipLaunchKernelGGL(xconv_wgrad_reduce_kernel, dim3(cdiv(len, kThreads)), dim3(kThreads), 0, hs, len, splits, ws,
+            hipLaunchKernelGGL(xconv_reduce_kernel, dim3(cdiv(len, kThreads)), dim3(kThreads), 0, hs, len, splits, ws,
                                dwd);
         pcops_note_pipe(0);
         return pcops_launch_status();

@@ -1,4 +1,5 @@
-"""X-Conv and the PointCNN trunk -- mirror of `PointCNN/pointcnn.py` (xconv :10-52, PointCNN :55-159).
+"""X-Conv and the PointCNN trunks -- mirror of `PointCNN/pointcnn.py` (xconv :10-52, PointCNN :55-159, PointCNN_SEG
+:161-277, whose encoder loop is the classifier's and is shared here).
 
 The hot path of xconv -- gather_nd of the previous features, the concat with the lifted coordinates, the matmul with the
 X-transform and the depthwise half of fts_conv -- is one contraction (xconv_ops.xconv_contract, csrc/xconv.hip); the
@@ -66,7 +67,19 @@ def sample(pts, P, sampling, tag):
     raise ValueError("%sunknown sampling method %r" % (tag, sampling))
 
 
-class PointCNN:
+def fc_stack(fts, fc_params, name, is_training):
+    """dense + dropout per row of fc_params, the layers named name.format(i) -> [fts, fc_0, fc_1, ...]"""
+    layers = [fts]
+    for layer_idx, layer_param in enumerate(fc_params):
+        fc = pf.dense(layers[-1], layer_param['C'], name.format(layer_idx), is_training)
+        # tf.layers.dropout(rate): `rate` of the units are DROPPED (0.8 on the last layer keeps a fifth)
+        layers.append(torch.nn.functional.dropout(fc, float(layer_param['dropout_rate']), bool(is_training)))
+    return layers
+
+
+class Encoder:
+    """the X-Conv layers of `xconv_params` (:68-131, and again :173-234): layer_pts / layer_fts, entry 0 the input"""
+
     def __init__(self, points, features, is_training, setting):
         xconv_params = setting.xconv_params
         if features is not None:
@@ -102,8 +115,41 @@ class PointCNN:
             fts_list = [self.layer_fts[link][:, :qrs.shape[1]] for link in links if self.layer_fts[link] is not None]
             self.layer_fts.append(torch.cat(fts_list + [fts_xconv], dim=-1) if fts_list else fts_xconv)
 
-        self.fc_layers = [self.layer_fts[-1]]
-        for layer_idx, layer_param in enumerate(setting.fc_params):
-            fc = pf.dense(self.fc_layers[-1], layer_param['C'], 'fc{:d}'.format(layer_idx), is_training)
-            # tf.layers.dropout(rate): `rate` of the units are DROPPED (0.8 on the last layer keeps a fifth)
-            self.fc_layers.append(torch.nn.functional.dropout(fc, float(layer_param['dropout_rate']), bool(is_training)))
+
+
+class PointCNN(Encoder):
+    def __init__(self, points, features, is_training, setting):
+        Encoder.__init__(self, points, features, is_training, setting)
+        self.fc_layers = fc_stack(self.layer_fts[-1], setting.fc_params, 'fc{:d}', is_training)
+
+
+class PointCNN_SEG(Encoder):
+    """mirror of :161-277: the encoder, the classification head on its last features, the X-DeConv decoder back up to the
+    input points, the segmentation head.  An X-DeConv layer is xconv() from the points of encoder layer pts_layer_idx onto
+    those of qrs_layer_idx with depth multiplier 1 and no global branch, then concat with the encoder's features at the
+    query points and a dense layer."""
+
+    def __init__(self, points, features, is_training, setting):
+        Encoder.__init__(self, points, features, is_training, setting)
+        xconv_params = setting.xconv_params
+        N = points.shape[0]
+        self.fc_layers_classification = fc_stack(self.layer_fts[-1], setting.fc_params_classification, 'fc_class_{:d}',
+                                                 is_training)
+
+        for layer_idx, layer_param in enumerate(getattr(setting, 'xdconv_params', [])):
+            tag = 'xdconv_' + str(layer_idx + 1) + '_'
+            K, D, pts_layer_idx, qrs_layer_idx = (layer_param[k] for k in ('K', 'D', 'pts_layer_idx', 'qrs_layer_idx'))
+
+            pts = self.layer_pts[pts_layer_idx + 1]
+            fts = self.layer_fts[pts_layer_idx + 1] if layer_idx == 0 else self.layer_fts[-1]
+            qrs = self.layer_pts[qrs_layer_idx + 1]
+            fts_qrs = self.layer_fts[qrs_layer_idx + 1]
+            C = xconv_params[qrs_layer_idx]['C']
+            C_pts_fts = xconv_params[pts_layer_idx]['C'] // 4
+            fts_xdconv = xconv(pts, fts, qrs, tag, N, K, D, qrs.shape[1], C, C_pts_fts, is_training,
+                               setting.with_X_transformation, 1, setting.sorting_method)
+            fts_concat = torch.cat([fts_xdconv, fts_qrs], dim=-1)
+            self.layer_pts.append(qrs)
+            self.layer_fts.append(pf.dense(fts_concat, C, tag + 'fts_fuse', is_training))
+
+        self.fc_layers_segmentation = fc_stack(self.layer_fts[-1], setting.fc_params_segmentation, 'fc_seg_{:d}', is_training)

@@ -47,13 +47,15 @@ def learning_rate(step, base, decay_steps, decay_rate, lr_min):
     return max(base * decay_rate ** (int(step) // int(decay_steps)), lr_min)
 
 
-def _setting_of(args):
-    return settings.get(getattr(args, "setting", None) or "modelnet_x3_l4")
+def setting_of(args):
+    """--setting, or the setting of --model when the flag is left out (settings.MODEL_DEFAULT)"""
+    return settings.get(getattr(args, "setting", None) or
+                        settings.MODEL_DEFAULT.get(getattr(args, "model", None), "modelnet_x3_l4"))
 
 
 def flag_defaults(args):
     """the trainer flags this model takes from its setting when the command line leaves them out (train.py:76-77)"""
-    s = _setting_of(args)
+    s = setting_of(args)
     return {"learning_rate": s.learning_rate_base, "decay_step": s.decay_steps, "decay_rate": s.decay_rate,
             "batch_size": s.batch_size, "max_epoch": s.num_epochs}
 
@@ -64,7 +66,7 @@ class Trainer:
     has resolved them) with the setting's floor, Adam's epsilon, the regulariser and the augmentation of --setting."""
 
     def __init__(self, args):
-        self.setting = s = _setting_of(args)
+        self.setting = s = setting_of(args)
         given = lambda name, default: default if getattr(args, name, None) is None else getattr(args, name)  # noqa: E731
         self.base = float(given("learning_rate", s.learning_rate_base))
         self.decay_steps = int(given("decay_step", s.decay_steps))
@@ -85,15 +87,18 @@ def trainer(args):
     return Trainer(args)
 
 
-def bind(setting):
+def bind(setting, model=None):
+    """get_model (or another model of the family with the same signature) under `setting`"""
+    model = model or get_model
+
     def bound(point_cloud, is_training, bn_decay=None, num_class=NUM_CLASSES):
-        return get_model(point_cloud, is_training, bn_decay=bn_decay, setting=setting, num_class=num_class)
+        return model(point_cloud, is_training, bn_decay=bn_decay, setting=setting, num_class=num_class)
     return bound
 
 
 def model_fn(args, device=None):
     """the classifier for --setting (modelnet_x3_l4)"""
-    return bind(_setting_of(args))
+    return bind(setting_of(args))
 
 
 def augment(batch, generator=None, setting=settings.modelnet_x3_l4):

@@ -49,13 +49,16 @@ def fwd(lifted, fts, idx, X, wd):
 
 
 def dgrad(lifted, fts, idx, X, wd, dout, need_dfts=True):
-    """-> dX (B,P,K,K), dlifted (B,P,K,c1), dfts_grouped (B,P,K,c2) or None"""
+    """-> dX (B,P,K,K), dlifted (B,P,K,c1), dfts_grouped (B,P,K,c2) or None; a layer of more than 256 channels runs in
+    pcops_xconv_channel_groups groups whose partial dX sums meet in a workspace (PCOPS_XCONV_GROUPS=0: one group)"""
     dims = _dims(lifted, fts, X, wd)
     b, _, p, k, c1, c2, _ = dims
     dX, dl = torch.empty_like(X), torch.empty_like(lifted)
     dfg = torch.empty((b, p, k, c2), dtype=torch.float32, device=X.device) if need_dfts and c2 else None
-    _lib.call("pcops_xconv_dgrad", *dims, lifted.data_ptr(), _lib.ptr(fts), _lib.ptr(idx), X.data_ptr(), wd.data_ptr(),
-              dout.data_ptr(), dX.data_ptr(), dl.data_ptr(), _lib.ptr(dfg))
+    nbytes = int(_lib.load().pcops_xconv_dgrad_workspace_bytes(*dims))
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=X.device) if nbytes else None
+    _lib.call("pcops_xconv_dgrad_ws", *dims, lifted.data_ptr(), _lib.ptr(fts), _lib.ptr(idx), X.data_ptr(), wd.data_ptr(),
+              dout.data_ptr(), dX.data_ptr(), dl.data_ptr(), _lib.ptr(dfg), _lib.ptr(ws))
     return dX, dl, dfg
 
 

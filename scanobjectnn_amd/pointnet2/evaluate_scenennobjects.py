@@ -109,15 +109,18 @@ def eval_one_epoch(net, data, labels, batch_size, num_votes=1, device="cuda:0", 
 
 
 @torch.no_grad()
-def eval_seg_one_epoch(net, data, labels, masks, batch_size, device="cuda:0"):
-    """BGA models: class accuracy + mask accuracy = correct points / (seen clouds * points)"""
+def eval_seg_one_epoch(net, data, labels, masks, batch_size, device="cuda:0", scores_fn=None):
+    """BGA models: class accuracy + mask accuracy = correct points / (seen clouds * points).  scores_fn: the model module's
+    optional class_scores hook on the class head (pointcnn_seg: per-point logits -> the softmax summed over the points)"""
     cls_pred, seen, seg_correct, n_pts = [], [], 0, 0
+    if scores_fn is None:
+        scores_fn = lambda logits: logits                              # noqa: E731
     labels, masks = _host(labels), _host(masks)
     for b in range(data.shape[0] // batch_size):
         sl = slice(b * batch_size, (b + 1) * batch_size)
         pts = torch.as_tensor(data[sl], dtype=torch.float32, device=device)
         class_pred, seg_pred = net(pts.contiguous(), is_training=False)
-        cls_pred.append(class_pred.argmax(dim=1).cpu().numpy())
+        cls_pred.append(scores_fn(class_pred).argmax(dim=1).cpu().numpy())
         seen.append(np.asarray(labels[sl]))
         seg_correct += int((seg_pred.argmax(dim=2).cpu().numpy() == np.asarray(masks[sl])).sum())
         n_pts += masks[sl].size
@@ -151,7 +154,7 @@ def eval_partseg_one_epoch(net, data, parts, batch_size, num_classes=6, device="
 
 # ---- the command line of `pointnet2/evaluate_scenennobjects.py` ----------------------------------------------------
 def parse_args(argv=None):
-    from .train import MODELS, _flag, add_model_flags
+    from .train import MODELS, _flag, add_model_flags, resolve_model_flags
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     p.add_argument("--gpu", type=int, default=0, help="GPU to use (:27)")
     p.add_argument("--model", default="pointnet2_cls_ssg", choices=sorted(MODELS))            # :28
@@ -173,7 +176,7 @@ def parse_args(argv=None):
                    "ScanObjectNN names; the reference reads ../training_data/shape_names_*.txt, :57-62)")
     p.add_argument("--synthetic_clouds", type=int, default=256)
     add_model_flags(p)
-    return p.parse_args(argv)
+    return resolve_model_flags(p.parse_args(argv))
 
 
 def restore(net, model_path, strict=True):
@@ -215,12 +218,12 @@ def load_test_set(args):
 
 def evaluate(args):
     from ..graph import Model
-    from .train import MODELS, model_fn
+    from .train import MASK_MODELS, MODELS, model_fn
     if not torch.cuda.is_available() or not 0 <= args.gpu < torch.cuda.device_count():
         raise RuntimeError("--gpu %d: no such device (%d visible)" % (args.gpu, torch.cuda.device_count()))
     dev = torch.device("cuda", args.gpu)
     torch.cuda.set_device(dev)
-    if args.model.endswith("_bga") or args.model.endswith("_partseg"):
+    if args.model in MASK_MODELS or args.model.endswith("_partseg"):
         raise SystemExit("evaluate_scenennobjects.py evaluates classifiers; the background-aware models have their own "
                          "command line, as in the reference: python -m scanobjectnn_amd.pointnet2."
                          "evaluate_seg_scenennobjects (part models: eval_partseg_one_epoch)")

@@ -7,7 +7,9 @@ the per-class table) and its outputs `dump_dir/pred_label.txt` (`:252`) and `dum
 is taken in file order with the FIRST `num_point` points of every cloud (`get_current_data_withmask_h5(...,
 shuffle=False)`, `:196`); masks are binarised (`convert_to_binary_mask`, `:84`: background -1 -> 0, object parts -> 1).
 Visual dumps (`--visu`, `--visu_mask`: obj / bin / jpg files of the masks, `:254-320`) are out of scope; the flags are
-accepted.
+accepted.  `--model pointcnn_seg` (PointCNN's BGA model, `PointCNN/evaluate_seg_scenennobjects.py`) runs through the same
+loop: its class head is per point, so every vote's class logits go through the model's `class_scores` (the softmax summed
+over the points) before the votes are summed; `--setting` picks its setting (object_dataset_x3).
 
   python -m scanobjectnn_amd.pointnet2.evaluate_seg_scenennobjects --model pointnet2_cls_bga --num_point 1024 \
          --batch_size 32 --model_path log/model.ckpt --test_file test_withmask.npz --num_votes 12
@@ -42,10 +44,14 @@ def seg_summary(class_pred, labels, seg_pred, masks, num_classes=NUM_CLASSES):
 
 @torch.no_grad()
 def eval_seg_votes(net, data, labels, masks, batch_size, num_votes=1, device="cuda:0", num_classes=NUM_CLASSES,
-                   loss_fn=None):
+                   loss_fn=None, scores_fn=None):
     """net: graph.Model of a *_bga get_model -> (class_pred (B,C), seg_pred (B,N,2)); data (K,N,3), labels (K,), masks
     (K,N) in {0,1}.  Whole batches only (`num_batches = K // BATCH_SIZE`, `:203`).  loss_fn(class_pred, seg_pred, labels,
-    masks) -> total loss of one vote; accumulated as loss * batch / num_votes (`:229`)."""
+    masks) -> total loss of one vote; accumulated as loss * batch / num_votes (`:229`).  scores_fn: the model module's
+    optional class_scores hook, applied to every vote's class head before the votes are summed (pointcnn_seg: per-point
+    logits (B,P,C) -> the softmax summed over the points); None: identity."""
+    if scores_fn is None:
+        scores_fn = lambda logits: logits                              # noqa: E731
     labels, masks = _host(labels), _host(masks)
     cls_all, seg_all, seen_lab, seen_mask = [], [], [], []
     loss_sum = 0.0
@@ -58,7 +64,7 @@ def eval_seg_votes(net, data, labels, masks, batch_size, num_votes=1, device="cu
         for vote_idx in range(num_votes):
             rotated = provider.rotate_point_cloud_by_angle(pts, vote_idx / float(num_votes) * math.pi * 2)
             class_pred, seg_pred = net(rotated.contiguous(), is_training=False)
-            cls_sum = class_pred if cls_sum is None else cls_sum + class_pred
+            cls_sum = scores_fn(class_pred) if cls_sum is None else cls_sum + scores_fn(class_pred)
             seg_sum = seg_pred if seg_sum is None else seg_sum + seg_pred
             if loss_fn is not None:
                 loss_sum += float(loss_fn(class_pred, seg_pred, y, mk)) * batch_size / float(num_votes)
@@ -74,10 +80,10 @@ def eval_seg_votes(net, data, labels, masks, batch_size, num_votes=1, device="cu
 
 
 def parse_args(argv=None):
-    from .train import MODELS, _flag
+    from .train import MASK_MODELS, _flag, add_model_flags, resolve_model_flags
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     p.add_argument("--gpu", type=int, default=0, help="GPU to use (:34)")
-    p.add_argument("--model", default="pointnet2_cls_bga", choices=sorted(m for m in MODELS if m.endswith("_bga")))  # :35
+    p.add_argument("--model", default="pointnet2_cls_bga", choices=sorted(MASK_MODELS))                 # :35
     p.add_argument("--batch_size", type=int, default=1)                                       # :36
     p.add_argument("--num_point", type=int, default=1024)                                     # :37
     p.add_argument("--seg_weight", type=float, default=0.5, help="weight of the mask loss in the reported loss (:42)")
@@ -95,7 +101,8 @@ def parse_args(argv=None):
     p.add_argument("--shape_names", default="", help="text file with one class name per line (default: the 15 "
                    "ScanObjectNN names; the reference reads ../training_data/shape_names_ext.txt, :76-77)")
     p.add_argument("--synthetic_clouds", type=int, default=256)
-    return p.parse_args(argv)
+    add_model_flags(p)
+    return resolve_model_flags(p.parse_args(argv))
 
 
 def load_test_set(args):
@@ -120,7 +127,7 @@ def load_test_set(args):
 
 def evaluate(args):
     from ..graph import Model
-    from .train import MODELS
+    from .train import MODELS, model_fn
     if not torch.cuda.is_available() or not 0 <= args.gpu < torch.cuda.device_count():
         raise RuntimeError("--gpu %d: no such device (%d visible)" % (args.gpu, torch.cuda.device_count()))
     dev = torch.device("cuda", args.gpu)
@@ -137,14 +144,15 @@ def evaluate(args):
         print(s)
 
     data, labels, masks = load_test_set(args)
-    net = Model(mod.get_model, device=dev, seed=0).build(torch.zeros((2, args.num_point, 3), device=dev))
+    net = Model(model_fn(mod, args, dev), device=dev, seed=0).build(torch.zeros((2, args.num_point, 3), device=dev))
     info = restore(net, args.model_path)
     log_string("Model restored. (%s, %d variables)" % (info["format"], info["loaded"]))
     # file order, the first num_point points of every cloud (:196, shuffle=False)
     cur, lab, msk = data_utils.get_current_data_withmask_h5(data, labels, masks, args.num_point, shuffle=False)
     lab, msk = np.squeeze(lab), np.squeeze(msk)
     ev = eval_seg_votes(net, cur, lab, msk, args.batch_size, num_votes=args.num_votes, device=dev,
-                        loss_fn=lambda cp, sp, y, mk: mod.get_loss(cp, sp, y, mk, seg_weight=args.seg_weight)[0])
+                        loss_fn=lambda cp, sp, y, mk: mod.get_loss(cp, sp, y, mk, seg_weight=args.seg_weight)[0],
+                        scores_fn=getattr(mod, "class_scores", None))
     with open(os.path.join(args.dump_dir, "pred_label.txt"), "w") as fout:                 # :252
         for p, l in zip(ev["pred"], ev["label"]):
             fout.write("%s, %s\n" % (names[p], names[l]))

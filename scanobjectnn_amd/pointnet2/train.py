@@ -37,7 +37,10 @@ MODELS = {"pointnet2_cls_ssg": "scanobjectnn_amd.pointnet2.pointnet2_cls_ssg",
           "dgcnn": "scanobjectnn_amd.dgcnn.dgcnn", "dgcnn_bga": "scanobjectnn_amd.dgcnn.dgcnn_bga",
           "spidercnn_cls_xyz": "scanobjectnn_amd.spidercnn.spidercnn_cls_xyz",
           "3dmfv_net_cls": "scanobjectnn_amd.mfv3d.mfv3d_net_cls",
-          "pointcnn_cls": "scanobjectnn_amd.pointcnn.pointcnn_cls"}
+          "pointcnn_cls": "scanobjectnn_amd.pointcnn.pointcnn_cls",
+          "pointcnn_seg": "scanobjectnn_amd.pointcnn.pointcnn_seg"}
+# the models that predict a per-point foreground mask beside the class (the reference's train_seg.py trainers)
+MASK_MODELS = frozenset(m for m in MODELS if m.endswith("_bga")) | {"pointcnn_seg"}
 # flags a model may take from its own setting when the command line leaves them out (the module's flag_defaults);
 # for every other model these are the defaults
 FLAG_DEFAULTS = {"max_epoch": 250, "batch_size": 16, "learning_rate": 0.001, "decay_step": 200000, "decay_rate": 0.7}
@@ -50,7 +53,29 @@ def add_model_flags(p):
     p.add_argument("--gmm_type", default="grid", help="3dmfv_net_cls: grid (learn, the EM mixture, is out of scope and raises)")
     p.add_argument("--num_gaussians", type=int, default=5, help="3dmfv_net_cls: grid subdivisions per axis (5: 125 Gaussians)")
     p.add_argument("--gmm_variance", type=float, default=0.04, help="3dmfv_net_cls: variance of every grid Gaussian")
-    p.add_argument("--setting", default="modelnet_x3_l4", help="pointcnn_cls: the setting (PointCNN/train.py:41)")
+    p.add_argument("--setting", default=None, help="pointcnn_cls / pointcnn_seg: the setting (PointCNN/train.py:41) "
+                   "[the model's own: modelnet_x3_l4 / object_dataset_x3].  pointcnn_cls takes the flags it is not given from "
+                   "its setting; pointcnn_seg keeps this file's defaults: give --learning_rate 0.01 --decay_step 8000 "
+                   "--decay_rate 0.5 --batch_size 32 --max_epoch 400 for object_dataset_x3's numbers")
+
+
+def resolve_model_flags(args):
+    """--setting left out: the model's own setting (modelnet_x3_l4 for every model that reads none)"""
+    if args.setting is None:
+        from ..pointcnn.settings import MODEL_DEFAULT
+        args.setting = MODEL_DEFAULT.get(args.model, "modelnet_x3_l4")
+    return args
+
+
+def own_trainer(mod, args):
+    """the trainer numbers a model brings instead of this file's defaults (PointCNN: Adam's epsilon, the lr schedule in
+    steps, the regulariser, the augmentation): the module's own `trainer` hook, or the hook of the module that its
+    TRAINER_FROM names -- pointcnn_seg trains with pointcnn_cls's and defines none of its own; None for every other model"""
+    if hasattr(mod, "trainer"):
+        return mod.trainer(args)
+    if hasattr(mod, "TRAINER_FROM"):
+        return importlib.import_module(mod.TRAINER_FROM).trainer(args)
+    return None
 
 
 def model_fn(mod, args, dev):
@@ -100,7 +125,7 @@ def parse_args(argv=None):
     p.add_argument("--deterministic", action="store_true",
                    help="bit-reproducible backward passes: ordered owner sums instead of float atomics (slower)")
     add_model_flags(p)
-    args = p.parse_args(argv)
+    args = resolve_model_flags(p.parse_args(argv))
     mod = importlib.import_module(MODELS[args.model])
     own = mod.flag_defaults(args) if hasattr(mod, "flag_defaults") else {}
     for name, default in FLAG_DEFAULTS.items():
@@ -185,7 +210,7 @@ def train(args):
         _lib.set_deterministic(True)
     mod = importlib.import_module(MODELS[args.model])
     partseg = args.model.endswith("_partseg")
-    with_mask = "parts" if partseg else args.model.endswith("_bga")
+    with_mask = "parts" if partseg else args.model in MASK_MODELS
     per_rank = args.batch_size // world
     rng = np.random.RandomState(args.seed)          # same stream on every rank -> same epoch order
     gen = torch.Generator(device=dev)
@@ -200,7 +225,7 @@ def train(args):
     net = Model(model_fn(mod, args, dev), device=dev, seed=args.seed, **kw).build(example)
     fp = TU.FlatParams(net).enable_overlap(world)        # N > 1: gradient ranges travel while the backward pass runs
     D.broadcast_(fp.flat)
-    own = mod.trainer(args) if hasattr(mod, "trainer") else None   # a model with trainer numbers of its own (PointCNN)
+    own = own_trainer(mod, args)                                   # a model with trainer numbers of its own (PointCNN)
     opt = TU.make_optimizer(args.optimizer, fp, args.momentum, **({"epsilon": own.adam_epsilon} if own else {}))
     augment = own.augment if own else getattr(mod, "augment", None)
     scores = getattr(mod, "class_scores", lambda logits: logits)     # what argmax and the votes are taken on
@@ -265,7 +290,7 @@ def train(args):
         if partseg:
             ev = EV.eval_partseg_one_epoch(net, td, tm, per_rank, device=dev)
         elif with_mask:
-            ev = EV.eval_seg_one_epoch(net, td, tl, tm, per_rank, device=dev)
+            ev = EV.eval_seg_one_epoch(net, td, tl, tm, per_rank, device=dev, scores_fn=scores)
         else:
             ev = EV.eval_one_epoch(net, td, tl, per_rank, device=dev, num_classes=args.num_class, scores_fn=scores)
         rec = {"epoch": epoch, "mean_loss": loss_sum / max(nb, 1), "train_acc": correct / max(seen, 1),
