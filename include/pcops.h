@@ -1051,6 +1051,30 @@ int pcops_xconv_wgrad(int b, int n, int p, int k, int c1, int c2, int dm, const 
                       const int *idx, const float *X, const float *dout, float *dwd, void *workspace,
                       pcops_stream_t stream);
 
+/* ------------------------------------------------------------------ PointNet's per-cloud feature transform (csrc/tnet.hip)
+ * tf.matmul(net, transform) of pointnet/models/pointnet_cls.py:47 with a DIFFERENT k x k matrix per cloud, and the
+ * orthogonality regulariser of :86-91.  k is the transform's width; only k == 64 is built.
+ *   X, out, G, dX (b, n, k) row-major;  T, dT (b, k, k);  every pointer, the workspace included, 16-byte aligned
+ *   fwd:  out[c][p][:] = X[c][p][:] T[c]
+ *   bwd:  dX[c] = G[c] T[c]^T (dX may be NULL: not wanted),  dT[c] = X[c]^T G[c], one pass over G.  A cloud's points are cut
+ *         into pcops_transformk_bwd_splits contiguous ranges: the largest power of two <= min(ceil(512 / b), ceil(n / 64), 16),
+ *         each range ceil(ceil(n / splits) / 64) 64 points (trailing ranges may hold no point and contribute zeros).  One
+ *         split stores dT directly (workspace may be NULL); more write partial sums to pcops_transformk_workspace_bytes =
+ *         b splits k k 4 bytes of caller-owned workspace and a second kernel adds them in ascending order.
+ *   ortho: Gm = T[c] T[c]^T - I, loss_parts[c] = weight / 2 sum Gm^2, dT[c] = 2 weight Gm T[c] -- loss and gradient from one
+ *         launch, one workgroup per cloud.  The loss of tf.nn.l2_loss is the SUM of loss_parts over the clouds (the caller's).
+ * fp32 operands on the fp32 matrix pipe, no split operands; every sum in a fixed order, no float atomics: two calls give the
+ * same bits whatever pcops_set_deterministic says.
+ * Supported (pcops_transformk_supported): k == 64, 1 <= b <= 65535, n >= 1, b n k < 2^31; pcops_ortho_reg: k == 64,
+ * 1 <= b <= 65535.  PCOPS_ERR_UNSUPPORTED outside, before any launch and any pointer check; the queries answer 0. */
+int pcops_transformk_supported(int b, int n, int k);
+int pcops_transformk_bwd_splits(int b, int n, int k);
+unsigned long long pcops_transformk_workspace_bytes(int b, int n, int k);
+int pcops_transformk_fwd(int b, int n, int k, const float *X, const float *T, float *out, pcops_stream_t stream);
+int pcops_transformk_bwd(int b, int n, int k, const float *X, const float *T, const float *G, float *dX, float *dT,
+                         void *workspace, pcops_stream_t stream);
+int pcops_ortho_reg(int b, int k, const float *T, float weight, float *loss_parts, float *dT, pcops_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -38,7 +38,9 @@ MODELS = {"pointnet2_cls_ssg": "scanobjectnn_amd.pointnet2.pointnet2_cls_ssg",
           "spidercnn_cls_xyz": "scanobjectnn_amd.spidercnn.spidercnn_cls_xyz",
           "3dmfv_net_cls": "scanobjectnn_amd.mfv3d.mfv3d_net_cls",
           "pointcnn_cls": "scanobjectnn_amd.pointcnn.pointcnn_cls",
-          "pointcnn_seg": "scanobjectnn_amd.pointcnn.pointcnn_seg"}
+          "pointcnn_seg": "scanobjectnn_amd.pointcnn.pointcnn_seg",
+          "pointnet_cls": "scanobjectnn_amd.pointnet.pointnet_cls",
+          "pointnet_cls_basic": "scanobjectnn_amd.pointnet.pointnet_cls_basic"}
 # the models that predict a per-point foreground mask beside the class (the reference's train_seg.py trainers)
 MASK_MODELS = frozenset(m for m in MODELS if m.endswith("_bga")) | {"pointcnn_seg"}
 # flags a model may take from its own setting when the command line leaves them out (the module's flag_defaults);
