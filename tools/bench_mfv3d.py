@@ -12,14 +12,11 @@ its VALID-TAP FLOPs -- 2 B Cin Cout (sum over voxels of the taps inside the grid
 the MI355X.  No ratio is fixed in advance: the torch form is the yardstick, and a layer where the native kernel loses shows as
 such."""
 import argparse
-import json
 import os
-import statistics
-import subprocess
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import ab_bench
+
 PEAK_TF = 157.3
 CONVS = ("pcops_conv3d_fwd", "pcops_conv3d_dgrad", "pcops_conv3d_wgrad")
 
@@ -30,28 +27,10 @@ def valid_pairs(r, k):
     return sum(1 for i in range(r) for d in range(-h, h + 1) if 0 <= i + d < r)
 
 
-def _timed(fn, warmup, steps):
-    import torch
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    torch.cuda.reset_peak_memory_stats()
-    times = []
-    for _ in range(steps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        times.append(e0.elapsed_time(e1))
-    return statistics.median(times), torch.cuda.max_memory_allocated() / 2 ** 20
-
-
 def child(args):
-    sys.path.insert(0, ROOT)
+    sys.path.insert(0, ab_bench.ROOT)
     import numpy as np
     import torch
-    from scanobjectnn_amd import _lib
     from scanobjectnn_amd.graph import Model
     from scanobjectnn_amd.mfv3d import mfv3d_net_cls as m
     from scanobjectnn_amd.mfv3d import tf_util as T
@@ -65,10 +44,9 @@ def child(args):
            "kernels": []}
     if args.what == "fv":
         w, mu, sigma = (torch.as_tensor(np.asarray(a), dtype=torch.float32, device=dev) for a in gmm)
-        res["ms"], res["max_memory_allocated_mb"] = _timed(lambda: T.get_3dmfv(x, w, mu, sigma, flatten=False), args.warmup,
-                                                           args.steps)
-        print("RESULT " + json.dumps(res), flush=True)
-        return
+        res["ms"], res["max_memory_allocated_mb"] = ab_bench.timed(lambda: T.get_3dmfv(x, w, mu, sigma, flatten=False),
+                                                                   args.warmup, args.steps)
+        return ab_bench.emit(res)
     y = torch.from_numpy(synth_labels(args.batch, seed=1)).to(dev)
     net = Model(m.bind(gmm, device=dev), device=dev, seed=0).build(x)
     opt = torch.optim.Adam(net.parameters(), lr=1e-3)
@@ -78,96 +56,81 @@ def child(args):
         m.get_loss(net(x, is_training=True, bn_decay=0.9)[0], y).backward()
         opt.step()
 
-    res["ms"], res["max_memory_allocated_mb"] = _timed(step, args.warmup, args.steps)
+    res["ms"], res["max_memory_allocated_mb"] = ab_bench.timed(step, args.warmup, args.steps)
     if native:
-        calls = []
-
-        def hook(name, phase, a):
-            if not name.startswith(("pcops_fv3d_", "pcops_conv3d_")):
-                return
-            ev = torch.cuda.Event(enable_timing=True)
-            ev.record()
-            if phase == "pre":
-                calls.append([name, a[:5] if name in CONVS else a[:3], ev, None])
-            else:
-                calls[-1][3] = ev
-        _lib._hooks.append(hook)
-        step()
-        torch.cuda.synchronize()
-        _lib._hooks.remove(hook)
-        for name, shape, e0, e1 in calls:
-            rec = {"name": name, "shape": [int(v) for v in shape], "ms": e0.elapsed_time(e1)}
+        for name, shape, ms in ab_bench.time_entry_points(step, ("pcops_fv3d_", "pcops_conv3d_"),
+                                                          lambda name: 5 if name in CONVS else 3):
+            rec = {"name": name, "shape": shape, "ms": ms}
             if name in CONVS:
-                b, r, k, cin, cout = rec["shape"]
+                b, r, k, cin, cout = shape
                 rec["valid_gflop"] = 2.0 * b * cin * cout * valid_pairs(r, k) ** 3 / 1e9
                 rec["dense_gflop"] = 2.0 * b * cin * cout * (r * k) ** 3 / 1e9
                 rec["tflops"] = rec["valid_gflop"] / rec["ms"]
                 rec["peak_fraction"] = rec["tflops"] / PEAK_TF
             res["kernels"].append(rec)
-    print("RESULT " + json.dumps(res), flush=True)
+    ab_bench.emit(res)
 
 
-def parent(args):
-    lines, results = [], []
+def configs(args):
+    """(child argv, environment overlay, the record fields of the config) in run order"""
+    return [(["--child", "--what", what, "--batch", str(b), "--points", str(n), "--gaussians", str(g), "--steps",
+              str(args.steps), "--warmup", str(args.warmup)], {}, {"what": what, "batch": b, "points": n, "gaussians": g ** 3})
+            for what, b, n, g in (("step", 64, 1024, 5), ("step", 64, 1024, 8), ("fv", 256, 2048, 8))]
 
-    def say(s):
-        print(s, flush=True)
-        lines.append(s)
-    say("# tools/bench_mfv3d.py: 3DmFV-Net, %d timed iterations (median), warmup %d, %d rounds of alternating child processes"
-        % (args.steps, args.warmup, args.rounds))
-    configs = [("step", 64, 1024, 5), ("step", 64, 1024, 8), ("fv", 256, 2048, 8)]
-    for what, b, n, g in configs:
-        for r in range(args.rounds):
-            for native in ("1", "0"):
-                env = dict(os.environ, PCOPS_MFV_NATIVE=native)
-                cmd = [sys.executable, os.path.abspath(__file__), "--child", "--what", what, "--batch", str(b), "--points", str(n),
-                       "--gaussians", str(g), "--steps", str(args.steps), "--warmup", str(args.warmup)]
-                t0 = time.time()
-                out = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=args.child_timeout)
-                if out.returncode != 0:
-                    say("child %s B=%d K=%d native=%s failed (exit %d): %s" % (what, b, g ** 3, native, out.returncode,
-                                                                              out.stderr[-2000:]))
-                    raise SystemExit(1)
-                res = json.loads([l for l in out.stdout.splitlines() if l.startswith("RESULT ")][-1][7:])
-                results.append(res)
-                say("%-4s B=%-3d N=%-4d K=%-3d %-6s round %d: %9.3f ms  peak %9.1f MB  (%.0f s)"
-                    % (what, b, n, g ** 3, "native" if res["native"] else "torch", r, res["ms"], res["max_memory_allocated_mb"],
-                       time.time() - t0))
-    say("")
-    for what, b, n, g in configs:
-        sel = [r for r in results if (r["what"], r["batch"], r["gaussians"]) == (what, b, g ** 3)]
-        nat, ref = [r for r in sel if r["native"]], [r for r in sel if not r["native"]]
-        mn, mt = statistics.median(r["ms"] for r in nat), statistics.median(r["ms"] for r in ref)
-        say("%s B=%d N=%d K=%d: native %.3f ms, torch %.3f ms: torch / native %.2f; peak memory %.0f MB vs %.0f MB"
-            % ("training step" if what == "step" else "representation", b, n, g ** 3, mn, mt, mt / mn,
-               max(r["max_memory_allocated_mb"] for r in nat), max(r["max_memory_allocated_mb"] for r in ref)))
-        if what == "step":
-            say("  3DmFV kernels of one native step (last round; convolutions on valid-tap FLOPs):")
+
+def header(args):
+    return ("# tools/bench_mfv3d.py: 3DmFV-Net, %d timed iterations (median), warmup %d, %d rounds of alternating child processes"
+            % (args.steps, args.warmup, args.rounds))
+
+
+def run_line(res, r, seconds):
+    return ("%-4s B=%-3d N=%-4d K=%-3d %-6s round %d: %9.3f ms  peak %9.1f MB  (%.0f s)"
+            % (res["what"], res["batch"], res["points"], res["gaussians"], "native" if res["native"] else "torch", r, res["ms"],
+               res["max_memory_allocated_mb"], seconds))
+
+
+def summarise(results, args):
+    lines = []
+    for _, _, key in configs(args):
+        nat, ref = ab_bench.split_on_off(results, key)
+        mn, mt = ab_bench.median(nat), ab_bench.median(ref)
+        lines.append("%s B=%d N=%d K=%d: native %.3f ms, torch %.3f ms: torch / native %.2f; peak memory %.0f MB vs %.0f MB"
+                     % (("training step" if key["what"] == "step" else "representation", key["batch"], key["points"],
+                         key["gaussians"], mn, mt, mt / mn) + ab_bench.peak_mb(nat, ref)))
+        if key["what"] == "step":
+            lines.append("  3DmFV kernels of one native step (last round; convolutions on valid-tap FLOPs):")
             for k in nat[-1]["kernels"]:
                 extra = ""
                 if "tflops" in k:
                     extra = "  %7.3f of %7.3f GFLOP  %6.2f TF  %.3f of the fp32 matrix peak" % (
                         k["valid_gflop"], k["dense_gflop"], k["tflops"], k["peak_fraction"])
-                say("    %-20s %-24s %8.3f ms%s" % (k["name"], k["shape"], k["ms"], extra))
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
-            f.write("# raw\n" + "\n".join(json.dumps(r) for r in results) + "\n")
+                lines.append("    %-20s %-24s %8.3f ms%s" % (k["name"], k["shape"], k["ms"], extra))
+    return lines
 
 
-def main():
+def parent(args):
+    report, results = ab_bench.Report(), []
+    report.say(header(args))
+    for argv, env, _ in configs(args):
+        for r in range(args.rounds):
+            for value in ("1", "0"):
+                res, seconds = ab_bench.run_child(os.path.abspath(__file__), argv, dict(env, PCOPS_MFV_NATIVE=value),
+                                                  args.child_timeout)
+                results.append(res)
+                report.say(run_line(res, r, seconds))
+    for line in [""] + summarise(results, args):
+        report.say(line)
+    report.write(args.out, results)
+
+
+def main(argv=None):
     p = argparse.ArgumentParser()
-    p.add_argument("--child", action="store_true")
+    ab_bench.add_common_args(p, steps=20, warmup=5)
     p.add_argument("--what", default="step", choices=["step", "fv"])
     p.add_argument("--batch", type=int, default=64)
     p.add_argument("--points", type=int, default=1024)
     p.add_argument("--gaussians", type=int, default=5, help="grid subdivisions per axis")
-    p.add_argument("--steps", type=int, default=20)
-    p.add_argument("--warmup", type=int, default=5)
-    p.add_argument("--rounds", type=int, default=2)
-    p.add_argument("--child_timeout", type=int, default=300)
-    p.add_argument("--out", default="")
-    args = p.parse_args()
+    args = p.parse_args(argv)
     child(args) if args.child else parent(args)
 
 

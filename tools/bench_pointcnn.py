@@ -30,14 +30,12 @@ started with --model pointcnn_seg under PCOPS_XCONV_GROUPS=<0|1>; --kernel_stats
 forward and the data gradient (with its reduce pass) of both values side by side with the spread between the rounds.  It prints, per X-Conv kernel, calls, average and minimum time and the operand bytes it has to move (every operand once, the
 gathered rows once per use) over the average time, beside the 8.0 TB/s HBM peak of the MI355X."""
 import argparse
-import json
 import os
 import statistics
-import subprocess
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import ab_bench
+
 # (n, p, K, c1, c2, dm) at N = 1024: the four X-Conv layers of modelnet_x3_l4, the five X-DeConv layers of object_dataset_x3
 MODEL_LAYERS = {
     "pointcnn_cls": [(1024, 1024, 8, 24, 0, 4), (1024, 384, 12, 12, 48, 2), (384, 128, 16, 24, 96, 2),
@@ -47,57 +45,10 @@ MODEL_LAYERS = {
 }
 SETTING = {"pointcnn_cls": "modelnet_x3_l4", "pointcnn_seg": "object_dataset_x3"}
 WIDE_LAYERS = (0, 1)          # pointcnn_seg: xdconv_1 and xdconv_2 run in channel groups
-VIEWS = {"view", "reshape", "detach", "alias", "expand", "slice", "select", "t", "transpose", "unsqueeze", "squeeze",
-         "as_strided", "empty", "empty_like", "empty_strided", "_unsafe_view", "permute", "split", "unbind", "narrow",
-         "set_", "lift_fresh", "sym_size", "sym_stride", "sym_numel", "sym_storage_offset", "is_same_size", "new_empty"}
-
-
-def _timed(fn, warmup, steps, inner):
-    """median over `steps` windows of `inner` calls each, per call"""
-    import torch
-    for _ in range(warmup * inner):
-        fn()
-    torch.cuda.synchronize()
-    torch.cuda.reset_peak_memory_stats()
-    times = []
-    for _ in range(steps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(inner):
-            fn()
-        e1.record()
-        e1.synchronize()
-        times.append(e0.elapsed_time(e1) / inner)
-    return statistics.median(times), torch.cuda.max_memory_allocated() / 2 ** 20
-
-
-def _count_launches(fn):
-    import torch
-    from torch.utils._python_dispatch import TorchDispatchMode
-    from scanobjectnn_amd import _lib
-    count = [0, 0]
-
-    class Log(TorchDispatchMode):
-        def __torch_dispatch__(self, func, types, args=(), kwargs=None):
-            if str(func).split(".")[1] not in VIEWS:
-                count[0] += 1
-            return func(*args, **(kwargs or {}))
-
-    def hook(name, phase, a):
-        if phase == "pre":
-            count[1] += 1
-    _lib._hooks.append(hook)
-    try:
-        with torch.autograd.set_multithreading_enabled(False), Log():       # backward runs under the mode too
-            fn()
-    finally:
-        _lib._hooks.remove(hook)
-    torch.cuda.synchronize()
-    return count
 
 
 def child(args):
-    sys.path.insert(0, ROOT)
+    sys.path.insert(0, ab_bench.ROOT)
     import torch
     from scanobjectnn_amd import train_util as TU
     from scanobjectnn_amd.graph import Model
@@ -151,65 +102,68 @@ def child(args):
             opt.step(own.learning_rate(0))
 
     inner = args.inner_layer if args.what == "layer" else args.inner_step
-    res["ms"], res["max_memory_allocated_mb"] = _timed(step, args.warmup, args.steps, inner)
+    res["ms"], res["max_memory_allocated_mb"] = ab_bench.timed(step, args.warmup, args.steps, inner)
     res["window_ms"] = res["ms"] * inner
-    res["aten_ops"], res["pcops_calls"] = _count_launches(step)
-    print("RESULT " + json.dumps(res), flush=True)
+    res["aten_ops"], res["pcops_calls"] = ab_bench.count_launches(step)
+    ab_bench.emit(res)
+
+
+def configs(args):
+    """(child argv, environment overlay, the record fields of the config) in run order.  The last field names the switch
+    that alternates: native against torch everywhere; pointcnn_seg also groups on / off, both native."""
+    steps = [("step", 32, -1)] + ([("step", 128, -1)] if args.model == "pointcnn_cls" else [])
+    runs = [c + ("PCOPS_XCONV_NATIVE",) for c in steps + [("layer", 32, i) for i in range(len(MODEL_LAYERS[args.model]))]]
+    if args.model == "pointcnn_seg":
+        runs += [c + ("PCOPS_XCONV_GROUPS",) for c in steps + [("layer", 32, i) for i in WIDE_LAYERS]]
+    return [(["--child", "--model", args.model, "--what", what, "--batch", str(b), "--layer", str(layer), "--steps",
+              str(args.steps), "--warmup", str(args.warmup), "--inner_step", str(args.inner_step), "--inner_layer",
+              str(args.inner_layer)], {"PCOPS_XCONV_NATIVE": "1", "PCOPS_XCONV_GROUPS": "1"},
+             {"what": what, "batch": b, "layer": layer, "switch": switch}) for what, b, layer, switch in runs]
+
+
+def header(args):
+    return ("# tools/bench_pointcnn.py: PointCNN %s %s, N = 1024; ms per call = median of %d timed windows of %d steps / "
+            "%d contraction calls each, %d rounds of alternating child processes.  Call times include the host's launch work."
+            % (args.model, SETTING[args.model], args.steps, args.inner_step, args.inner_layer, args.rounds))
+
+
+def run_line(res, r, seconds, args):
+    return ("%-5s B=%-3d %-28s %-10s round %d: %9.3f ms (windows of %4.0f ms)  peak %8.1f MB  launches %4d aten + %3d "
+            "pcops  (%.0f s)"
+            % (res["what"], res["batch"], "" if res["layer"] < 0 else str(MODEL_LAYERS[args.model][res["layer"]]),
+               _label(res["switch"], res["on"]), r, res["ms"], res["window_ms"], res["max_memory_allocated_mb"],
+               res["aten_ops"], res["pcops_calls"], seconds))
+
+
+def summarise(results, args):
+    lines = []
+    for _, _, key in configs(args):
+        on, off = ab_bench.split_on_off(results, key)
+        mn, mt = ab_bench.median(on), ab_bench.median(off)
+        label = "training step B=%d" % key["batch"] if key["what"] == "step" else \
+            "contraction fwd+bwd CALL time incl. launches, B=%d (n, p, K, c1, c2, dm) = %s" % (
+                key["batch"], MODEL_LAYERS[args.model][key["layer"]])
+        lines.append("%s: %s %.3f ms (rounds %s), %s %.3f ms (rounds %s): ratio %.2f; peak memory %.0f MB vs %.0f MB; "
+                     "launches %d vs %d"
+                     % ((label, _label(key["switch"], True), mn, ab_bench.per_round(on), _label(key["switch"], False), mt,
+                         ab_bench.per_round(off), mt / mn) + ab_bench.peak_mb(on, off) + ab_bench.launches(on, off)))
+    return lines
 
 
 def parent(args):
-    lines, results = [], []
-    layers = MODEL_LAYERS[args.model]
-
-    def say(s):
-        print(s, flush=True)
-        lines.append(s)
-    say("# tools/bench_pointcnn.py: PointCNN %s %s, N = 1024; ms per call = median of %d timed windows of %d steps / "
-        "%d contraction calls each, %d rounds of alternating child processes.  Call times include the host's launch work."
-        % (args.model, SETTING[args.model], args.steps, args.inner_step, args.inner_layer, args.rounds))
-    # (what, batch, layer, the switch that alternates): native against torch everywhere; pointcnn_seg also groups on / off
-    steps = [("step", 32, -1)] + ([("step", 128, -1)] if args.model == "pointcnn_cls" else [])
-    configs = [c + ("PCOPS_XCONV_NATIVE",) for c in steps + [("layer", 32, i) for i in range(len(layers))]]
-    if args.model == "pointcnn_seg":
-        configs += [c + ("PCOPS_XCONV_GROUPS",) for c in steps + [("layer", 32, i) for i in WIDE_LAYERS]]
-    for what, b, layer, switch in configs:
+    report, results = ab_bench.Report(), []
+    report.say(header(args))
+    for argv, env, key in configs(args):
         for r in range(args.rounds):
             for value in ("1", "0"):
-                env = dict(os.environ, PCOPS_XCONV_NATIVE="1", PCOPS_XCONV_GROUPS="1")
-                env[switch] = value
-                cmd = [sys.executable, os.path.abspath(__file__), "--child", "--model", args.model, "--what", what, "--batch",
-                       str(b), "--layer", str(layer), "--steps", str(args.steps), "--warmup", str(args.warmup),
-                       "--inner_step", str(args.inner_step), "--inner_layer", str(args.inner_layer)]
-                t0 = time.time()
-                out = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=args.child_timeout)
-                if out.returncode != 0:
-                    say("child %s B=%d layer %d %s=%s failed (exit %d): %s" % (what, b, layer, switch, value, out.returncode,
-                                                                              out.stderr[-2000:]))
-                    raise SystemExit(1)
-                res = json.loads([l for l in out.stdout.splitlines() if l.startswith("RESULT ")][-1][7:])
-                res["switch"], res["on"] = switch, value == "1"
+                res, seconds = ab_bench.run_child(os.path.abspath(__file__), argv, dict(env, **{key["switch"]: value}),
+                                                  args.child_timeout)
+                res["switch"], res["on"] = key["switch"], value == "1"
                 results.append(res)
-                say("%-5s B=%-3d %-28s %-10s round %d: %9.3f ms (windows of %4.0f ms)  peak %8.1f MB  launches %4d aten + %3d "
-                    "pcops  (%.0f s)"
-                    % (what, b, "" if layer < 0 else str(layers[layer]), _label(switch, value == "1"), r, res["ms"],
-                       res["window_ms"], res["max_memory_allocated_mb"], res["aten_ops"], res["pcops_calls"],
-                       time.time() - t0))
-    say("")
-    for what, b, layer, switch in configs:
-        sel = [r for r in results if (r["what"], r["batch"], r["layer"], r["switch"]) == (what, b, layer, switch)]
-        on, off = [r for r in sel if r["on"]], [r for r in sel if not r["on"]]
-        mn, mt = statistics.median(r["ms"] for r in on), statistics.median(r["ms"] for r in off)
-        label = "training step B=%d" % b if what == "step" else \
-            "contraction fwd+bwd CALL time incl. launches, B=%d (n, p, K, c1, c2, dm) = %s" % (b, layers[layer])
-        say("%s: %s %.3f ms (rounds %s), %s %.3f ms (rounds %s): ratio %.2f; peak memory %.0f MB vs %.0f MB; launches %d vs %d"
-            % (label, _label(switch, True), mn, " ".join("%.3f" % r["ms"] for r in on), _label(switch, False), mt,
-               " ".join("%.3f" % r["ms"] for r in off), mt / mn, max(r["max_memory_allocated_mb"] for r in on),
-               max(r["max_memory_allocated_mb"] for r in off), on[-1]["aten_ops"] + on[-1]["pcops_calls"],
-               off[-1]["aten_ops"] + off[-1]["pcops_calls"]))
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
-            f.write("# raw\n" + "\n".join(json.dumps(r) for r in results) + "\n")
+                report.say(run_line(res, r, seconds, args))
+    for line in [""] + summarise(results, args):
+        report.say(line)
+    report.write(args.out, results)
 
 
 def _label(switch, on):
@@ -231,14 +185,9 @@ def operand_bytes(kernel, b, shape):
 
 
 def _trace_rows(directory, sub):
-    """{short kernel name: (calls, average us, minimum us)} of the X-Conv kernels of DIR/sub/**/*kernel_stats.csv"""
-    import csv
-    import glob
-    files = sorted(glob.glob(os.path.join(directory, sub, "**", "*kernel_stats.csv"), recursive=True))
-    if not files:
-        raise SystemExit("no kernel_stats.csv under %s/%s" % (directory, sub))
+    """{short kernel name: (calls, average us, minimum us)} of the X-Conv kernels in the kernel trace under DIR/sub"""
     rows = {}
-    for row in csv.DictReader(open(files[-1])):
+    for row in ab_bench.kernel_stats_rows(directory, sub, required=True):
         if "xconv" in row["Name"]:
             short = row["Name"].split("xconv_")[1].split("(")[0]
             rows[short] = (int(row["Calls"]), float(row["AverageNs"]) / 1e3, float(row["MinNs"]) / 1e3)
@@ -246,7 +195,7 @@ def _trace_rows(directory, sub):
 
 
 def kernel_stats(args):
-    """the X-Conv kernels of DIR/layer<i>/**/*kernel_stats.csv (rocprofv3 --kernel-trace --stats, one run per layer)"""
+    """the X-Conv kernels of the traces under DIR/layer<i> (rocprofv3 --kernel-trace --stats, one run per layer)"""
     if args.model == "pointcnn_seg":
         return kernel_stats_groups(args)
     layers = MODEL_LAYERS[args.model]
@@ -264,10 +213,18 @@ def kernel_stats(args):
             total += avg
             lines.append(line)
         lines.append("layer %d: X-Conv kernels of one forward + backward %.1f us" % (layer + 1, total))
-    print("\n".join(lines))
-    if args.out:
-        with open(args.out, "a") as f:
-            f.write("\n".join(lines) + "\n")
+    ab_bench.Report.append(args.out, lines)
+
+
+def _groups_verdict(layer, what, on, off, args):
+    """one wide layer's kernel, average us per round with groups (on) and with one group (off)"""
+    spread = ab_bench.spread(on, off)
+    gain = statistics.mean(off) - statistics.mean(on)
+    gbs = operand_bytes(what, args.batch, MODEL_LAYERS[args.model][layer]) / (statistics.mean(on) * 1e3)
+    return ("xdconv_%d %-5s: groups %s us, one group %s us; one group - groups = %.1f us, spread between rounds "
+            "%.1f us: %s; with groups %.0f GB/s, %.3f of the 8000 GB/s peak"
+            % (layer + 1, what, " ".join("%.1f" % v for v in on), " ".join("%.1f" % v for v in off), gain, spread,
+               "LOWER by more than the spread" if gain > spread else "NOT lower by more than the spread", gbs, gbs / 8000.0))
 
 
 def kernel_stats_groups(args):
@@ -297,37 +254,21 @@ def kernel_stats_groups(args):
                                  % (layer + 1, layers[layer], g, r, short, calls, avg, mn))
             lines.append("xdconv_%d round %d: the reduce pass over the groups' dX: %.1f us per data gradient" % (layer + 1, r, extra))
         for what in ("fwd", "dgrad"):
-            on, off = t[(what, 1)], t[(what, 0)]
-            spread = max(max(on) - min(on), max(off) - min(off))
-            gain = statistics.mean(off) - statistics.mean(on)
-            gbs = operand_bytes(what, args.batch, layers[layer]) / (statistics.mean(on) * 1e3)
-            lines.append("xdconv_%d %-5s: groups %s us, one group %s us; one group - groups = %.1f us, spread between rounds "
-                         "%.1f us: %s; with groups %.0f GB/s, %.3f of the 8000 GB/s peak"
-                         % (layer + 1, what, " ".join("%.1f" % v for v in on), " ".join("%.1f" % v for v in off), gain, spread,
-                            "LOWER by more than the spread" if gain > spread else "NOT lower by more than the spread", gbs,
-                            gbs / 8000.0))
-    print("\n".join(lines))
-    if args.out:
-        with open(args.out, "a") as f:
-            f.write("\n".join(lines) + "\n")
+            lines.append(_groups_verdict(layer, what, t[(what, 1)], t[(what, 0)], args))
+    ab_bench.Report.append(args.out, lines)
 
 
-def main():
+def main(argv=None):
     p = argparse.ArgumentParser()
-    p.add_argument("--child", action="store_true")
+    ab_bench.add_common_args(p, steps=10, warmup=3, windows=True)
     p.add_argument("--model", default="pointcnn_cls", choices=sorted(MODEL_LAYERS))
     p.add_argument("--what", default="step", choices=["step", "layer"])
     p.add_argument("--batch", type=int, default=32)
     p.add_argument("--layer", type=int, default=-1)
-    p.add_argument("--steps", type=int, default=10, help="timed windows per run")
-    p.add_argument("--warmup", type=int, default=3, help="untimed windows first")
     p.add_argument("--inner_step", type=int, default=10, help="training steps per window")
     p.add_argument("--inner_layer", type=int, default=500, help="contraction calls per window")
     p.add_argument("--kernel_stats", default="", help="directory of per-layer rocprofv3 kernel traces to summarise")
-    p.add_argument("--rounds", type=int, default=2)
-    p.add_argument("--child_timeout", type=int, default=300)
-    p.add_argument("--out", default="")
-    args = p.parse_args()
+    args = p.parse_args(argv)
     if args.kernel_stats:
         kernel_stats(args)
     else:
