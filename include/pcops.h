@@ -1075,6 +1075,38 @@ int pcops_transformk_bwd(int b, int n, int k, const float *X, const float *T, co
                          void *workspace, pcops_stream_t stream);
 int pcops_ortho_reg(int b, int k, const float *T, float weight, float *loss_parts, float *dT, pcops_stream_t stream);
 
+/* ---------------------------------------------- first conv of PointNet's segmentation heads (csrc/cloudpoint.hip)
+ * conv6 of pointnet/models/pointnet_seg.py:81-88 and pointnet_partseg.py:66-73 on concat([point_feat (64) | tiled global feature
+ * (1024)]): the per-cloud columns are one row Ctr[cloud] = global W_c + bias per cloud (the caller's small product), the
+ * per-point columns a k = 64 deep product that is evaluated INSIDE the streaming pass -- neither Q = X Wx nor its gradient
+ * dQ ever exists in memory (the pcops_cloud_bias_* form of the same layer reads and writes both).
+ *   X, dX (b n, k);  Wx, dWx (k, c);  Ctr, dCtr (b, c);  Y, G (b n, c), all row-major; every pointer, the workspace included,
+ *   16-byte aligned;  p, q, t [c]: the coefficients of pcops_mlp_bn_bwd_coeffs
+ *   fwd:  Y[r, :] = X[r, :] Wx + Ctr[r / n, :].  stats_partial (NULL: evaluation mode, no statistics):
+ *         [pcops_cloud_point_rows(b, n) = b ceil(n / 128)][2][c] sums of (y - pivot) and (y - pivot)^2 over the rows of one
+ *         workgroup -- the layout pcops_cloud_bias_fwd produces and pcops_mlp_bn_finalize consumes; stat_pivot [c] (NULL: 0).
+ *         A workgroup holds 128 points of ONE cloud; the tail tile of a cloud is masked.
+ *   bwd:  D = p G + q Y + t per element, never stored;  dX = D Wx^T (dX may be NULL: not wanted),  dWx = X^T D,
+ *         dCtr[cloud] = the sum of D over the cloud's rows.  A cloud's points are cut into s contiguous ranges, s = the largest
+ *         power of two <= min(ceil(512 / b), ceil(n / 64), 16), each ceil(ceil(n / s) / 64) 64 points (trailing ranges may hold
+ *         no point and contribute zeros); pcops_cloud_point_bwd_parts = b s is the number of partial dWx matrices.  One part
+ *         stores dWx and dCtr directly (workspace may be NULL); more write partial sums to pcops_cloud_point_bwd_ws bytes of
+ *         caller-owned workspace ([parts][k][c], then [parts][c] where s > 1) and one launch each adds them in ascending order.
+ *         Layers wider than 512 channels run the pass once per 512 channels; the later passes add to the first's dX.
+ * fp32 operands on the fp32 matrix pipe, no split operands; every sum in a fixed order, no float atomics: two calls give the
+ * same bits whatever pcops_set_deterministic says.
+ * Supported (pcops_cloud_point_supported): k == 64, c % 64 == 0, 64 <= c <= 1024, 1 <= b <= 65535, n >= 1, b n c < 2^31.
+ * PCOPS_ERR_UNSUPPORTED outside, before any launch and any pointer check; the queries answer 0. */
+int pcops_cloud_point_supported(int b, int n, int k, int c);
+int pcops_cloud_point_rows(int b, int n);
+int pcops_cloud_point_fwd(int b, int n, int k, int c, const float *X, const float *Wx, const float *Ctr, float *Y,
+                          float *stats_partial, const float *stat_pivot, pcops_stream_t stream);
+int pcops_cloud_point_bwd_parts(int b, int n, int c);
+unsigned long long pcops_cloud_point_bwd_ws(int b, int n, int k, int c);
+int pcops_cloud_point_bwd(int b, int n, int k, int c, const float *G, const float *Y, const float *p, const float *q,
+                          const float *t, const float *X, const float *Wx, float *dX, float *dWx, float *dCtr, void *workspace,
+                          pcops_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -72,17 +72,19 @@ def _p(t):
 # the products (on the arithmetic first layer, compacted rows with / without the pooled epilogue, pooled epilogue, plain)
 F_QC, F_CLOUD, F_GATHER, F_XYZ, F_POOL_ROWS, F_ROWS, F_POOL, F_GEMM = (
     "qc", "cloud_bias", "gather", "xyz", "pool_rows", "rows", "pool", "gemm")
+F_CLOUD_POINT = "cloud_point"       # whole clouds + per-cloud term with the 64-wide per-point product inside the pass
 # backward arms of a layer.  First layer of a gather stack: arithmetic, direct edge, [Q | Ctr] scatter, cloud-bias,
 # generic scatter (with the identity shortcut where the scatter is a reshape).  Products: algebraic top layer, one pass
 # for both gradients in its five forms, separate weight + data gradient (below it a stored / the arithmetic layer)
 B_XYZ_FIRST, B_EDGE_FIRST, B_QC, B_CLOUD, B_SCATTER, B_SCATTER_ID = (
     "xyz_first", "edge_first", "qc_scatter", "cloud_bias", "scatter", "scatter_identity")
+B_CLOUD_POINT = "cloud_point"       # ... its dX, dWx and dCtr out of one pass over G and Y (pcops_cloud_point_bwd)
 B_TOP, B_SPLIT, B_SPLIT_XYZ = "top", "split", "split_xyz"
 B_ONEPASS, B_ONEPASS_XYZ, B_ONEPASS_GW, B_ONEPASS_EDGE, B_ONEPASS_EDGE_GW = (
     "onepass", "onepass_xyz", "onepass_gw", "onepass_edge", "onepass_edge_gw")
 _ONEPASS = (B_ONEPASS, B_ONEPASS_XYZ, B_ONEPASS_GW, B_ONEPASS_EDGE, B_ONEPASS_EDGE_GW)
 # the arms that read the layer's own stored Y / the Y of the layer below
-_READS_Y = (B_CLOUD, B_SCATTER, B_SCATTER_ID, B_SPLIT, B_SPLIT_XYZ) + _ONEPASS
+_READS_Y = (B_CLOUD, B_CLOUD_POINT, B_SCATTER, B_SCATTER_ID, B_SPLIT, B_SPLIT_XYZ) + _ONEPASS
 _READS_Y_BELOW = (B_TOP, B_SPLIT, B_ONEPASS, B_ONEPASS_GW, B_ONEPASS_EDGE, B_ONEPASS_EDGE_GW)
 
 
@@ -112,15 +114,17 @@ class StackPlan(NamedTuple):
 
 
 def plan_stack(*, R, S, K0, widths, pool, training, need_grad, need_dx, sync, w_aligned, has_b, geom=None, present=(),
-               a0_contiguous=True, rows=False):
+               a0_contiguous=True, rows=False, point_k=None):
     """The StackPlan of a stack: no side effect, no launch.
     R rows in groups of S; K0: width of a dense input; pool: the bits of FusedMLPStack.apply; need_grad / need_dx: a
     backward can happen / reaches the input (the backward arms are only planned for one that can happen); sync: SyncBN;
     w_aligned[l] / has_b[l]: layer l's weight lies at a 16-byte address / it has a bias;
     geom = (B, Nsrc, M) of a gather first layer and present: which of "a0", "ctr", "xyz", "wxyz", "bias" it is given;
-    rows: a compacted row set is given.  Reads the module flags and the library's shape queries, here and nowhere later."""
+    rows: a compacted row set is given; point_k: with bit 4 of pool, the width of the RAW per-point input that a0 holds in
+    place of Q (wxyz then holds its (point_k, C1) weight).  Reads the module flags and the library's shape queries, here and nowhere later."""
     lib = _lib.load()
     L, C1 = len(widths), widths[0]
+    point = bool(pool & 16)
     identity, qc, direct, pool = bool(pool & 2), bool(pool & 4), bool(pool & 8), bool(pool & 1)
     gather = geom is not None
     direct = gather and qc and direct
@@ -144,7 +148,15 @@ def plan_stack(*, R, S, K0, widths, pool, training, need_grad, need_dx, sync, w_
         onepass = int(need_grad and BWD_FUSED and l > 0 and lib.pcops_mlp_bwd_fused_groups(R, K, N, S if top else 0, int(top)))
         if l == 0 and gather:
             B, Nsrc, M = geom
-            if qc:
+            if point:
+                # a0 is the raw per-point input, not a product: no other arm can take it, so a shape or a switch that rules
+                # this one out is the caller's error (pointnet.seg_ops asks cloud_point_fused_supported first)
+                if not (gather and identity and not qc and CLOUD_POINT_FUSED and set(present) == {"a0", "ctr", "wxyz"}
+                        and not rows and not top and M == 1 and Nsrc == S and a0_contiguous and point_k is not None
+                        and lib.pcops_cloud_point_supported(B, S, point_k, C1)):
+                    raise _lib.PcopsError("plan_stack: no per-cloud + per-point first layer for this stack")
+                fwd = F_CLOUD_POINT
+            elif qc:
                 fwd = F_QC
             elif (identity and CLOUD_BIAS and set(present) == {"a0", "ctr"} and not rows and M == 1 and Nsrc == S
                     and a0_contiguous and lib.pcops_cloud_bias_supported(R, S, C1)):
@@ -153,8 +165,8 @@ def plan_stack(*, R, S, K0, widths, pool, training, need_grad, need_dx, sync, w_
                 fwd, store_y = F_GATHER, not virt
             if need_grad:
                 shortcut = "a0" in present and need_dx and identity and not top     # idx = 0..n-1: dQ = dY row for row
-                bwd = (B_XYZ_FIRST if virt else B_EDGE_FIRST if direct else B_QC if qc
-                       else B_CLOUD if (fwd == F_CLOUD and not top) else B_SCATTER_ID if shortcut else B_SCATTER)
+                bwd = (B_CLOUD_POINT if fwd == F_CLOUD_POINT else B_XYZ_FIRST if virt else B_EDGE_FIRST if direct
+                       else B_QC if qc else B_CLOUD if (fwd == F_CLOUD and not top) else B_SCATTER_ID if shortcut else B_SCATTER)
         else:
             xyz_prev = virt and l == 1          # the layer below is the arithmetic first layer
             algebraic = False                   # pcops.h "algebraic backward of a pooled top layer": never reads Y
@@ -265,7 +277,8 @@ class FusedMLPStack(torch.autograd.Function):
           bit 2 a0 is the (B, N, 2 C1) product [Q | Ctr] of ONE GEMM (pcops.h "[Q | Ctr] forms"); bit 3 with bit 2, an
           input that needs no gradient (DGCNN's T-Net on the raw cloud): xyz = the (B, N, 3) input, wxyz = the layer's
           (6, C1) weight, bias = its bias -- their gradients come from ONE streaming pass over the masked gradient
-          (pcops.h pcops_edge_first_*), a0 gets none and no scatter runs
+          (pcops.h pcops_edge_first_*), a0 gets none and no scatter runs; bit 4 with bit 1, a0 is the RAW (B, N, 64) per-point
+          input and wxyz its (64, C1) weight: Y1 = a0 wxyz + ctr[cloud] inside one pass (pcops.h pcops_cloud_point_*)
     per_layer (6 each): weights (K,N), biases (N), gamma, beta, moving_mean, moving_var -- the first two are None
     for a gather first layer.  Returns (R//S, C_L) if pool else (R, C_L)."""
 
@@ -292,7 +305,8 @@ class FusedMLPStack(torch.autograd.Function):
                           has_b=[l[1] is not None for l in layers], geom=geom,
                           present=[n for n, v in (("a0", a0), ("ctr", ctr), ("xyz", xyz), ("wxyz", wxyz), ("bias", bias))
                                    if v is not None],
-                          a0_contiguous=a0 is None or a0.is_contiguous(), rows=rows is not None)
+                          a0_contiguous=a0 is None or a0.is_contiguous(), rows=rows is not None,
+                          point_k=a0.shape[2] if (int(pool) & 16 and a0 is not None) else None)
         identity, pool = bool(int(pool) & 2), bool(int(pool) & 1)
         if plan.layers[0].fwd == F_QC:
             C1 = widths[0]
@@ -373,6 +387,8 @@ class FusedMLPStack(torch.autograd.Function):
                 first = _bwd_qc_scatter(dn, lp.N, p, q, t)
             elif lp.bwd == B_CLOUD:
                 first = _bwd_cloud_bias(dn, lp.N, p, q, t)
+            elif lp.bwd == B_CLOUD_POINT:
+                first = _bwd_cloud_point(dn, lp.N, p, q, t)
             elif lp.bwd in (B_SCATTER, B_SCATTER_ID):
                 first = _bwd_scatter(dn, lp, p, q, t, top)
             elif lp.bwd == B_TOP:
@@ -415,6 +431,11 @@ def _fwd_first(up, lp, Y, piv):
         P = lib.pcops_cloud_bias_rows(up.R)
         part = _f32((P, 2, N), up.dev) if up.training else None
         _lib.call("pcops_cloud_bias_fwd", up.R, S, N, a0.data_ptr(), up.ctr.data_ptr(), Y.data_ptr(), _p(part), piv)
+    elif lp.fwd == F_CLOUD_POINT:     # pcops.h pcops_cloud_point_*
+        P = lib.pcops_cloud_point_rows(B, S)
+        part = _f32((P, 2, N), up.dev) if up.training else None
+        _lib.call("pcops_cloud_point_fwd", B, S, a0.shape[2], N, a0.data_ptr(), up.wxyz.data_ptr(), up.ctr.data_ptr(),
+                  Y.data_ptr(), _p(part), piv)
     else:
         other = up.wxyz is not None or up.bias is not None or up.off4 is not None
         P = lib.pcops_sa_gather_fwd_stats_rows(B, Nsrc, M, S, N, int(a0 is not None), int(up.ctr is not None),
@@ -599,6 +620,20 @@ def _bwd_cloud_bias(dn, N, p, q, t):
     _lib.call("pcops_cloud_bias_bwd", R, dn.S, N, dn.Gm.data_ptr(), sv.Ys[0].data_ptr(), p.data_ptr(), q.data_ptr(),
               t.data_ptr(), _p(d0), d1.data_ptr(), scratch.data_ptr())
     return d0, d1, None, None
+
+
+def _bwd_cloud_point(dn, N, p, q, t):
+    """dX, dCtr and dWx of Y = X Wx + Ctr[cloud] out of ONE pass over the masked gradient and Y: dY is never written"""
+    sv, dev = dn.sv, dn.dev
+    B, Nsrc, K = sv.a0.shape
+    d0 = _f32((B, Nsrc, K), dev) if dn.plan.need_dx else None
+    d1 = _f32((B, 1, N), dev)
+    dw = _f32((K, N), dev)
+    nbytes = int(_lib.load().pcops_cloud_point_bwd_ws(B, Nsrc, K, N))
+    wsp = _f32(nbytes // 4, dev) if nbytes else None
+    _lib.call("pcops_cloud_point_bwd", B, Nsrc, K, N, dn.Gm.data_ptr(), sv.Ys[0].data_ptr(), p.data_ptr(), q.data_ptr(),
+              t.data_ptr(), sv.a0.data_ptr(), sv.wxyz.data_ptr(), _p(d0), dw.data_ptr(), d1.data_ptr(), _p(wsp))
+    return d0, d1, dw, None
 
 
 def _bwd_scatter(dn, lp, p, q, t, top):
@@ -1274,6 +1309,9 @@ FUSE_POOL_ROWS = os.environ.get("PCOPS_FUSE_POOL_ROWS", "1") != "0"    # per-blo
 BWD_FUSED = os.environ.get("PCOPS_BWD_FUSED", "1") != "0"   # one-pass data + weight gradient of narrow layers (pcops_mlp_bwd_fused)
 CLOUD_BIAS = os.environ.get("PCOPS_CLOUD_BIAS", "1") != "0"     # ... its Y = Q + Ctr[cloud] and the backward as streaming passes
 CLOUD_POINT = os.environ.get("PCOPS_CLOUD_POINT", "1") != "0"   # dgcnn_bga's head: per-cloud + per-point first conv without the concat
+# PointNet's segmentation heads: the 64-wide per-point product inside the streaming pass (pcops_cloud_point_*); "0": Q = X Wx
+# through rows_linear and the cloud-bias arm above
+CLOUD_POINT_FUSED = os.environ.get("PCOPS_CLOUD_POINT_FUSED", "1") != "0"
 EDGE_DIRECT = os.environ.get("PCOPS_EDGE_DIRECT", "1") != "0"   # first EdgeConv layer of a stack on an input without gradient
 EDGE_DIRECT_FUSED = os.environ.get("PCOPS_EDGE_DIRECT_FUSED", "1") != "0"   # ... its E^T Gm inside the one-pass backward above
 POOL_TOP = os.environ.get("PCOPS_POOL_TOP", "1") != "0"     # algebraic backward of pooled top layers (fused_mlp._pool_top_backward)
@@ -1310,6 +1348,11 @@ def edge_qc_supported(b, n, s, c):
                 and not _dist.sync_bn_active())
 
 
+def cloud_point_fused_supported(b, n, k, c1):
+    """the first conv on [per-point k | per-cloud] channels has its fused kernels for this shape (pcops.h pcops_cloud_point_*)"""
+    return bool(CLOUD_POINT_FUSED and _lib.load().pcops_cloud_point_supported(int(b), int(n), int(k), int(c1)))
+
+
 def edge_direct_supported(b, n, k, c_in, c1, n_layers, x):
     """the first EdgeConv layer's weight gradient without a scatter (pcops.h pcops_edge_first_*): 3-channel input that
     needs no gradient, a stack of at least two layers on the one-GEMM path"""
@@ -1320,15 +1363,23 @@ def edge_direct_supported(b, n, k, c_in, c1, n_layers, x):
 
 def gather_mlp_stack(idx, pool, training, decay, eps, unbiased, layer_tensors, Q=None, Ctr=None, xyz=None,
                      new_xyz=None, wxyz=None, bias=None, identity_idx=False, pts_cnt=None, QC=None, cat_slot=None,
-                     direct=None):
+                     direct=None, point=None):
     """Grouped stack whose first conv was applied before the grouping:
          Y1[b,j,s,:] = Q[b,idx] + Ctr[b,j] + (xyz[b,idx] - new_xyz[b,j]) wxyz + bias     (terms optional)
     idx (B,M,S) int32, Q (B,N,C1), Ctr (B,M,C1), xyz (B,N,3), new_xyz (B,M,3), wxyz (3,C1), bias (C1);
     layer_tensors[0] supplies only the BN variables of layer 1.  identity_idx: the caller guarantees
     idx[b, 0, s] = s with M = 1 and S = N (group_all), which turns the backward scatter into a reshape.
+    point = (X (B, N, 64), Wx (64, C1)) with Ctr (B, 1, C1) and identity_idx: Y1 = X Wx + Ctr[b] with the product inside the
+    first layer's pass (cloud_point_fused_supported); X and Wx travel in the Q and wxyz slots, their gradients come back there.
     Returns (B*M, C_L) if pool else (B*M*S, C_L)."""
     c = lambda t: t.contiguous() if t is not None else None   # noqa: E731
     S = idx.shape[2]
+    if point is not None:
+        x64, wx = point
+        assert QC is None and Q is None and xyz is None and wxyz is None and bias is None and identity_idx and not pool
+        return FusedMLPStack.apply(x64.contiguous(), c(Ctr), idx.contiguous(), None, None, wx.contiguous(), None, int(S),
+                                   2 | 16, bool(training), float(decay), float(eps), bool(unbiased), None,
+                                   len(layer_tensors), *_flat(layer_tensors, True))
     if QC is not None:
         # QC (B, N, 2 C1) = [Q | Ctr], the product of the layer's input with the concatenated weight (edge_qc_supported)
         assert Q is None and Ctr is None and xyz is None and wxyz is None and bias is None

@@ -10,6 +10,8 @@ Visual dumps (`--visu`, `--visu_mask`: obj / bin / jpg files of the masks, `:254
 accepted.  `--model pointcnn_seg` (PointCNN's BGA model, `PointCNN/evaluate_seg_scenennobjects.py`) runs through the same
 loop: its class head is per point, so every vote's class logits go through the model's `class_scores` (the softmax summed
 over the points) before the votes are summed; `--setting` picks its setting (object_dataset_x3).
+`--model pointnet_seg` (`pointnet/evaluate_seg_scenennobjects.py`) returns its end points as a third output; its loss takes
+them (the transform regulariser).
 
   python -m scanobjectnn_amd.pointnet2.evaluate_seg_scenennobjects --model pointnet2_cls_bga --num_point 1024 \
          --batch_size 32 --model_path log/model.ckpt --test_file test_withmask.npz --num_votes 12
@@ -47,7 +49,8 @@ def eval_seg_votes(net, data, labels, masks, batch_size, num_votes=1, device="cu
                    loss_fn=None, scores_fn=None):
     """net: graph.Model of a *_bga get_model -> (class_pred (B,C), seg_pred (B,N,2)); data (K,N,3), labels (K,), masks
     (K,N) in {0,1}.  Whole batches only (`num_batches = K // BATCH_SIZE`, `:203`).  loss_fn(class_pred, seg_pred, labels,
-    masks) -> total loss of one vote; accumulated as loss * batch / num_votes (`:229`).  scores_fn: the model module's
+    masks) -> total loss of one vote; accumulated as loss * batch / num_votes (`:229`).  A model that returns end points as
+    a third output (pointnet_seg) has them passed to loss_fn as a fifth argument.  scores_fn: the model module's
     optional class_scores hook, applied to every vote's class head before the votes are summed (pointcnn_seg: per-point
     logits (B,P,C) -> the softmax summed over the points); None: identity."""
     if scores_fn is None:
@@ -63,11 +66,11 @@ def eval_seg_votes(net, data, labels, masks, batch_size, num_votes=1, device="cu
         cls_sum = seg_sum = None
         for vote_idx in range(num_votes):
             rotated = provider.rotate_point_cloud_by_angle(pts, vote_idx / float(num_votes) * math.pi * 2)
-            class_pred, seg_pred = net(rotated.contiguous(), is_training=False)
+            class_pred, seg_pred, *extra = net(rotated.contiguous(), is_training=False)
             cls_sum = scores_fn(class_pred) if cls_sum is None else cls_sum + scores_fn(class_pred)
             seg_sum = seg_pred if seg_sum is None else seg_sum + seg_pred
             if loss_fn is not None:
-                loss_sum += float(loss_fn(class_pred, seg_pred, y, mk)) * batch_size / float(num_votes)
+                loss_sum += float(loss_fn(class_pred, seg_pred, y, mk, *extra)) * batch_size / float(num_votes)
         cls_all.append(cls_sum.argmax(dim=1).cpu().numpy())
         seg_all.append(seg_sum.argmax(dim=2).cpu().numpy())
         seen_lab.append(np.asarray(labels[sl]))
@@ -80,10 +83,10 @@ def eval_seg_votes(net, data, labels, masks, batch_size, num_votes=1, device="cu
 
 
 def parse_args(argv=None):
-    from .train import MASK_MODELS, _flag, add_model_flags, resolve_model_flags
+    from .train import ALL_MASK_MODELS, _flag, add_model_flags, resolve_model_flags
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     p.add_argument("--gpu", type=int, default=0, help="GPU to use (:34)")
-    p.add_argument("--model", default="pointnet2_cls_bga", choices=sorted(MASK_MODELS))                 # :35
+    p.add_argument("--model", default="pointnet2_cls_bga", choices=sorted(ALL_MASK_MODELS))                 # :35
     p.add_argument("--batch_size", type=int, default=1)                                       # :36
     p.add_argument("--num_point", type=int, default=1024)                                     # :37
     p.add_argument("--seg_weight", type=float, default=0.5, help="weight of the mask loss in the reported loss (:42)")
@@ -151,7 +154,7 @@ def evaluate(args):
     cur, lab, msk = data_utils.get_current_data_withmask_h5(data, labels, masks, args.num_point, shuffle=False)
     lab, msk = np.squeeze(lab), np.squeeze(msk)
     ev = eval_seg_votes(net, cur, lab, msk, args.batch_size, num_votes=args.num_votes, device=dev,
-                        loss_fn=lambda cp, sp, y, mk: mod.get_loss(cp, sp, y, mk, seg_weight=args.seg_weight)[0],
+                        loss_fn=lambda cp, sp, y, mk, *ep: mod.get_loss(cp, sp, y, mk, *ep, seg_weight=args.seg_weight)[0],
                         scores_fn=getattr(mod, "class_scores", None))
     with open(os.path.join(args.dump_dir, "pred_label.txt"), "w") as fout:                 # :252
         for p, l in zip(ev["pred"], ev["label"]):

@@ -5,6 +5,10 @@ over the GPUs of one node.
   python -m scanobjectnn_amd.pointnet2.train --model pointnet2_cls_ssg --num_point 2048 --batch_size 256 \
          --max_epoch 1 [--train_file x.npz --test_file y.npz]          (synthetic clouds when no file is given)
   python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m scanobjectnn_amd.pointnet2.train ...
+  python -m scanobjectnn_amd.pointnet2.train --model pointnet_seg --batch_size 32 --num_point 1024 \
+         --train_file train_withmask.h5 --test_file test_withmask.h5   (`pointnet/train_seg.py:33-35`: its batch and points)
+  python -m scanobjectnn_amd.pointnet2.train --model pointnet_partseg --batch_size 32 --num_point 1024 \
+         --train_file train_parts.h5 --test_file test_parts.h5         (`pointnet/train_partseg.py`)
 
 Input pipeline, all on the device: the loaded set is uploaded ONCE, centred and normalised there
 (`train.py:100-106` does it on the host: `data_utils.center_data`, `normalize_data`), the per-epoch point subset /
@@ -40,9 +44,14 @@ MODELS = {"pointnet2_cls_ssg": "scanobjectnn_amd.pointnet2.pointnet2_cls_ssg",
           "pointcnn_cls": "scanobjectnn_amd.pointcnn.pointcnn_cls",
           "pointcnn_seg": "scanobjectnn_amd.pointcnn.pointcnn_seg",
           "pointnet_cls": "scanobjectnn_amd.pointnet.pointnet_cls",
-          "pointnet_cls_basic": "scanobjectnn_amd.pointnet.pointnet_cls_basic"}
+          "pointnet_cls_basic": "scanobjectnn_amd.pointnet.pointnet_cls_basic",
+          "pointnet_seg": "scanobjectnn_amd.pointnet.pointnet_seg",
+          "pointnet_partseg": "scanobjectnn_amd.pointnet.pointnet_partseg"}
 # the models that predict a per-point foreground mask beside the class (the reference's train_seg.py trainers)
 MASK_MODELS = frozenset(m for m in MODELS if m.endswith("_bga")) | {"pointcnn_seg"}
+# ... whose get_model also returns end points that their get_loss takes (pointnet/train_seg.py: the transform regulariser)
+MASK_MODELS_END_POINTS = frozenset({"pointnet_seg"})
+ALL_MASK_MODELS = MASK_MODELS | MASK_MODELS_END_POINTS
 # flags a model may take from its own setting when the command line leaves them out (the module's flag_defaults);
 # for every other model these are the defaults
 FLAG_DEFAULTS = {"max_epoch": 250, "batch_size": 16, "learning_rate": 0.001, "decay_step": 200000, "decay_rate": 0.7}
@@ -212,7 +221,7 @@ def train(args):
         _lib.set_deterministic(True)
     mod = importlib.import_module(MODELS[args.model])
     partseg = args.model.endswith("_partseg")
-    with_mask = "parts" if partseg else args.model in MASK_MODELS
+    with_mask = "parts" if partseg else args.model in ALL_MASK_MODELS
     per_rank = args.batch_size // world
     rng = np.random.RandomState(args.seed)          # same stream on every rank -> same epoch order
     gen = torch.Generator(device=dev)
@@ -259,10 +268,14 @@ def train(args):
             out = net(x, is_training=True, bn_decay=bn_decay)
             if partseg:
                 m = msk[sl]
-                loss = mod.get_loss(out, m)
+                seg_pred, end_points = EV.split_output(out)     # pointnet_partseg: (seg_pred, end_points)
+                loss = mod.get_loss(seg_pred, m) if end_points is None else mod.get_loss(seg_pred, m, end_points)
             elif with_mask:
                 m = msk[sl]
-                loss = mod.get_loss(out[0], out[1], y, m, seg_weight=args.seg_weight)[0]
+                if args.model in MASK_MODELS_END_POINTS:
+                    loss = mod.get_loss(out[0], out[1], y, m, out[2], seg_weight=args.seg_weight)[0]
+                else:
+                    loss = mod.get_loss(out[0], out[1], y, m, seg_weight=args.seg_weight)[0]
             else:
                 logits, end_points = EV.split_output(out)      # SpiderCNN returns bare logits
                 loss = EV.model_loss(mod, logits, y, end_points)
@@ -276,7 +289,7 @@ def train(args):
             with torch.no_grad():
                 tot[0] += loss.detach()
                 if partseg:                      # point accuracy (`train_partseg.py:237-241`)
-                    tot[1] += (out.argmax(dim=2) == m).sum()
+                    tot[1] += (seg_pred.argmax(dim=2) == m).sum()
                     tot[2] += per_rank * args.num_point
                 else:
                     tot[1] += (scores(EV.split_output(out)[0]).argmax(dim=1) == y).sum()
