@@ -1,5 +1,5 @@
-"""Settings of the PointCNN models -- the numbers of `PointCNN/pointcnn_cls/modelnet_x3_l4.py` and
-`PointCNN/pointcnn_seg/object_dataset_x3.py` as plain namespaces.  `as_setting` takes any object with the same attributes,
+"""Settings of the PointCNN models -- the numbers of `PointCNN/pointcnn_cls/modelnet_x3_l4.py`, its 40-class twin
+`modelnet40_expt.py` and `PointCNN/pointcnn_seg/object_dataset_x3.py` as plain namespaces.  `as_setting` takes any object with the same attributes,
 so tests build much smaller ones."""
 import math
 from types import SimpleNamespace
@@ -57,6 +57,9 @@ modelnet_x3_l4 = make(
     fc_params=fc_params([(128 * _x, 0.0), (64 * _x, 0.8)]),
     with_global=True, sampling='random', with_X_transformation=True, sorting_method=None)
 
+# the ModelNet40 experiment (train on synthetic, test on real): modelnet_x3_l4 with 40 classes, nothing else differs
+modelnet40_expt = make(**dict(vars(modelnet_x3_l4), num_class=40))
+
 object_dataset_x3 = make(
     xconv_params=xconv_params(_ENCODER_X3),
     xdconv_params=xdconv_params([(16, 6, 3, 3),
@@ -68,9 +71,12 @@ object_dataset_x3 = make(
     fc_params_segmentation=fc_params([(32 * _x, 0.0), (32 * _x, 0.5)]),
     with_global=True, sampling='random', with_X_transformation=True, sorting_method=None, data_dim=3)
 
-SETTINGS = {"modelnet_x3_l4": modelnet_x3_l4, "object_dataset_x3": object_dataset_x3}
+SETTINGS = {"modelnet_x3_l4": modelnet_x3_l4, "modelnet40_expt": modelnet40_expt, "object_dataset_x3": object_dataset_x3}
 # the setting a model takes when --setting is left out
 MODEL_DEFAULT = {"pointcnn_cls": "modelnet_x3_l4", "pointcnn_seg": "object_dataset_x3"}
+# the models that take --num_class from their setting when it is left out (pointcnn_seg keeps the command line's default,
+# like its other flags)
+NUM_CLASS_FROM_SETTING = frozenset({"pointcnn_cls"})
 
 
 def get(name):

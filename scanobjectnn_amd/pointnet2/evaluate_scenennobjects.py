@@ -166,7 +166,7 @@ def parse_args(argv=None):
     p.add_argument("--with_bg", type=_flag, default=True)                                     # :35
     p.add_argument("--norm", type=_flag, default=True)                                        # :36
     p.add_argument("--center_data", type=_flag, default=True)                                 # :37
-    p.add_argument("--num_class", type=int, default=15)                                       # :38
+    p.add_argument("--num_class", type=int, default=None, help="[15; pointcnn_cls: its setting's]")   # :38
     p.add_argument("--test_file", default="", help=".npz / .h5 / pickled split list (:40); synthetic clouds if empty")
     p.add_argument("--data_path", default="", help="root of the raw objects_bin/ files for pickled split lists")
     p.add_argument("--normal", action="store_true", help="accepted for CLI compatibility (:42); never read")

@@ -65,16 +65,20 @@ def add_model_flags(p):
     p.add_argument("--num_gaussians", type=int, default=5, help="3dmfv_net_cls: grid subdivisions per axis (5: 125 Gaussians)")
     p.add_argument("--gmm_variance", type=float, default=0.04, help="3dmfv_net_cls: variance of every grid Gaussian")
     p.add_argument("--setting", default=None, help="pointcnn_cls / pointcnn_seg: the setting (PointCNN/train.py:41) "
-                   "[the model's own: modelnet_x3_l4 / object_dataset_x3].  pointcnn_cls takes the flags it is not given from "
-                   "its setting; pointcnn_seg keeps this file's defaults: give --learning_rate 0.01 --decay_step 8000 "
+                   "[the model's own: modelnet_x3_l4 / object_dataset_x3; modelnet40_expt: modelnet_x3_l4 with 40 classes].  "
+                   "pointcnn_cls takes the flags it is not given from its setting, --num_class included; pointcnn_seg keeps this file's defaults: give --learning_rate 0.01 --decay_step 8000 "
                    "--decay_rate 0.5 --batch_size 32 --max_epoch 400 for object_dataset_x3's numbers")
 
 
-def resolve_model_flags(args):
-    """--setting left out: the model's own setting (modelnet_x3_l4 for every model that reads none)"""
+def resolve_model_flags(args, num_class=15, setting=None):
+    """--setting left out: the model's own setting (modelnet_x3_l4 for every model that reads none); `setting`: a command
+    line's own {model: setting} defaults, looked up first.  --num_class left out: the class count of the setting for the
+    models that take it from there (pointcnn_cls), `num_class` for every other model."""
+    from ..pointcnn import settings as S
     if args.setting is None:
-        from ..pointcnn.settings import MODEL_DEFAULT
-        args.setting = MODEL_DEFAULT.get(args.model, "modelnet_x3_l4")
+        args.setting = (setting or {}).get(args.model) or S.MODEL_DEFAULT.get(args.model, "modelnet_x3_l4")
+    if getattr(args, "num_class", num_class) is None:
+        args.num_class = S.get(args.setting).num_class if args.model in S.NUM_CLASS_FROM_SETTING else num_class
     return args
 
 
@@ -115,7 +119,7 @@ def parse_args(argv=None):
     p.add_argument("--with_bg", type=_flag, default=True, help="keep background points of raw .bin objects (:30)")
     p.add_argument("--norm", type=_flag, default=True, help="divide every cloud by its max L2 norm (:31)")
     p.add_argument("--center_data", type=_flag, default=True, help="subtract every cloud's centroid (:32)")
-    p.add_argument("--num_class", type=int, default=15)             # :33
+    p.add_argument("--num_class", type=int, default=None, help="[15; pointcnn_cls: its setting's]")    # :33
     p.add_argument("--num_point", type=int, default=1024)           # :38
     p.add_argument("--max_epoch", type=int, default=None, help="[250]")             # :39
     p.add_argument("--batch_size", type=int, default=None, help="GLOBAL batch, split over the ranks [16]")
