@@ -520,6 +520,31 @@ int pcops_mlp_pool_top_wsparse(int M, int Kp, int N, int S, const float *gout, c
                                const unsigned char *argmax, const float *pool_scale, const float *pool_shift,
                                const float *p, const float *Yprev, const float *prev_scale, const float *prev_shift,
                                float *Ssp, float *cfsum, pcops_stream_t stream);
+/* ... for MANY SMALL groups on uncompacted rows (S = 32 / 64 with N = 128: nearly every row is some channel's arg-max, a
+ * compact addend would be as large as X).  The sparse halves stay on the chip, each call is ONE pass over Yprev:
+ *   pcops_mlp_dgrad_top_groups   Gprev [M][Kp] = mask_prev . (X Mq + vconst + sum_c cf[g,c] Wt[c,:] on row argmax[g,c]),
+ *                                cf = p gout where pool_scale ysel + pool_shift > 0, else 0 (pcops_mlp_pool_top_addend's
+ *                                coefficient); stats_partial [pcops_mlp_stats_rows(M)][2][Kp] as pcops_mlp_gemm_dgrad_top
+ *   pcops_mlp_wgrad_top_groups   gram = X^T X (full, mirrored), xsum = X^T 1, Ssp [Kp][N] = X^T (p.G), cfsum [N] = 1^T (p.G):
+ *                                what pcops_mlp_gram + pcops_mlp_pool_top_wsparse give; partial: scratch of
+ *                                pcops_mlp_pool_top_groups_partial(M, Kp, N) floats (a copy of Kp Kp + Kp + Kp N + N per
+ *                                workgroup)
+ * prep, the small products and finish are the ones above.  Both take Kp == 64, N % 32 == 0 with 2 Kp <= N <= 256, S = 32 or
+ * 64, M % S == 0, M Kp 4 below the 32-bit bound of the calls above, 16-byte aligned rows; PCOPS_ERR_UNSUPPORTED otherwise,
+ * before any pointer check.  prev_scale / prev_shift are required.  pcops_mlp_pool_top_groups_supported is the ONE answer a
+ * planner asks: that shape AND M >= 262144 (below it the Y this form does not store stays in the cache level; a planning
+ * threshold, not a kernel limit).  No float atomics, every sum in a fixed order. */
+int pcops_mlp_pool_top_groups_supported(int M, int Kp, int N, int S);
+int pcops_mlp_pool_top_groups_partial(int M, int Kp, int N);
+int pcops_mlp_dgrad_top_groups(int M, int Kp, int N, int S, const float *Yprev, const float *prev_scale,
+                               const float *prev_shift, const float *Mq, const float *vconst, const float *gout,
+                               const float *ysel, const unsigned char *argmax, const float *pool_scale,
+                               const float *pool_shift, const float *p, const float *Wt, float *Gprev, float *stats_partial,
+                               pcops_stream_t stream);
+int pcops_mlp_wgrad_top_groups(int M, int Kp, int N, int S, const float *Yprev, const float *prev_scale,
+                               const float *prev_shift, const float *gout, const float *ysel, const unsigned char *argmax,
+                               const float *pool_scale, const float *pool_shift, const float *p, float *partial, float *gram,
+                               float *xsum, float *Ssp, float *cfsum, pcops_stream_t stream);
 /* The layer that FOLLOWS an arithmetic first layer  y1[row][k] = fma(dz, w2[k], fma(dy, w1[k], fma(dx, w0[k], b[k])))
  * (grouped xyz offsets only: the first set-abstraction level, pointnet_util.py:44-54 with points == None).  y1 is
  * rebuilt from off4 [M][4] = (dx, dy, dz, 0) and xyzw [4][C1] (rows w0, w1, w2, b) wherever the plain entry points

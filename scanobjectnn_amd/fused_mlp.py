@@ -96,6 +96,7 @@ class LayerPlan(NamedTuple):
     pooled: str         # pooled epilogue fused into the forward product: "" | "raw" (plain rows) | "rows" (per 16-row block)
     bwd: str            # backward arm (B_*); "" where no backward can happen
     count: int          # what the arm's launches are sized by: one-pass groups / weight-gradient splits
+    groups: bool = False    # B_TOP in its many-small-groups form: the sparse halves inside the two passes over X
 
 
 class StackPlan(NamedTuple):
@@ -170,6 +171,7 @@ def plan_stack(*, R, S, K0, widths, pool, training, need_grad, need_dx, sync, w_
         else:
             xyz_prev = virt and l == 1          # the layer below is the arithmetic first layer
             algebraic = False                   # pcops.h "algebraic backward of a pooled top layer": never reads Y
+            groups = False                      # ... in the form for many small groups (pcops_mlp_*_top_groups)
             if xyz_prev:
                 fwd = F_XYZ
             elif rows and top and l > 0 and FUSE_POOL_ROWS and lib.pcops_mlp_gemm_fwd_pool_rows_supported(R, K, N):
@@ -187,6 +189,11 @@ def plan_stack(*, R, S, K0, widths, pool, training, need_grad, need_dx, sync, w_
                 fwd, pooled = F_POOL, "raw"
                 algebraic = bool(need_grad and POOL_TOP and S >= 64 and N >= 2 * K and has_b[l]
                                  and lib.pcops_mlp_pool_top_supported(R, K, N, S))
+                # many small groups (SA1: 64 -> 128 over S = 32): the sparse halves inside the two passes over X
+                # (pcops.h pcops_mlp_*_top_groups); it replaces the one-pass arm for these shapes
+                groups = bool(need_grad and POOL_TOP and POOL_TOP_GROUPS and l > 0 and has_b[l] and w_aligned[l]
+                              and lib.pcops_mlp_pool_top_groups_supported(R, K, N, S))
+                algebraic = algebraic or groups
                 store_y = need_grad and not algebraic
             else:
                 fwd = F_GEMM
@@ -206,7 +213,7 @@ def plan_stack(*, R, S, K0, widths, pool, training, need_grad, need_dx, sync, w_
                 count = onepass
             elif need_grad:
                 bwd, count = (B_SPLIT_XYZ if xyz_prev else B_SPLIT), lib.pcops_mlp_wgrad_splits(R, K, N)
-        layers.append(LayerPlan(fwd, K, N, bool(store_y), pooled, bwd, int(count)))
+        layers.append(LayerPlan(fwd, K, N, bool(store_y), pooled, bwd, int(count), bool(bwd == B_TOP and groups)))
     for l, lp in enumerate(layers):     # an arm that reads layer l's Y exists only where the forward stores it
         reads = (lp.bwd in _READS_Y or (l + 1 < L and layers[l + 1].bwd in _READS_Y_BELOW)
                  or (need_grad and not pool and l == L - 1))
@@ -789,12 +796,20 @@ def _pool_top_backward(dn, l, lp, p, q, t):
     Gprev = part = None
     # the Gram matrix of the input first: with it the layer's two K-sized products (W diag(q) W^T for the data gradient, gram W diag(q)
     # for the weight gradient) are independent of everything else and leave in ONE launch
-    scratch = _f32(lp.count * (K * K + K), dev)
     gram, xsum = _f32((K, K), dev), _f32(K, dev)
-    if rows is not None:        # X^T diag(w) X and X^T w
+    Ssp, cfsum = _f32((K, N), dev), _f32(N, dev)
+    if lp.groups:               # ... and the sparse half of the weight gradient from the same staging of X
+        wpart = _f32(int(lib.pcops_mlp_pool_top_groups_partial(R, K, N)), dev)
+        _lib.call("pcops_mlp_wgrad_top_groups", R, K, N, S, Yprev.data_ptr(), psc.data_ptr(), psh.data_ptr(),
+                  grad_out.data_ptr(), ysel.data_ptr(), argmax.data_ptr(), sc.data_ptr(), sh.data_ptr(), p.data_ptr(),
+                  wpart.data_ptr(), gram.data_ptr(), xsum.data_ptr(), Ssp.data_ptr(), cfsum.data_ptr())
+        del wpart               # (the workgroups' partial copies: dead before Gprev is allocated)
+    elif rows is not None:      # X^T diag(w) X and X^T w
+        scratch = _f32(lp.count * (K * K + K), dev)
         _lib.call("pcops_mlp_gram_rows", R, K, Yprev.data_ptr(), K, _p(psc), _p(psh), scratch.data_ptr(),
                   gram.data_ptr(), xsum.data_ptr(), rref)
     else:
+        scratch = _f32(lp.count * (K * K + K), dev)
         _lib.call("pcops_mlp_gram", R, K, Yprev.data_ptr(), K, _p(psc), _p(psh), scratch.data_ptr(),
                   gram.data_ptr(), xsum.data_ptr())
     dW = _f32((K, N), dev)
@@ -811,12 +826,15 @@ def _pool_top_backward(dn, l, lp, p, q, t):
             v = _f32(K, dev)
             _lib.call("pcops_small_gemm", 1, N, K, u.data_ptr(), N, Wt.data_ptr(), K, v.data_ptr(), K)
         G = R // S
-        # (compacted rows: the addend is indexed by the compacted row itself)
-        addend = _f32((R if rows is not None else G * min(S, N), K), dev)
-        rowmap = torch.empty(R, dtype=torch.int32, device=dev)
         Gprev = _f32((R, K), dev)
         part = _f32((lib.pcops_mlp_stats_rows(R), 2, K), dev) if psc is not None else None
-        if rows is not None:
+        if lp.groups:           # the addend rows are built in the kernel: no addend, no row map in memory
+            _lib.call("pcops_mlp_dgrad_top_groups", R, K, N, S, Yprev.data_ptr(), psc.data_ptr(), psh.data_ptr(),
+                      Mq.data_ptr(), v.data_ptr(), grad_out.data_ptr(), ysel.data_ptr(), argmax.data_ptr(), sc.data_ptr(),
+                      sh.data_ptr(), p.data_ptr(), Wt.data_ptr(), Gprev.data_ptr(), part.data_ptr())
+        elif rows is not None:  # (compacted rows: the addend is indexed by the compacted row itself)
+            addend = _f32((R, K), dev)
+            rowmap = torch.empty(R, dtype=torch.int32, device=dev)
             _lib.call("pcops_mlp_pool_top_addend_rows", R, K, N, S, grad_out.data_ptr(), ysel.data_ptr(),
                       argmax.data_ptr(), sc.data_ptr(), sh.data_ptr(), p.data_ptr(), Wt.data_ptr(), addend.data_ptr(),
                       rowmap.data_ptr(), rref)
@@ -824,18 +842,19 @@ def _pool_top_backward(dn, l, lp, p, q, t):
                       v.data_ptr(), addend.data_ptr(), addend.shape[0], rowmap.data_ptr(), Gprev.data_ptr(), _p(part),
                       rref)
         else:
+            addend = _f32((G * min(S, N), K), dev)
+            rowmap = torch.empty(R, dtype=torch.int32, device=dev)
             _lib.call("pcops_mlp_pool_top_addend", R, K, N, S, grad_out.data_ptr(), ysel.data_ptr(), argmax.data_ptr(),
                       sc.data_ptr(), sh.data_ptr(), p.data_ptr(), Wt.data_ptr(), addend.data_ptr(), rowmap.data_ptr())
             _lib.call("pcops_mlp_gemm_dgrad_top", R, K, Yprev.data_ptr(), _p(psc), _p(psh), Mq.data_ptr(),
                       v.data_ptr(), addend.data_ptr(), addend.shape[0], rowmap.data_ptr(), Gprev.data_ptr(), _p(part))
-    # weight gradient
-    Ssp, cfsum = _f32((K, N), dev), _f32(N, dev)
-    if rows is not None:
+    # sparse half of the weight gradient (the groups form has it out of the Gram pass already)
+    if rows is not None and not lp.groups:
         wpart = _f32(int(lib.pcops_mlp_pool_top_wsparse_rows_partial(K, N)), dev)
         _lib.call("pcops_mlp_pool_top_wsparse_rows", R, K, N, S, grad_out.data_ptr(), ysel.data_ptr(), argmax.data_ptr(),
                   sc.data_ptr(), sh.data_ptr(), p.data_ptr(), Yprev.data_ptr(), _p(psc), _p(psh),
                   Ssp.data_ptr(), cfsum.data_ptr(), wpart.data_ptr(), rref)
-    else:
+    elif not lp.groups:
         _lib.call("pcops_mlp_pool_top_wsparse", R, K, N, S, grad_out.data_ptr(), ysel.data_ptr(), argmax.data_ptr(),
                   sc.data_ptr(), sh.data_ptr(), p.data_ptr(), Yprev.data_ptr(), _p(psc), _p(psh),
                   Ssp.data_ptr(), cfsum.data_ptr())
@@ -1316,6 +1335,7 @@ EDGE_DIRECT = os.environ.get("PCOPS_EDGE_DIRECT", "1") != "0"   # first EdgeConv
 EDGE_DIRECT_FUSED = os.environ.get("PCOPS_EDGE_DIRECT_FUSED", "1") != "0"   # ... its E^T Gm inside the one-pass backward above
 POOL_TOP = os.environ.get("PCOPS_POOL_TOP", "1") != "0"     # algebraic backward of pooled top layers (fused_mlp._pool_top_backward)
 POOL_TOP_ROWS = os.environ.get("PCOPS_POOL_TOP_ROWS", "1") != "0"    # ... of the stacks over compacted rows too (the *_rows forms)
+POOL_TOP_GROUPS = os.environ.get("PCOPS_POOL_TOP_GROUPS", "1") != "0"    # ... of many small uncompacted groups (the *_groups forms)
 # the step's short generic launches folded into their neighbours (round 6): db out of the FC head's dW launch, the algebraic top
 # layer's operand / closing sums as one launch each, one concatenation for the gradient of a split weight (split_rows), the
 # whole-cloud group's index built once, the smoothed cross entropy as one launch per direction; "0": the torch forms (A/B, tests)
