@@ -8,6 +8,8 @@
 // would be as large as X.  Here the sparse halves never leave the chip: two kernels, each ONE pass over Yprev,
 //   dgrad_top_groups_kernel   X Mq on the fp32 matrix pipe (Mq resident in registers), a tile's addend rows built from
 //                             (gout, ysel, argmax) and the LDS-resident W^T, epilogue + statistics, one float4 store
+//   dgrad_top_groups_mm_kernel   the same at N = 128 with the tile's addend as ONE product P W^T on split bf16 operands, the
+//                             default there (PCOPS_POOL_TOP_GROUPS_MM=0: the kernel above for every N)
 //   wgrad_top_groups_kernel   X^T X (upper 32 x 32 blocks), X^T 1, X^T (p.G), 1^T (p.G) from one staged image of X
 // Both are persistent over 64-row tiles (whole groups), the next tile's rows and (gout, ysel, argmax) triples requested
 // before this tile's arithmetic.  No float atomics; every sum in a fixed order (channel-ascending per row, tiles in
@@ -239,6 +241,236 @@ __global__ __launch_bounds__(256) void dgrad_top_groups_kernel(long long M, int 
     }
 }
 
+// ------------------------------------------------------------------------------------------------ data gradient, N = 128
+// The same tile loop with the tile's addend as ONE product on the 16-bit matrix pipe: addend = P W^T, P [64][N] with
+// P[r][c] = cf[g(r)][c] where argmax[g(r)][c] == r, else 0.  Its cost is fixed -- it does not depend on how the hits are spread
+// over the rows -- where the walk above is serial in a row's hits.  Split operands (mlp.hip split3: x = h + m + l in bf16
+// pieces), six products hh | lh, mh, mm, hm, hl on v_mfma_f32_32x32x16_bf16, large and small terms in separate accumulators.
+//   B  W^T's pieces as ready fragments in LDS, split once per workgroup: [piece][k-step][column block][lane] x 8 bf16 (48 KB)
+//   A  built in registers: the triple owners store cf pre-split (three bf16 arrays) and the arg-max bytes per (group, channel);
+//      for a k-step a lane at (row, half) reads 8 arg-max bytes and 3 x 8 pieces (one address per half: broadcast reads) and
+//      keeps the entries whose arg-max is its row.  An arg-max >= S equals no row; cf == 0 is three zero pieces.
+// X Mq runs on split operands as well (24 instead of 32 matrix instructions of twice the length; measured).
+// The wave that owns a 32 x 32 block holds X Mq and the addend in the same accumulator layout and writes (acc + v) + addend
+// into the tile image that held X (one more barrier; a thread's epilogue reads exactly the floats its next staging overwrites).
+// LDS 78.5 KB: two workgroups per CU.  N = 128 is the only width <= 128 the *_groups forms take (N >= 2 Kp).
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int NM = 128;           // the width of the matrix form
+constexpr int NKS = NM / 16;      // its k-steps
+
+// two fp32 values as three packed bf16 pairs (the arithmetic of mlp.hip's split3_pair)
+__device__ __forceinline__ void split3_pair(float a, float b, unsigned &h, unsigned &m, unsigned &l) {
+    const f32x2 v = {a, b};
+    const bf16x2 hh = __builtin_convertvector(v, bf16x2);
+    const f32x2 r1 = v - __builtin_convertvector(hh, f32x2);
+    const bf16x2 mm = __builtin_convertvector(r1, bf16x2);
+    const f32x2 r2 = r1 - __builtin_convertvector(mm, f32x2);
+    const bf16x2 ll = __builtin_convertvector(r2, bf16x2);
+    h = __builtin_bit_cast(unsigned, hh); m = __builtin_bit_cast(unsigned, mm); l = __builtin_bit_cast(unsigned, ll);
+}
+
+// Four arg-max bytes XORed with the lane's row (every byte < 128: the staged arg-max is clamped to 127, a row is < 64) -> 0xff
+// in the bytes that are zero, four bytes at a time: (x | 0x80) - 1 keeps bit 7 of a byte unless the byte was zero and never
+// borrows from its neighbour.  The pair of words that mask a fragment's four bf16 pairs is the mask's bytes doubled (v_perm).
+// (As a compare and a select per byte the fragment build was 56 of a k-step's 70 vector instructions.)
+__device__ __forceinline__ unsigned zero_bytes(unsigned x) {
+    const unsigned hit = ~((x | 0x80808080u) - 0x01010101u) & 0x80808080u;
+    return (hit << 1) - (hit >> 7);
+}
+__device__ __forceinline__ unsigned double_bytes(unsigned m, int hi) {
+    return __builtin_amdgcn_perm(m, m, hi ? 0x03030202u : 0x01010000u);
+}
+
+__global__ __launch_bounds__(256, 2) void dgrad_top_groups_mm_kernel(int M, int S, const float *__restrict__ Yprev,
+                                                                     const float *__restrict__ psc, const float *__restrict__ psh,
+                                                                     const float *__restrict__ Mq, const float *__restrict__ vconst,
+                                                                     const float *__restrict__ gout, const float *__restrict__ ysel,
+                                                                     const unsigned char *__restrict__ arg,
+                                                                     const float *__restrict__ sc, const float *__restrict__ sh,
+                                                                     const float *__restrict__ p, const float *__restrict__ Wt,
+                                                                     float *__restrict__ Gprev, float *__restrict__ stats) {
+    constexpr int N = NM;
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    u32x4 *wf = reinterpret_cast<u32x4 *>(lds);                              // [3][NKS][2][64] fragments of 8 bf16
+    float *xs = lds + 3 * NKS * 2 * 64 * 4;                                  // [TR][XLD]: X, then the result tile
+    float *cst = xs + TR * XLD;                                              // prev_scale, prev_shift, vconst [KP] each
+    float *pv = cst + 3 * KP;                                                // pool_scale, pool_shift, p [NMAX] each
+    unsigned short *cfp = reinterpret_cast<unsigned short *>(pv + 3 * NMAX);  // [3 pieces][2 groups][NM]
+    unsigned char *amb = reinterpret_cast<unsigned char *>(cfp + 3 * 2 * NM);  // [2 groups][NM]
+    u32x4 *qlf = reinterpret_cast<u32x4 *>(amb + 2 * NM);                     // Mq's third piece, [4 k-steps][2][64] fragments
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, row = tid >> 2;
+    const int gpt = TR / S;
+    const int G = M / S, ntiles = (M + TR - 1) / TR;
+
+    // W^T [N][KP] as B fragments: element j of lane (l32, h) at k-step ks, column block cb is W^T[16 ks + 8 h + j][32 cb + l32]
+    for (int i = tid; i < NKS * 2 * 64; i += 256) {
+        const float *src = Wt + (16 * (i >> 7) + 8 * ((i >> 5) & 1)) * KP + 32 * ((i >> 6) & 1) + (i & 31);
+        u32x4 fh, fm, fl;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            unsigned a, b, c;
+            split3_pair(src[2 * q * KP], src[(2 * q + 1) * KP], a, b, c);
+            fh[q] = a; fm[q] = b; fl[q] = c;
+        }
+        wf[i] = fh; wf[NKS * 128 + i] = fm; wf[2 * NKS * 128 + i] = fl;
+    }
+    if (tid < KP) { cst[tid] = psc[tid]; cst[KP + tid] = psh[tid]; cst[2 * KP + tid] = vconst[tid]; }
+    if (tid < N) { pv[tid] = sc[tid]; pv[NMAX + tid] = sh[tid]; pv[2 * NMAX + tid] = p[tid]; }
+    const int l32 = lane & 31, h = lane >> 5, row0 = 32 * (wave >> 1), col0 = 32 * (wave & 1);
+    // the wave's 32 columns of Mq as the B operand, three bf16 pieces: element j of k-step ks is Mq[16 ks + 8 h + j][col0 + l32].
+    // The two large pieces in registers, the third in LDS (with all three in registers hipcc spilled 20 bytes a lane)
+    u32x4 qh[4], qm[4];
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const float *src = Mq + (16 * ks + 8 * h + 2 * q) * KP + col0 + l32;
+            unsigned a, b, c;
+            split3_pair(src[0], src[KP], a, b, c);
+            qh[ks][q] = a; qm[ks][q] = b;
+            if (wave < 2) reinterpret_cast<unsigned *>(qlf + (2 * ks + wave) * 64 + lane)[q] = c;
+        }
+    float4 s1[4], s2[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) s1[k] = s2[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+
+    // the wave's rows lie in ONE group: group (S = 32: its row block; S = 64: the tile's only one) and the lane's row in it
+    const int glw = S == 32 ? (wave >> 1) : 0;
+    const unsigned rig4 = (unsigned)((S == 32 ? 0 : row0) + l32) * 0x01010101u;
+    const unsigned short *cfa = cfp + glw * NM + 8 * h;
+    const unsigned char *ama = amb + glw * NM + 8 * h;
+    const u32x4 *wfa = wf + 64 * (wave & 1) + lane;
+    // the request and the triple in 32-bit indices (M Kp 4 < 2^31: groups_shape_ok; as 64-bit values the group count lived in
+    // a register pair that hipcc spilled, and a scratch reload in the tile body is a vector-memory load waited for with
+    // vmcnt(0) behind the request).  One triple per thread: gpt N <= 256.  Unconditional loads at clamped addresses, as above.
+    const int gch = tid & (NM - 1), ggl = tid >> 7;                           // the thread's (group in tile, channel)
+    auto request = [&](TileRegs &t, int tile) {
+        const int tl = tile < ntiles ? tile : ntiles - 1;
+        const int g = tl * gpt + (ggl < gpt ? ggl : 0);
+        const unsigned o = (unsigned)(g < G ? g : G - 1) * NM + gch;
+        t.go[0] = gout[o]; t.ys[0] = ysel[o]; t.am[0] = arg[o];
+        const int r = tl * TR + row;
+        const float *src = Yprev + (unsigned)(r < M ? r : M - 1) * KP;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) t.y[i] = *reinterpret_cast<const float4 *>(src + tcol<true>(i));
+    };
+    auto do_tile = [&](int tile, TileRegs &cur, TileRegs &nxt) {
+        request(nxt, tile + (int)gridDim.x);
+        const bool in = tile * TR + row < M;
+        // ---- stage X = relu(bn(Yprev)) (rows past the end: zero), the coefficients' pieces and the arg-max bytes
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int c = tcol<true>(k);
+            *reinterpret_cast<float4 *>(xs + row * XLD + c) =
+                bn_relu4(cur.y[k], *reinterpret_cast<const float4 *>(cst + c), *reinterpret_cast<const float4 *>(cst + KP + c), in);
+        }
+        if (tid < gpt * N) {
+            // cf (pool_top_addend's coefficient): p g where relu(bn(ysel)) > 0; 0 for a group past the end
+            const bool live = tile * gpt + ggl < G && fmaf(cur.ys[0], pv[gch], pv[NMAX + gch]) > 0.f;
+            unsigned ch, cm, cl;
+            split3_pair(live ? pv[2 * NMAX + gch] * cur.go[0] : 0.f, 0.f, ch, cm, cl);
+            cfp[tid] = (unsigned short)ch; cfp[2 * NM + tid] = (unsigned short)cm; cfp[4 * NM + tid] = (unsigned short)cl;
+            amb[tid] = (unsigned char)(cur.am[0] < 127 ? cur.am[0] : 127);   // (>= S either way: it equals no row)
+        }
+        __syncthreads();
+        // ---- X Mq on split operands too: four k-steps, X's pieces made from the staged fp32 row as it is read
+        f32x16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, accs = acc;
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) {
+            const float *xr = xs + (row0 + l32) * XLD + 16 * ks + 8 * h;
+            const float4 x0 = *reinterpret_cast<const float4 *>(xr), x1 = *reinterpret_cast<const float4 *>(xr + 4);
+            u32x4 xh, xm, xl;
+            { unsigned a, b, c; split3_pair(x0.x, x0.y, a, b, c); xh[0] = a; xm[0] = b; xl[0] = c; }
+            { unsigned a, b, c; split3_pair(x0.z, x0.w, a, b, c); xh[1] = a; xm[1] = b; xl[1] = c; }
+            { unsigned a, b, c; split3_pair(x1.x, x1.y, a, b, c); xh[2] = a; xm[2] = b; xl[2] = c; }
+            { unsigned a, b, c; split3_pair(x1.z, x1.w, a, b, c); xh[3] = a; xm[3] = b; xl[3] = c; }
+            const bf16x8 ah = __builtin_bit_cast(bf16x8, xh), am = __builtin_bit_cast(bf16x8, xm), al = __builtin_bit_cast(bf16x8, xl);
+            const bf16x8 bh = __builtin_bit_cast(bf16x8, qh[ks]), bm = __builtin_bit_cast(bf16x8, qm[ks]);
+            const bf16x8 bl = __builtin_bit_cast(bf16x8, qlf[(2 * ks + (wave & 1)) * 64 + lane]);
+            accs = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, accs, 0, 0, 0);
+            accs = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bh, accs, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc, 0, 0, 0);
+            accs = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bm, accs, 0, 0, 0);
+            accs = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bm, accs, 0, 0, 0);
+            accs = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, accs, 0, 0, 0);
+        }
+        acc += accs;
+        // ---- the addend of the wave's block, P W^T over ascending channel blocks of 16
+        f32x16 big = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, sml = big;
+#pragma unroll
+        for (int ks = 0; ks < NKS; ++ks) {
+            const uint2 a = *reinterpret_cast<const uint2 *>(ama + 16 * ks);
+            u32x4 ph = *reinterpret_cast<const u32x4 *>(cfa + 16 * ks);
+            u32x4 pm = *reinterpret_cast<const u32x4 *>(cfa + 2 * NM + 16 * ks);
+            u32x4 pl = *reinterpret_cast<const u32x4 *>(cfa + 4 * NM + 16 * ks);
+            const unsigned m0 = zero_bytes(a.x ^ rig4), m1 = zero_bytes(a.y ^ rig4);
+            const u32x4 mk = {double_bytes(m0, 0), double_bytes(m0, 1), double_bytes(m1, 0), double_bytes(m1, 1)};
+            ph &= mk; pm &= mk; pl &= mk;
+            const bf16x8 ah = __builtin_bit_cast(bf16x8, ph), am = __builtin_bit_cast(bf16x8, pm), al = __builtin_bit_cast(bf16x8, pl);
+            const bf16x8 bh = __builtin_bit_cast(bf16x8, wfa[ks * 128]);
+            const bf16x8 bm = __builtin_bit_cast(bf16x8, wfa[(NKS + ks) * 128]);
+            const bf16x8 bl = __builtin_bit_cast(bf16x8, wfa[(2 * NKS + ks) * 128]);
+            sml = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, sml, 0, 0, 0);
+            sml = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bh, sml, 0, 0, 0);
+            big = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, big, 0, 0, 0);
+            sml = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bm, sml, 0, 0, 0);
+            sml = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bm, sml, 0, 0, 0);
+            sml = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, sml, 0, 0, 0);
+        }
+        __syncthreads();                                                     // every wave has read X
+        const float vc = cst[2 * KP + col0 + l32];
+#pragma unroll
+        for (int i = 0; i < 16; ++i)
+            xs[(row0 + 8 * (i >> 2) + 4 * h + (i & 3)) * XLD + col0 + l32] = (acc[i] + vc) + (big[i] + sml[i]);
+        __syncthreads();
+        // ---- epilogue: the ReLU mask of X, statistics, the row's quarters stored as float4
+        if (in) {
+            float *dst = Gprev + (unsigned)(tile * TR + row) * KP;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int c = tcol<true>(k);
+                const float4 o = *reinterpret_cast<const float4 *>(xs + row * XLD + c);
+                const float4 vsc = *reinterpret_cast<const float4 *>(cst + c), vsh = *reinterpret_cast<const float4 *>(cst + KP + c);
+                const float4 y = cur.y[k];
+                float4 d;
+                d.x = fmaf(y.x, vsc.x, vsh.x) > 0.f ? o.x : 0.f;
+                d.y = fmaf(y.y, vsc.y, vsh.y) > 0.f ? o.y : 0.f;
+                d.z = fmaf(y.z, vsc.z, vsh.z) > 0.f ? o.z : 0.f;
+                d.w = fmaf(y.w, vsc.w, vsh.w) > 0.f ? o.w : 0.f;
+                *reinterpret_cast<float4 *>(dst + c) = d;
+                s1[k].x += d.x; s1[k].y += d.y; s1[k].z += d.z; s1[k].w += d.w;
+                s2[k].x = fmaf(d.x, y.x, s2[k].x); s2[k].y = fmaf(d.y, y.y, s2[k].y);
+                s2[k].z = fmaf(d.z, y.z, s2[k].z); s2[k].w = fmaf(d.w, y.w, s2[k].w);
+            }
+        }
+    };
+    TileRegs ra, rb;
+    request(ra, (int)blockIdx.x);
+    __syncthreads();
+    for (int tile = blockIdx.x; tile < ntiles; tile += 2 * (int)gridDim.x) {
+        do_tile(tile, ra, rb);
+        if (tile + (int)gridDim.x < ntiles) do_tile(tile + (int)gridDim.x, rb, ra);
+    }
+    // ---- the workgroup's statistics row: the 64 row slots of a column added in index order
+    __syncthreads();
+    float *red = lds;                                // [TR][2][KP], over the fragments of W^T
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        *reinterpret_cast<float4 *>(red + (row * 2 + 0) * KP + tcol<true>(k)) = s1[k];
+        *reinterpret_cast<float4 *>(red + (row * 2 + 1) * KP + tcol<true>(k)) = s2[k];
+    }
+    __syncthreads();
+    if (tid < 2 * KP) {
+        float s = 0.f;
+        for (int i = 0; i < TR; ++i) s += red[i * 2 * KP + tid];
+        stats[(long long)blockIdx.x * 2 * KP + tid] = s;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ weight gradient
 // 256 threads.  Dense half: wave w multiplies rows 16 w .. 16 w + 15 of the tile into the three upper 32 x 32 blocks of
 // X^T X (48 accumulators, carried over every tile of the workgroup).  Sparse half: thread = (channel, k part); a group's
@@ -426,6 +658,16 @@ int pcops_mlp_dgrad_top_groups(int M, int Kp, int N, int S, const float *Yprev, 
     // one workgroup per statistics row: pcops_mlp_stats_rows(M) never exceeds the 64-row tiles nor kMaxGrid
     const int grid = pcops_mlp_stats_rows(M);
     if (grid < 1 || grid > kMaxGrid || grid > (M + TR - 1) / TR) return PCOPS_ERR_UNSUPPORTED;
+    // PCOPS_POOL_TOP_GROUPS_MM = 1 (default): N = 128 takes the addend as a product on the 16-bit matrix pipe; 0: the walk
+    static const bool mm_on = [] { const char *e = getenv("PCOPS_POOL_TOP_GROUPS_MM"); return !(e && e[0] == '0'); }();   // kernel A/B only
+    if (mm_on && N == NM) {
+        const size_t lds = (size_t)(3 * NKS * 2 * 64 * 4 + TR * XLD + 3 * KP + 3 * NMAX) * sizeof(float) + 3 * 2 * NM * 2 + 2 * NM +
+                           4 * 2 * 64 * 16;
+        pcops_note_pipe(1);
+        return pcops_launch_lds(dgrad_top_groups_mm_kernel, dim3(grid), dim3(256), lds, 160 * 1024, as_stream(stream), M, S, Yprev,
+                                prev_scale, prev_shift, Mq, vconst, gout, ysel, argmax, pool_scale, pool_shift, p, Wt, Gprev,
+                                stats_partial);
+    }
     const size_t lds = (size_t)(N * WLD + 2 * TR * XLD + 3 * KP + 5 * NMAX + TR * MW) * sizeof(float);
     pcops_note_pipe(0);
     return pcops_launch_lds(dgrad_top_groups_kernel, dim3(grid), dim3(256), lds, 160 * 1024, as_stream(stream), (long long)M, N,
