@@ -137,6 +137,7 @@ int pcops_last_launch_pipe(void);
  *              16 pcops_sa_gather_fwd(_rows) on the generic kernel (sa_gather_fwd_kernel):  [1] groups per workgroup (1 or 8);
  *                 [2] rows of stats_partial written (0 without statistics);  [3] 1 for the statistics-from-moments route
  *                 (sa_gather_offsets_kernel + xyz_stats_from_moments_kernel);  [4] 4 compacted rows
+ *              17 pcops_mlp_bwd_fused_xyz_rows on the all-wave tile kernel (csrc/xyz_bwd_tiles.hip): [1] = 2, [2] = 64
  *   [1] split  1 when the operands are split into bf16 pieces (the one-pass backward: 1 its dX half, 2 both halves)
  *   [2] bn     output columns per block (64, 96, 128; the weight gradients: columns of their dW tile; 0 tiled)
  *   [3] wst    1 when the weights are streamed rather than resident in LDS
@@ -560,7 +561,10 @@ int pcops_mlp_wgrad_top_groups(int M, int Kp, int N, int S, const float *Yprev, 
 int pcops_mlp_xyz_supported(int M, int C1, int N2);
 /* pcops_mlp_bwd_fused over the xyz form (round 3): pcops_mlp_wgrad_xyz + pcops_mlp_gemm_dgrad_xyz (Gprev == NULL form) in
  * one pass -- dW, db of the layer, stats_partial [groups][2][K] and xyz_stats [groups][3][K] of the arithmetic layer
- * below; groups = pcops_mlp_bwd_fused_groups(M, K, N, S, pooled), 0 = not taken.  W [K][N] as the forward holds it. */
+ * below; groups = pcops_mlp_bwd_fused_groups(M, K, N, S, pooled), 0 = not taken.  W [K][N] as the forward holds it.
+ * K == N == 64 with rows == NULL and gpool == NULL (M * 256 bytes below 2^31) takes the all-wave tile kernel of
+ * csrc/xyz_bwd_tiles.hip, both products on split bf16 operands (pcops_last_launch_pipe() 1, plan path 17); same buffers,
+ * same sizes.  PCOPS_BWD_XYZ_TILES=0 in the environment, read once by the library, gives bwd_fused_kernel back for every shape. */
 int pcops_mlp_bwd_fused_xyz_rows(long long M, int K, int N, const float *off4, const float *xyzw, const float *a_scale,
                                  const float *a_shift, const float *G, const float *Y, const float *p, const float *q,
                                  const float *t, const float *gpool, const unsigned char *argmax, int S, const float *W,

@@ -56,6 +56,14 @@ void pcops_note_pipe(int pipe);                   // abi.hip: what pcops_last_la
 void pcops_note_plan(int path, int split, int bn, int wst, int pool);
 void pcops_note_plan_field(int field, int value);   // one field of the plan just noted (a sub-launcher's own decision)
 
+// xyz_bwd_tiles.hip: the form of pcops_mlp_bwd_fused_xyz_rows its kernel takes (uncompacted rows and a dense G are the caller's
+// to check), and the launch -- buffers as bwd_fused_kernel's for `groups` workgroups, dW and db final
+bool pcops_xyz_bwd_tiles_form(long long M, int K, int N);
+int pcops_xyz_bwd_tiles_launch(long long M, int groups, const float *off4, const float *xyzw, const float *a_scale,
+                               const float *a_shift, const float *G, const float *Y, const float *p, const float *q,
+                               const float *t, const float *W, float *partial, float *dW, float *db, float *stats_partial,
+                               float *xyz_stats, hipStream_t st);
+
 constexpr int kWave = 64;  // CDNA wavefront
 
 // Asymmetric STATIC wave priority (round 4; MI355X_MICROARCH.md "Two waves per SIMD").  Two co-resident waves that run

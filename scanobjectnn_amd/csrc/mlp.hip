@@ -6590,6 +6590,10 @@ int pcops_mlp_bwd_fused_xyz_rows(long long M, int K, int N, const float *off4, c
         return rc;
     a.amode = A_XYZ; a.ldx = 4; a.off4 = off4; a.xw = xyzw; a.xw_ld = K; a.xstats = xyz_stats;
     if (const int rc = set_rows(a, rows)) return rc;
+    // 64 -> 64, every row, dense G: the all-wave tile kernel of xyz_bwd_tiles.hip (PCOPS_BWD_XYZ_TILES=0: the kernel below)
+    if (!rows && !gpool && pcops_xyz_bwd_tiles_form(M, K, N))
+        return pcops_xyz_bwd_tiles_launch(M, groups, off4, xyzw, a_scale, a_shift, G, Y, p, q, t, W, partial, dW, db,
+                                          stats_partial, xyz_stats, as_stream(stream));
     return bwd_fused_launch(a, true, groups, partial, dW, db, as_stream(stream));
 }
 
