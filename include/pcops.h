@@ -145,6 +145,10 @@ int pcops_last_launch_pipe(void);
  *              with S % 32 != 0), 4 compacted rows; the Gram form of the one-pass backward adds 8
  * A diagnostic like the one above: no product path reads it. */
 int pcops_last_launch_plan(int *out, int n);
+/* ... and 1 when it was the pooled forward that stores no Y and sums its statistics on the accumulator registers (pcops_mlp_gemm_fwd_pool
+ * / _rows with Y == NULL on the split-operand, resident-weights 128-column tile), else 0.  Same plan tuple, same
+ * bits as the transposing kernel, which PCOPS_POOL_FWD_ACC_STATS=0 in the environment (read once) keeps.  A diagnostic as well. */
+int pcops_last_launch_acc_stats(void);
 
 /* ------------------------------------------------------------------ sampling */
 /* farthestpointsamplingLauncher(b,n,m,inp,temp,out)   sampling/tf_sampling.cpp:94,

@@ -90,13 +90,19 @@ extern "C" int pcops_get_deterministic(void) { return g_deterministic.load(); }
 // (or no product), 1 the bf16 pipe with split operands, 2 half and half (one-pass backward: dW fp32, dX split; 1 where dW is split too).  The
 // launchers note it where they decide, so a roofline label is the library's own decision, not a mirror of its rules.
 static thread_local int t_last_pipe = 0;
-void pcops_note_pipe(int pipe) { t_last_pipe = pipe; }
+// ... and whether it was the pooled forward that takes its statistics from the accumulator registers (gemm_ws_kernel VAR 5 | 16):
+// every product launcher notes its pipe where it decides, which clears the flag; the one launcher of that variant sets it after
+static thread_local int t_last_acc_stats = 0;
+void pcops_note_pipe(int pipe) { t_last_pipe = pipe; t_last_acc_stats = 0; }
+void pcops_note_acc_stats(int on) { t_last_acc_stats = on; }
 extern "C" int pcops_last_launch_pipe(void) { return t_last_pipe; }
+extern "C" int pcops_last_launch_acc_stats(void) { return t_last_acc_stats; }
 
 // ... and which variant it was (pcops.h pcops_last_launch_plan): noted by the launchers where they decide, like the pipe
 static thread_local int t_last_plan[5] = {0, 0, 0, 0, 0};
 void pcops_note_plan(int path, int split, int bn, int wst, int pool) {
     t_last_plan[0] = path; t_last_plan[1] = split; t_last_plan[2] = bn; t_last_plan[3] = wst; t_last_plan[4] = pool;
+    t_last_acc_stats = 0;       // (launchers that note a plan but no pipe)
 }
 void pcops_note_plan_field(int field, int value) {
     if (field >= 0 && field < 5) t_last_plan[field] = value;

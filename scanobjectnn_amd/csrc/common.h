@@ -52,6 +52,7 @@ static inline int pcops_dispatch(int v, int otherwise, F &&f) {
 extern "C" int pcops_get_deterministic(void);     // abi.hip: bit-reproducible backward passes requested
 extern "C" int pcops_get_option(int option);      // abi.hip: the arithmetic options of pcops.h (read at every call)
 void pcops_note_pipe(int pipe);                   // abi.hip: what pcops_last_launch_pipe() reports (0 fp32, 1 split bf16, 2 both)
+void pcops_note_acc_stats(int on);                // abi.hip: what pcops_last_launch_acc_stats() reports (pcops_note_pipe clears it)
 // abi.hip: what pcops_last_launch_plan() reports -- the variant the last product launch took (codes in pcops.h)
 void pcops_note_plan(int path, int split, int bn, int wst, int pool);
 void pcops_note_plan_field(int field, int value);   // one field of the plan just noted (a sub-launcher's own decision)

@@ -526,6 +526,11 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void gemm_ws_kernel(GemmArgs
     constexpr bool BF3 = (VAR & 4) != 0;
     constexpr bool S4 = (VAR & 8) != 0;       // pooled forward over groups that are not whole tiles (GemmArgs::pool_s4)
     constexpr bool POOL = (VAR & 3) == 1 || (VAR & 3) == 3, WST = (VAR & 3) == 2 || (VAR & 3) == 3;   // 3: pooled AND streamed
+    // +16: the pooled forward that stores no Y: the statistics are summed on the accumulator registers, in
+    //      the order the transposed epilogue sums them (same bits), and the tile never goes through the stripe
+    constexpr bool ACCST = (VAR & 16) != 0;
+    static_assert(!ACCST || (POOL && BF3 && !WST && !S4 && EM == E_FWD && EH == NT && WAVES == 8),
+                  "statistics from the accumulators: the pooled, split-operand, resident-weights tile with 32-column passes");
     constexpr int BN = NT * 32;
     constexpr int NTH = NT / EH;                   // accumulator tiles per epilogue pass
     constexpr int BNH = BN / EH;                   // columns per epilogue pass
@@ -1086,6 +1091,54 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void gemm_ws_kernel(GemmArgs
             }
         }
     };
+    // ---- ACCST: the statistics on the accumulator registers, in the transposed epilogue's order.  There, in pass h, a lane owns
+    // one column quad of rows rho + 8 j (rho = lane / 8, j ascending, tile after tile); here row rho = 4 (lane >> 5) + i of column
+    // 32 nt + (lane & 31) is the registers acc[nt][i + 4 j] -- the same chain, so s1[nt][i] / s2[nt][i] (the register count of
+    // s1[EH][4] / s2[EH][4]) hold bit for bit what the transposed pass's lane (rho, column quad) holds.  Compacted rows: tile rows 0
+    // and 16 (lanes 0..31, i = 0, j = 0 / 2) carry their block's weight, the form the epilogue takes for every row of those steps
+    // (w = 1 elsewhere: w o == o exactly)
+    auto acc_stats = [&](const f32x16 (&acc)[NT], long long tile) {
+        if constexpr (ACCST) {
+        const long long row0 = tile * 32;
+        const int erem = (int)((long long)M - row0 < 32 ? (long long)M - row0 : 32);
+        const int hrow = 4 * (lane >> 5);
+        float ew[2] = {1.f, 1.f};
+        if (compact) {
+            const int nblk = (M + kBlk - 1) / kBlk;
+#pragma unroll
+            for (int hb = 0; hb < 2; ++hb) {
+                long long bi = tile * 2 + hb;
+                bi = bi < nblk ? bi : nblk - 1;
+                ew[hb] = lane < 32 ? uniform_block(a.blocks, bi).w : 1.f;
+            }
+        }
+        auto sweep = [&](auto full_) {
+            constexpr bool FULL = decltype(full_)::value;
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) {
+                const bool cin = FULL || (n0 + 32 * nt + (lane & 31) < N);
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const float o = acc[nt][i + 4 * j];          // s (y - pivot), as the transposed pass reads it back
+                        if (FULL || (i + 8 * j + hrow < erem && cin)) {
+                            if (compact && i == 0 && j % 2 == 0) {
+                                const float wo = ew[j / 2] * o;
+                                s1[nt][i] += wo;
+                                s2[nt][i] = fmaf(wo, o, s2[nt][i]);
+                            } else {
+                                s1[nt][i] += o;
+                                s2[nt][i] = fmaf(o, o, s2[nt][i]);
+                            }
+                        }
+                    }
+            }
+        };
+        if (erem == 32 && n0 + BN <= N) sweep(std::true_type{});
+        else sweep(std::false_type{});
+        }
+    };
 #ifdef PCOPS_PHASE_PROF
     unsigned long long pf_stage = 0, pf_mfma = 0, pf_epi = 0, pf_tiles = 0, pf_t;
     const unsigned long long pf_start = PROF_T();
@@ -1256,6 +1309,9 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void gemm_ws_kernel(GemmArgs
             for (int i = 0; i < NT; ++i) acc[i] += sm[i];
         }
         if (POOL) pool_acc(acc, tile, sub, st);
+        if constexpr (ACCST) {
+            acc_stats(acc, tile);       // no Y: nothing is transposed, nothing stored
+        } else {
         // ---- epilogue: accumulators -> stripe (transposed, EH column passes) -> 16-byte row-segment stores
         const long long row0 = tile * 32;
         const int erem = (int)((long long)M - row0 < 32 ? (long long)M - row0 : 32);   // rows of this tile (scalar, 32 bit)
@@ -1414,6 +1470,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void gemm_ws_kernel(GemmArgs
         if (EM != E_MASKX && erem == 32 && n0 + BN <= N) epilogue(std::true_type{});
         else epilogue(std::false_type{});
         }
+        }
 #ifdef PCOPS_PHASE_PROF
         if (active) { const unsigned long long n_ = PROF_T(); pf_epi += n_ - pf_t; ++pf_tiles; }
 #endif
@@ -1433,6 +1490,24 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void gemm_ws_kernel(GemmArgs
 #endif
 
     if (EM != E_PLAIN && EM != E_PLAINA && a.stats) {
+        if constexpr (ACCST) {
+            // the transposed kernel's tree over the eight row classes rho: shfl_xor 32, 16, 8 there is rho ^ 4, 2, 1, i.e.
+            // ((s0 + s4) + (s2 + s6)) + ((s1 + s5) + (s3 + s7)); here rho = 4 (lane >> 5) + i
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) {
+                float t1[4], t2[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    t1[i] = s1[nt][i] + __shfl_xor(s1[nt][i], 32, 64);
+                    t2[i] = s2[nt][i] + __shfl_xor(s2[nt][i], 32, 64);
+                }
+                const float r1 = (t1[0] + t1[2]) + (t1[1] + t1[3]), r2 = (t2[0] + t2[2]) + (t2[1] + t2[3]);
+                if (lane < 32) {
+                    red[(wave * 2 + 0) * BN + 32 * nt + lane] = r1 * ecoef[BN + 32 * nt + lane];   // the column's sign back
+                    red[(wave * 2 + 1) * BN + 32 * nt + lane] = r2;
+                }
+            }
+        } else {
         // lanes l, l + O4, l + 2 O4 ... own the same 4 columns
 #pragma unroll
         for (int h = 0; h < EH; ++h) {
@@ -1452,6 +1527,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void gemm_ws_kernel(GemmArgs
                     red[(wave * 2 + 1) * BN + h * BNH + ocl + e] = s2[h][e];
                 }
             }
+        }
         }
         __syncthreads();
         for (int i = tid; i < 2 * BN; i += NTHR) {
@@ -1686,6 +1762,12 @@ constexpr int ws_var(int wp, int base) {
     return base | ((wp & 1) && EM == E_FWD ? 1 : 0) | (wp & 2);
 }
 
+// PCOPS_POOL_FWD_ACC_STATS=0 (read once): the pooled forward without Y keeps the transposing kernel (kernel A/B; same bits)
+static bool pool_fwd_acc_stats_enabled() {
+    static const bool on = [] { const char *e = getenv("PCOPS_POOL_FWD_ACC_STATS"); return !(e && e[0] == '0'); }();
+    return on;
+}
+
 // one column tile (NT blocks of 32 columns, EH epilogue passes) of the family BASE names
 template <int AM, int EM, int NT, int EH, int BASE>
 static int launch_gemm_ws_tile(GemmArgs &a, const WsPlan &pl, hipStream_t st) {
@@ -1693,6 +1775,15 @@ static int launch_gemm_ws_tile(GemmArgs &a, const WsPlan &pl, hipStream_t st) {
     const int P = (a.stats && EM != E_PLAIN && EM != E_PLAINA) ? pcops_mlp_stats_rows(a.M) : 0;
     const dim3 grid(pl.gy > P ? pl.gy : P, pl.ncb);
     const int wp = (EM == E_FWD && a.pool_sub > 0 ? 1 : 0) | (pl.wst ? 2 : 0);
+    // the pooled, split-operand, resident-weights 128-column tile of a call that stores no Y: VAR 5 | 16, the statistics from
+    // the accumulator registers (same grid, same LDS, same plan tuple; pcops_last_launch_acc_stats() tells the two apart)
+    if constexpr (AM == A_BNRELU && EM == E_FWD && NT == 4 && EH == 4 && BASE == 4) {
+        if (wp == 1 && a.Y == nullptr && pool_fwd_acc_stats_enabled()) {
+            pcops_note_acc_stats(1);
+            return pcops_launch_lds(gemm_ws_kernel<4, A_BNRELU, E_FWD, 32, 8, 4, (5 | 16)>, grid, dim3(512), pl.lds,
+                                    160 * 1024, st, a);
+        }
+    }
     return pcops_dispatch<0, 1, 2, 3>(wp, PCOPS_ERR_UNSUPPORTED, [&](auto wp_) {
         constexpr int VAR = ws_var<AM, EM>(decltype(wp_)::value, BASE);
         return pcops_launch_lds(gemm_ws_kernel<NT, AM, EM, (BASE ? 32 : 64), 8, EH, VAR>, grid, dim3(512), pl.lds,
