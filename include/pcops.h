@@ -772,6 +772,12 @@ int pcops_xyz_first_layer_grads(int P1, const float *xyz_stats, int P2, const fl
  * bias-corrected root; reference trainers pointnet2/train.py:165-168). */
 int pcops_adam_step(long long n, float *p, const float *g, float *m, float *v, float beta1, float beta2, float lr_t,
                     float epsilon, pcops_stream_t stream);
+/* The same update, element for element and bit for bit, with lr_t read from DEVICE memory (one float, 4-byte aligned,
+ * the same value for every element): the launch then has no argument that changes from step to step, so a training
+ * step captured as a HIP graph replays it unchanged while the caller refreshes *lr_t on the same stream ahead of the
+ * replay.  Argument checks as pcops_adam_step, and lr_t must not be NULL. */
+int pcops_adam_step_dev(long long n, float *p, const float *g, float *m, float *v, float beta1, float beta2,
+                        const float *lr_t, float epsilon, pcops_stream_t stream);
 /* 1 when every launch of a grouped stack over compacted rows has a kernel for its shape (the *_rows entry points have
  * no tiled fallback): b clouds x m groups x s slots, n source points per cloud, has_q = the first layer has a feature
  * term (its gradient then walks the rows through the inverse index), widths [nlayers] = the layers' output widths

@@ -135,6 +135,27 @@ __global__ __launch_bounds__(256) void adam_step_kernel(long long n4, float4 *__
         m[i] = mi; v[i] = vi; p[i] = pi;
     }
 }
+// The same update with lr_t read from device memory: the one value of a training step that changes on every step and
+// would otherwise enter the launch by value, so a captured step (host: captured_step.py) replays this launch unchanged
+// and the host refreshes *lr_t with a one-element fill ahead of the replay.  Every lane reads the same address (a
+// uniform load, once per thread, ahead of the loop); the arithmetic is adam_step_kernel's, statement for statement.
+__global__ __launch_bounds__(256) void adam_step_dev_kernel(long long n4, float4 *__restrict__ p, const float4 *__restrict__ g,
+                                                            float4 *__restrict__ m, float4 *__restrict__ v, float b1, float b2,
+                                                            const float *__restrict__ lr_t_dev, float eps) {
+    const float c1 = 1.f - b1, c2 = 1.f - b2;
+    const float lr_t = *lr_t_dev;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
+        const float4 gi = g[i];
+        float4 mi = m[i], vi = v[i], pi = p[i];
+        mi.x = fmaf(c1, gi.x, b1 * mi.x); mi.y = fmaf(c1, gi.y, b1 * mi.y);
+        mi.z = fmaf(c1, gi.z, b1 * mi.z); mi.w = fmaf(c1, gi.w, b1 * mi.w);
+        vi.x = fmaf(c2 * gi.x, gi.x, b2 * vi.x); vi.y = fmaf(c2 * gi.y, gi.y, b2 * vi.y);
+        vi.z = fmaf(c2 * gi.z, gi.z, b2 * vi.z); vi.w = fmaf(c2 * gi.w, gi.w, b2 * vi.w);
+        pi.x -= lr_t * mi.x / (sqrtf(vi.x) + eps); pi.y -= lr_t * mi.y / (sqrtf(vi.y) + eps);
+        pi.z -= lr_t * mi.z / (sqrtf(vi.z) + eps); pi.w -= lr_t * mi.w / (sqrtf(vi.w) + eps);
+        m[i] = mi; v[i] = vi; p[i] = pi;
+    }
+}
 }  // namespace
 
 extern "C" int pcops_adam_step(long long n, float *p, const float *g, float *m, float *v, float beta1, float beta2,
@@ -149,6 +170,24 @@ extern "C" int pcops_adam_step(long long n, float *p, const float *g, float *m, 
     unsigned grid = cdiv(n4, 256);
     if (grid > 4096) grid = 4096;
     hipLaunchKernelGGL(adam_step_kernel, dim3(grid), dim3(256), 0, as_stream(stream), n4, reinterpret_cast<float4 *>(p),
+                       reinterpret_cast<const float4 *>(g), reinterpret_cast<float4 *>(m), reinterpret_cast<float4 *>(v),
+                       beta1, beta2, lr_t, epsilon);
+    return pcops_launch_status();
+}
+
+extern "C" int pcops_adam_step_dev(long long n, float *p, const float *g, float *m, float *v, float beta1, float beta2,
+                                   const float *lr_t, float epsilon, pcops_stream_t stream) {
+    PCOPS_REQUIRE_SHAPE(n >= 0 && n % 4 == 0);
+    if (n == 0) return PCOPS_OK;
+    PCOPS_REQUIRE_PTR(p); PCOPS_REQUIRE_PTR(g); PCOPS_REQUIRE_PTR(m); PCOPS_REQUIRE_PTR(v); PCOPS_REQUIRE_PTR(lr_t);
+    if ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
+         reinterpret_cast<uintptr_t>(v)) & 15)
+        return PCOPS_ERR_UNSUPPORTED;
+    if (reinterpret_cast<uintptr_t>(lr_t) & 3) return PCOPS_ERR_UNSUPPORTED;
+    const long long n4 = n / 4;
+    unsigned grid = cdiv(n4, 256);
+    if (grid > 4096) grid = 4096;
+    hipLaunchKernelGGL(adam_step_dev_kernel, dim3(grid), dim3(256), 0, as_stream(stream), n4, reinterpret_cast<float4 *>(p),
                        reinterpret_cast<const float4 *>(g), reinterpret_cast<float4 *>(m), reinterpret_cast<float4 *>(v),
                        beta1, beta2, lr_t, epsilon);
     return pcops_launch_status();

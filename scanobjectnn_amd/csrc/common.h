@@ -28,6 +28,26 @@ static inline hipStream_t as_stream(pcops_stream_t s) { return reinterpret_cast<
 
 static inline unsigned cdiv(long long a, long long b) { return (unsigned)((a + b - 1) / b); }
 
+// Zero `bytes` bytes at p on the stream: what the launchers that accumulate with atomics do to their output first.
+// hipMemsetAsync, as ever -- unless the stream is being captured into a HIP graph (captured_step.py).  A captured
+// hipMemsetAsync becomes a memset node, and on ROCm 7.0 such a node clears the whole range on the graph's first launch
+// and only HALF of it on every later one (measured on the MI355X: 128 of 256 and 98 304 of 196 608 floats left as they
+// were on the second and third replay; tests/test_captured_step_gpu.py replays one), so under capture the range is
+// cleared by a kernel node instead.  Ranges that are not whole, aligned 32-bit words keep the memset.
+static __global__ __launch_bounds__(256) void pcops_zero_kernel(unsigned *__restrict__ p, size_t n) {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) p[i] = 0u;
+}
+static inline hipError_t pcops_zero_async(void *p, size_t bytes, hipStream_t st) {
+    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+    if (st == nullptr || bytes == 0 || (bytes & 3) || (reinterpret_cast<uintptr_t>(p) & 3) ||
+        hipStreamIsCapturing(st, &capturing) != hipSuccess || capturing != hipStreamCaptureStatusActive)
+        return hipMemsetAsync(p, 0, bytes, st);
+    const size_t n = bytes / 4;
+    const unsigned grid = n < (size_t)4096 * 256 ? cdiv((long long)n, 256) : 4096u;
+    hipLaunchKernelGGL(pcops_zero_kernel, dim3(grid), dim3(256), 0, st, static_cast<unsigned *>(p), n);
+    return hipGetLastError();
+}
+
 // A kernel whose dynamic LDS may pass the 64 KB default: raise its ceiling to max_lds, launch it, and return the launch's
 // status.  The attribute is set at every call; a refused attribute is PCOPS_ERR_LAUNCH.
 template <typename... Params, typename... Args>

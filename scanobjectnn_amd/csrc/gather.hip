@@ -2188,7 +2188,7 @@ int pcops_sa_scatter_bwd_rows(int b, int n, int m, int s, int c, const float *G,
     hipStream_t st = as_stream(stream);
     const size_t dq_bytes = sizeof(float) * (size_t)b * n * c;
     if (Gn == 0) {
-        if (dQ && hipMemsetAsync(dQ, 0, dq_bytes, st) != hipSuccess) return PCOPS_ERR_LAUNCH;
+        if (dQ && pcops_zero_async(dQ, dq_bytes, st) != hipSuccess) return PCOPS_ERR_LAUNCH;
         return PCOPS_OK;
     }
     if (!rc_fwd) PCOPS_REQUIRE_PTR(Y);
@@ -2212,7 +2212,7 @@ int pcops_sa_scatter_bwd_rows(int b, int n, int m, int s, int c, const float *G,
             return scatter_qctr(b, n, m, s, c, G, p, q, t, idx, fwd_Q, c, fwd_Ctr, c, dQ, c, dCtr, c, workspace, false, st);
         case 8:
         case 9: {
-            if (pl.path == 8 && hipMemsetAsync(dQ, 0, dq_bytes, st) != hipSuccess) return PCOPS_ERR_LAUNCH;
+            if (pl.path == 8 && pcops_zero_async(dQ, dq_bytes, st) != hipSuccess) return PCOPS_ERR_LAUNCH;
             if (pl.split) {
                 const ScatterArgs sa = {b, n, m, s, c, c / pl.cs, pl.gsplit, G, Y, p, q, t, gpool, argmax, pool_scale,
                                         pool_shift, idx, xyz, new_xyz, nullptr, dCtr, wp, gpool ? dQ : nullptr, fwd_Q,
@@ -2249,7 +2249,7 @@ int pcops_sa_scatter_bwd_rows(int b, int n, int m, int s, int c, const float *G,
             return rc ? rc : reduce_wpartial(wp, b * pl.gsplit, c, dWxyz, dbias, st);
         }
         case 15: {      // global atomics
-            if (dQ && hipMemsetAsync(dQ, 0, dq_bytes, st) != hipSuccess) return PCOPS_ERR_LAUNCH;
+            if (dQ && pcops_zero_async(dQ, dq_bytes, st) != hipSuccess) return PCOPS_ERR_LAUNCH;
             const int rl = c >= 256 ? 1 : 256 / c;
             const size_t lds = (size_t)rl * 6 * c * sizeof(float);
             const int gpb = 16;
@@ -2357,7 +2357,7 @@ int pcops_edge_pool_bwd(int b, int n, int m, int s, int c, const float *Q, const
     const long long G = (long long)b * m;
     const EdgeBwdPlan pl = edge_pool_bwd_plan(b, n, m, s, c);
     if (pl.status) return pl.status;
-    if (pl.mode == 0 && hipMemsetAsync(dQ, 0, sizeof(float) * (size_t)b * n * c, st) != hipSuccess) return PCOPS_ERR_LAUNCH;
+    if (pl.mode == 0 && pcops_zero_async(dQ, sizeof(float) * (size_t)b * n * c, st) != hipSuccess) return PCOPS_ERR_LAUNCH;
     if (G == 0) return PCOPS_OK;
     PCOPS_REQUIRE_PTR(Q); PCOPS_REQUIRE_PTR(Ctr); PCOPS_REQUIRE_PTR(idx); PCOPS_REQUIRE_PTR(gpool); PCOPS_REQUIRE_PTR(ysel);
     PCOPS_REQUIRE_PTR(SQ); PCOPS_REQUIRE_PTR(arg); PCOPS_REQUIRE_PTR(scale); PCOPS_REQUIRE_PTR(shift); PCOPS_REQUIRE_PTR(p);

@@ -487,7 +487,7 @@ extern "C" int pcops_group_point_grad(int b, int n, int c, int m, int nsample, c
     PCOPS_REQUIRE_PTR(grad_points);
     if (pcops_get_deterministic()) return PCOPS_ERR_UNSUPPORTED;   // float atomics: pcops_scatter_rows_sorted instead
     hipStream_t st = as_stream(stream);
-    if (hipMemsetAsync(grad_points, 0, sizeof(float) * (size_t)b * n * c, st) != hipSuccess)
+    if (pcops_zero_async(grad_points, sizeof(float) * (size_t)b * n * c, st) != hipSuccess)
         return PCOPS_ERR_LAUNCH;
     const long long total = (long long)b * m * nsample * c;
     if (total == 0) return PCOPS_OK;

@@ -1071,7 +1071,7 @@ extern "C" int pcops_edge_feature_grad(int b, int n, int c, int k, const float *
     PCOPS_REQUIRE_PTR(grad_x);
     if (pcops_get_deterministic()) return PCOPS_ERR_UNSUPPORTED;   // atomics: use _central + pcops_scatter_rows_sorted
     hipStream_t st = as_stream(stream);
-    if (hipMemsetAsync(grad_x, 0, sizeof(float) * (size_t)total, st) != hipSuccess)
+    if (pcops_zero_async(grad_x, sizeof(float) * (size_t)total, st) != hipSuccess)
         return PCOPS_ERR_LAUNCH;
     if (k == 0) return PCOPS_OK;
     PCOPS_REQUIRE_PTR(grad_out);

@@ -468,8 +468,8 @@ extern "C" int pcops_conv3d_wgrad(int b, int r, int k, int cin, int cout, const 
     hipStream_t s = as_stream(stream);
     const size_t len = (size_t)k * k * k * cin * cout;
     if (b == 0) {
-        (void)hipMemsetAsync(dw, 0, len * sizeof(float), s);
-        if (dbias) (void)hipMemsetAsync(dbias, 0, (size_t)cout * sizeof(float), s);
+        (void)pcops_zero_async(dw, len * sizeof(float), s);
+        if (dbias) (void)pcops_zero_async(dbias, (size_t)cout * sizeof(float), s);
         return pcops_launch_status();
     }
     PCOPS_REQUIRE_PTR(x); PCOPS_REQUIRE_PTR(dy);

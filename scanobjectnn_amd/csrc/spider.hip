@@ -515,8 +515,8 @@ extern "C" int pcops_spider_taylor_bwd(long long rows, int t, const float *delta
     PCOPS_REQUIRE_PTR(dtheta); PCOPS_REQUIRE_PTR(dtbias);
     hipStream_t s = as_stream(stream);
     if (rows == 0) {
-        (void)hipMemsetAsync(dtheta, 0, kMono * kT * sizeof(float), s);
-        (void)hipMemsetAsync(dtbias, 0, kT * sizeof(float), s);
+        (void)pcops_zero_async(dtheta, kMono * kT * sizeof(float), s);
+        (void)pcops_zero_async(dtbias, kT * sizeof(float), s);
         return pcops_launch_status();
     }
     PCOPS_REQUIRE_PTR(delta); PCOPS_REQUIRE_PTR(dg); PCOPS_REQUIRE_PTR(workspace);
@@ -556,8 +556,8 @@ extern "C" int pcops_spider_conv_wgrad(int b, int n, int c, int k, int t, int o,
     hipStream_t s = as_stream(stream);
     const size_t K = (size_t)k * c * kT;
     if (b == 0) {
-        (void)hipMemsetAsync(dw, 0, K * o * sizeof(float), s);
-        if (dbias) (void)hipMemsetAsync(dbias, 0, (size_t)o * sizeof(float), s);
+        (void)pcops_zero_async(dw, K * o * sizeof(float), s);
+        if (dbias) (void)pcops_zero_async(dbias, (size_t)o * sizeof(float), s);
         return pcops_launch_status();
     }
     PCOPS_REQUIRE_PTR(feat); PCOPS_REQUIRE_PTR(idx); PCOPS_REQUIRE_PTR(g); PCOPS_REQUIRE_PTR(dy);
@@ -631,8 +631,8 @@ extern "C" int pcops_group_norm_relu_bwd(int b, int n, int c, int groups, const 
     PCOPS_REQUIRE_PTR(dgamma); PCOPS_REQUIRE_PTR(dbeta);
     hipStream_t s = as_stream(stream);
     if (b == 0) {
-        (void)hipMemsetAsync(dgamma, 0, (size_t)c * sizeof(float), s);
-        (void)hipMemsetAsync(dbeta, 0, (size_t)c * sizeof(float), s);
+        (void)pcops_zero_async(dgamma, (size_t)c * sizeof(float), s);
+        (void)pcops_zero_async(dbeta, (size_t)c * sizeof(float), s);
         return pcops_launch_status();
     }
     PCOPS_REQUIRE_PTR(dout); PCOPS_REQUIRE_PTR(x); PCOPS_REQUIRE_PTR(y); PCOPS_REQUIRE_PTR(gamma);

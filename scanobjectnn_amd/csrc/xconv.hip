@@ -428,7 +428,7 @@ extern "C" int pcops_xconv_wgrad(int b, int n, int p, int k, int c1, int c2, int
     const Shape s = make_shape(n, p, k, c1, c2, dm);
     const int len = k * s.cd;
     if (b == 0) {
-        (void)hipMemsetAsync(dwd, 0, (size_t)len * sizeof(float), hs);
+        (void)pcops_zero_async(dwd, (size_t)len * sizeof(float), hs);
         return pcops_launch_status();
     }
     PCOPS_REQUIRE_PTR(lifted); PCOPS_REQUIRE_PTR(X); PCOPS_REQUIRE_PTR(dout);

@@ -16,7 +16,9 @@ cloud order (`data_utils.get_current_data_h5`) is an index gather on the residen
 (`provider.py:34-52,189-200`) run per batch on the device.
 Per step: forward (training BN, dropout) -> loss -> backward -> ONE all-reduce of the flat gradient bucket ->
 Adam / momentum with the staircase lr; bn_decay follows the reference schedule.  Loss and accuracy are accumulated
-on the device and read ONCE per epoch (no per-step host synchronisation).  A checkpoint (`model.pt`, variables under
+on the device and read ONCE per epoch (no per-step host synchronisation).  `--graph` (single rank, the families listed in
+`captured_step.py`): that step is captured once as a HIP graph and replayed, with the input pipeline above staying outside
+the graph; evaluation, checkpoints and everything else are the same either way.  A checkpoint (`model.pt`, variables under
 the reference's TF scope names) is written every epoch after the BN moving statistics were made rank 0's.
 """
 import argparse
@@ -28,7 +30,7 @@ import time
 import numpy as np
 import torch
 
-from .. import data_utils, dist as D, provider
+from .. import captured_step as CS, data_utils, dist as D, provider
 from .. import train_util as TU
 from ..graph import Model
 from ..synth import synth_clouds, synth_labels, synth_masks
@@ -139,6 +141,9 @@ def parse_args(argv=None):
     p.add_argument("--no_augment", action="store_true", help="skip rotate + jitter (tests / debugging)")
     p.add_argument("--deterministic", action="store_true",
                    help="bit-reproducible backward passes: ordered owner sums instead of float atomics (slower)")
+    p.add_argument("--graph", action="store_true",
+                   help="capture one training step as a HIP graph and replay it every step (captured_step.py); a run that "
+                   "cannot be captured says why in one line and trains eagerly")
     add_model_flags(p)
     args = resolve_model_flags(p.parse_args(argv))
     mod = importlib.import_module(MODELS[args.model])
@@ -211,7 +216,9 @@ def epoch_view(data, labels, mask, num_point, rng, dev):
     return cur, labels.index_select(0, ic), msk
 
 
-def train(args):
+def train(args, state=None):
+    """-> the epoch records; `state`: a dict that receives the run's model, flat parameters, optimiser and last epoch's
+    running sums"""
     rank, world, local = D.init_from_env()
     if world == 1:
         if not 0 <= args.gpu < torch.cuda.device_count():
@@ -249,11 +256,52 @@ def train(args):
         os.makedirs(args.log_dir, exist_ok=True)
     log = []
     lo, hi = D.shard_range(args.batch_size, rank, world)
+
+    def step_body(x, y, m, bn_decay, tot, update):
+        """forward, loss, backward, gradient collection, the optimiser (`update`) and the epoch's running sums: one training
+        step, which is also what --graph captures"""
+        fp.begin_step()
+        out = net(x, is_training=True, bn_decay=bn_decay)
+        if partseg:
+            seg_pred, end_points = EV.split_output(out)     # pointnet_partseg: (seg_pred, end_points)
+            loss = mod.get_loss(seg_pred, m) if end_points is None else mod.get_loss(seg_pred, m, end_points)
+        elif with_mask:
+            if args.model in MASK_MODELS_END_POINTS:
+                loss = mod.get_loss(out[0], out[1], y, m, out[2], seg_weight=args.seg_weight)[0]
+            else:
+                loss = mod.get_loss(out[0], out[1], y, m, seg_weight=args.seg_weight)[0]
+        else:
+            logits, end_points = EV.split_output(out)      # SpiderCNN returns bare logits
+            loss = EV.model_loss(mod, logits, y, end_points)
+        if own:                                                   # minimised, not reported (PointCNN/train.py:171)
+            (loss + own.regularization_loss(net)).backward()
+        else:
+            loss.backward()
+        fp.collect_mean(world)
+        update()
+        with torch.no_grad():
+            tot[0] += loss.detach()
+            if partseg:                      # point accuracy (`train_partseg.py:237-241`)
+                tot[1] += (seg_pred.argmax(dim=2) == m).sum()
+                tot[2] += per_rank * args.num_point
+            else:
+                tot[1] += (scores(EV.split_output(out)[0]).argmax(dim=1) == y).sum()
+                tot[2] += per_rank
+
+    captured = None                                  # --graph: the step as one captured HIP graph, built at the first batch
+    use_graph = bool(getattr(args, "graph", False))
+    if use_graph:
+        why = CS.refusal(args, world, os.environ)         # decided here, never by catching a capture that failed
+        if why is not None:
+            print("--graph refused, training eagerly: %s" % why, flush=True)
+            use_graph = False
     for epoch in range(args.max_epoch):
         cur, lab, msk = epoch_view(train_data, train_lab, train_mask, args.num_point, rng, dev)
         nb = cur.shape[0] // args.batch_size
         t0 = time.time()
         tot = torch.zeros(3, dtype=torch.float64, device=dev)      # loss sum, correct, seen -- read once per epoch
+        if captured is not None:
+            tot = captured.tot.zero_()                             # ... accumulated inside the graph
         for b in range(nb):
             sl = slice(b * args.batch_size + lo, b * args.batch_size + hi)
             x = cur[sl]
@@ -268,36 +316,15 @@ def train(args):
             else:
                 lr = TU.get_learning_rate(step, args.batch_size, args.learning_rate, args.decay_step, args.decay_rate)
             bn_decay = TU.get_bn_decay(step, args.batch_size, float(args.decay_step))
-            fp.begin_step()
-            out = net(x, is_training=True, bn_decay=bn_decay)
-            if partseg:
-                m = msk[sl]
-                seg_pred, end_points = EV.split_output(out)     # pointnet_partseg: (seg_pred, end_points)
-                loss = mod.get_loss(seg_pred, m) if end_points is None else mod.get_loss(seg_pred, m, end_points)
-            elif with_mask:
-                m = msk[sl]
-                if args.model in MASK_MODELS_END_POINTS:
-                    loss = mod.get_loss(out[0], out[1], y, m, out[2], seg_weight=args.seg_weight)[0]
-                else:
-                    loss = mod.get_loss(out[0], out[1], y, m, seg_weight=args.seg_weight)[0]
+            m = msk[sl] if with_mask else None
+            if use_graph:
+                if captured is None:
+                    captured = CS.CapturedStep(step_body, net, fp, opt, x, y, m)
+                    tot = captured.tot
+                captured.step(x, y, m, lr, bn_decay)
             else:
-                logits, end_points = EV.split_output(out)      # SpiderCNN returns bare logits
-                loss = EV.model_loss(mod, logits, y, end_points)
-            if own:                                                   # minimised, not reported (PointCNN/train.py:171)
-                (loss + own.regularization_loss(net)).backward()
-            else:
-                loss.backward()
-            fp.collect_mean(world)
-            opt.step(lr)
+                step_body(x, y, m, bn_decay, tot, lambda: opt.step(lr))
             step += 1
-            with torch.no_grad():
-                tot[0] += loss.detach()
-                if partseg:                      # point accuracy (`train_partseg.py:237-241`)
-                    tot[1] += (seg_pred.argmax(dim=2) == m).sum()
-                    tot[2] += per_rank * args.num_point
-                else:
-                    tot[1] += (scores(EV.split_output(out)[0]).argmax(dim=1) == y).sum()
-                    tot[2] += per_rank
         if D.dist.is_initialized() and world > 1:
             D.dist.all_reduce(tot)
             tot[0] /= world
@@ -314,13 +341,18 @@ def train(args):
             ev = EV.eval_one_epoch(net, td, tl, per_rank, device=dev, num_classes=args.num_class, scores_fn=scores)
         rec = {"epoch": epoch, "mean_loss": loss_sum / max(nb, 1), "train_acc": correct / max(seen, 1),
                "eval_acc": ev["accuracy"], "eval_avg_class_acc": ev["avg_class_acc"],
-               "clouds_per_s": nb * args.batch_size / (time.time() - t0)}
+               "clouds_per_s": nb * args.batch_size / (time.time() - t0),
+               "graph": use_graph, "captures": captured.captures if captured is not None else 0}
         if "seg_accuracy" in ev:                 # BGA models: the mask accuracy of `train_seg.py:330`
             rec["eval_seg_acc"] = ev["seg_accuracy"]
         log.append(rec)
         if rank == 0:
             print(json.dumps(rec), flush=True)
             torch.save(net.state_dict(), os.path.join(args.log_dir, "model.pt"))
+    if state is not None:                        # what a test compares between two runs
+        state.update(net=net, fp=fp, opt=opt, tot=tot.clone(), captures=captured.captures if captured is not None else 0)
+    if captured is not None:
+        captured.release()
     return log
 
 

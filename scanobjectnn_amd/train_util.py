@@ -210,6 +210,33 @@ class TFAdam:
         _lib.call("pcops_adam_step", self.fp.numel, self.fp.flat.data_ptr(), self.fp.grad.data_ptr(), self.m.data_ptr(),
                   self.v.data_ptr(), float(self.b1), float(self.b2), float(lr_t), float(self.eps))
 
+    # -- a captured step (captured_step.py): the step size travels through device memory ---------------------------------
+    lr_t_dev = None
+
+    def enable_device_lr(self):
+        """the one-element device buffer pcops_adam_step_dev reads lr_t from"""
+        if not (self.fp.flat.is_cuda and FUSED_ADAM):
+            raise RuntimeError("the device-side step size needs the fused update on device buffers (PCOPS_FUSED_ADAM=1)")
+        if self.lr_t_dev is None:
+            self.lr_t_dev = torch.zeros(1, dtype=torch.float32, device=self.fp.flat.device)
+        return self
+
+    @torch.no_grad()
+    def set_lr(self, lr):
+        """the host's half of a captured step: count t and form lr_t exactly as `_step_device` does (float64, then cast to
+        float), then hand it over with a one-element fill on the current stream -- the fill's value is a launch argument,
+        so no host buffer has to outlive the call"""
+        self.t += 1
+        lr_t = lr * math.sqrt(1 - self.b2 ** self.t) / (1 - self.b1 ** self.t)
+        self.lr_t_dev.fill_(float(np.float32(lr_t)))
+
+    @torch.no_grad()
+    def step_from_device_lr(self):
+        """the device's half: pcops_adam_step with lr_t read from `lr_t_dev` -- the launch a captured step replays"""
+        from . import _lib
+        _lib.call("pcops_adam_step_dev", self.fp.numel, self.fp.flat.data_ptr(), self.fp.grad.data_ptr(), self.m.data_ptr(),
+                  self.v.data_ptr(), float(self.b1), float(self.b2), self.lr_t_dev.data_ptr(), float(self.eps))
+
 
 class TFMomentum:
     """tf.train.MomentumOptimizer(lr, momentum) (`pointnet2/train.py:165-166`): accum <- momentum*accum + g;
