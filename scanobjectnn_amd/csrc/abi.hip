@@ -25,10 +25,7 @@ extern "C" int pcops_abi_version(void) { return 4; }   // 2: stat_pivot (shifted
 // bit-reproducible backward passes (reference hazard tf_grouping_g.cu:61-78, tf_sampling_g.cu:183-192:
 // float atomics).  Off: scatter-adds may use atomics / unordered lists.  On: every sum is taken by one owner in
 // ascending row order; entry points that only have an atomic form return PCOPS_ERR_UNSUPPORTED.
-static std::atomic<int> g_deterministic{[] {
-    const char *e = getenv("PCOPS_DETERMINISTIC");
-    return (e && e[0] == '1') ? 1 : 0;
-}()};
+static std::atomic<int> g_deterministic{pcops_env_switch("PCOPS_DETERMINISTIC", false) ? 1 : 0};
 extern "C" void pcops_set_deterministic(int on) { g_deterministic.store(on ? 1 : 0); }
 
 // ---- arithmetic options (pcops.h pcops_set_option).  The ONLY process-wide mutable state besides the deterministic
@@ -36,14 +33,10 @@ extern "C" void pcops_set_deterministic(int on) { g_deterministic.store(on ? 1 :
 // process inside the launchers (a TF-side caller could not choose per call); now the environment
 // only provides the initial value (test override) and the launchers read the table at every call.
 namespace {
-int env_int(const char *name, int dflt) {
-    const char *e = getenv(name);
-    return e ? atoi(e) : dflt;
-}
 // an environment seed is held to the range pcops_set_option accepts (0..hi): a 3, 7 or -1 from the environment would
 // otherwise be returned by pcops_get_option and reach launchers that only know 0..2
 int env_opt(const char *name, int dflt, int hi) {
-    const int v = env_int(name, dflt);
+    const int v = pcops_env_int(name, dflt);
     return v < 0 ? 0 : (v > hi ? hi : v);
 }
 std::atomic<int> g_options[PCOPS_OPT_COUNT] = {};
@@ -54,16 +47,16 @@ void options_init() {
     while (busy.test_and_set(std::memory_order_acquire)) {}
     if (!g_options_init.load(std::memory_order_relaxed)) {
         g_options[PCOPS_OPT_GEMM_SPLIT_BF16].store(env_opt("PCOPS_GEMM_BF3", 1, 2));
-        g_options[PCOPS_OPT_WGRAD_SPLIT_BF16].store(env_int("PCOPS_WGRAD_BF3", 1) != 0);
+        g_options[PCOPS_OPT_WGRAD_SPLIT_BF16].store(pcops_env_int("PCOPS_WGRAD_BF3", 1) != 0);
         g_options[PCOPS_OPT_BWD_FUSED_DX_SPLIT_BF16].store(env_opt("PCOPS_BWD_FUSED_DX3", 2, 2));
-        g_options[PCOPS_OPT_KNN_F16_PREFILTER].store(env_int("PCOPS_KNN_F16", 1) != 0);
+        g_options[PCOPS_OPT_KNN_F16_PREFILTER].store(pcops_env_int("PCOPS_KNN_F16", 1) != 0);
         g_options[PCOPS_OPT_DGRAD_SPLIT_BF16].store(env_opt("PCOPS_DGRAD_BF3", 1, 2));
-        g_options[PCOPS_OPT_BWD_FUSED_GRAM_WGRAD].store(env_int("PCOPS_BWD_FUSED_GW", 0) != 0);
-        g_options[PCOPS_OPT_SCATTER_QFORM].store(env_int("PCOPS_SCATTER_QFORM", 1) != 0);
-        g_options[PCOPS_OPT_XYZ_STATS_MOMENTS].store(env_int("PCOPS_XYZ_STATS_MOMENTS", 0) != 0);
-        g_options[PCOPS_OPT_GRAM_SPLIT_BF16].store(env_int("PCOPS_GRAM_BF3", 1) != 0);
-        g_options[PCOPS_OPT_POOL_TOP_ROWS_PIPELINED].store(env_int("PCOPS_POOL_TOP_ROWS_PIPE", 1) != 0);
-        g_options[PCOPS_OPT_XCONV_CHANNEL_GROUPS].store(env_int("PCOPS_XCONV_GROUPS", 1) != 0);
+        g_options[PCOPS_OPT_BWD_FUSED_GRAM_WGRAD].store(pcops_env_int("PCOPS_BWD_FUSED_GW", 0) != 0);
+        g_options[PCOPS_OPT_SCATTER_QFORM].store(pcops_env_int("PCOPS_SCATTER_QFORM", 1) != 0);
+        g_options[PCOPS_OPT_XYZ_STATS_MOMENTS].store(pcops_env_int("PCOPS_XYZ_STATS_MOMENTS", 0) != 0);
+        g_options[PCOPS_OPT_GRAM_SPLIT_BF16].store(pcops_env_int("PCOPS_GRAM_BF3", 1) != 0);
+        g_options[PCOPS_OPT_POOL_TOP_ROWS_PIPELINED].store(pcops_env_int("PCOPS_POOL_TOP_ROWS_PIPE", 1) != 0);
+        g_options[PCOPS_OPT_XCONV_CHANNEL_GROUPS].store(pcops_env_int("PCOPS_XCONV_GROUPS", 1) != 0);
         g_options_init.store(1, std::memory_order_release);
     }
     busy.clear(std::memory_order_release);

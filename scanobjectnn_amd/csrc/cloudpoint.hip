@@ -41,17 +41,16 @@ constexpr int kSplitCap = 16;     // backward: splits per cloud (a power of two)
 constexpr int kTargetWGs = 512;
 constexpr int kPassChunks = 8;    // backward: chunks per pass (the dWx accumulators of a pass live in registers)
 
-typedef float f4 __attribute__((ext_vector_type(4)));
 
 // row p of a (n, 64) cloud as this lane's four 16-byte pieces: a[jj] = row[16 jj + 4 g .. + 3]; zeros past n
-__device__ __forceinline__ void load_row(const float *__restrict__ cloud, int p, int n, int g, f4 a[4]) {
+__device__ __forceinline__ void load_row(const float *__restrict__ cloud, int p, int n, int g, f32x4 a[4]) {
     if (p < n) {
-        const f4 *r = reinterpret_cast<const f4 *>(cloud + (size_t)p * kK);
+        const f32x4 *r = reinterpret_cast<const f32x4 *>(cloud + (size_t)p * kK);
 #pragma unroll
         for (int jj = 0; jj < 4; ++jj) a[jj] = r[4 * jj + g];
     } else {
 #pragma unroll
-        for (int jj = 0; jj < 4; ++jj) a[jj] = f4{0.f, 0.f, 0.f, 0.f};
+        for (int jj = 0; jj < 4; ++jj) a[jj] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
 }
 
@@ -59,7 +58,7 @@ __device__ __forceinline__ void load_row(const float *__restrict__ cloud, int p,
 __device__ __forceinline__ void stage_chunk(const float *__restrict__ Wx, int c, int cb, float *S) {
     for (int e = threadIdx.x; e < kK * kCW / 4; e += kThreads) {
         const int i = e >> 4, j = (e & 15) * 4;
-        *reinterpret_cast<f4 *>(S + i * kLd + j) = *reinterpret_cast<const f4 *>(Wx + (size_t)i * c + cb + j);
+        *reinterpret_cast<f32x4 *>(S + i * kLd + j) = *reinterpret_cast<const f32x4 *>(Wx + (size_t)i * c + cb + j);
     }
 }
 
@@ -83,7 +82,7 @@ __global__ void __launch_bounds__(kThreads) cloud_point_fwd_kernel(int n, int c,
     const float *Xc = X + cloud * n * kK;
     float *Yc = Y + cloud * n * c;
     const float *ctr = Ctr + cloud * c;
-    f4 a[2][4];
+    f32x4 a[2][4];
     load_row(Xc, p0 + l15, n, g, a[0]);
     load_row(Xc, p0 + 16 + l15, n, g, a[1]);
     const int nch = c / kCW;
@@ -92,11 +91,11 @@ __global__ void __launch_bounds__(kThreads) cloud_point_fwd_kernel(int n, int c,
     for (int j = 0; j < nch; ++j) {
         if (j + 1 < nch) stage_chunk(Wx, c, (j + 1) * kCW, Ws[(j + 1) & 1]);
         const float *M = Ws[j & 1];
-        f4 acc[2][4];
+        f32x4 acc[2][4];
 #pragma unroll
         for (int u = 0; u < 2; ++u)
 #pragma unroll
-            for (int t = 0; t < 4; ++t) acc[u][t] = f4{0.f, 0.f, 0.f, 0.f};
+            for (int t = 0; t < 4; ++t) acc[u][t] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int jj = 0; jj < 4; ++jj) {
 #pragma unroll
@@ -191,19 +190,19 @@ __global__ void __launch_bounds__(kThreads) cloud_point_bwd_kernel(int n, int c,
     __syncthreads();
     const float *Xc = X + cloud * n * kK;
     const float *Gc = G + cloud * n * c, *Yc = Y + cloud * n * c;
-    f4 accW[NCH][4];
+    f32x4 accW[NCH][4];
     float accC[NCH];
 #pragma unroll
     for (int j = 0; j < NCH; ++j) {
         accC[j] = 0.f;
 #pragma unroll
-        for (int t = 0; t < 4; ++t) accW[j][t] = f4{0.f, 0.f, 0.f, 0.f};
+        for (int t = 0; t < 4; ++t) accW[j][t] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
-    f4 gv[4], yv[4];
+    f32x4 gv[4], yv[4];
     auto load_gy = [&](int row, int cb) {
         if (row >= pend) return;
-        const f4 *gr = reinterpret_cast<const f4 *>(Gc + (size_t)row * c + cb);
-        const f4 *yr = reinterpret_cast<const f4 *>(Yc + (size_t)row * c + cb);
+        const f32x4 *gr = reinterpret_cast<const f32x4 *>(Gc + (size_t)row * c + cb);
+        const f32x4 *yr = reinterpret_cast<const f32x4 *>(Yc + (size_t)row * c + cb);
 #pragma unroll
         for (int jj = 0; jj < 4; ++jj) {
             gv[jj] = gr[4 * jj + g];
@@ -211,41 +210,41 @@ __global__ void __launch_bounds__(kThreads) cloud_point_bwd_kernel(int n, int c,
         }
     };
 #pragma unroll
-    for (int jj = 0; jj < 4; ++jj) gv[jj] = yv[jj] = f4{0.f, 0.f, 0.f, 0.f};
+    for (int jj = 0; jj < 4; ++jj) gv[jj] = yv[jj] = f32x4{0.f, 0.f, 0.f, 0.f};
     load_gy(pbeg + 16 * wave + l15, c0);
     for (int p0 = pbeg; p0 < pend; p0 += kPT) {
         const int pw = p0 + 16 * wave, prow = pw + l15;
         {
-            f4 xr[4];
+            f32x4 xr[4];
             load_row(Xc, prow, pend, g, xr);
             float *xs = Xs + (16 * wave + l15) * kTileLd + 4 * g;
 #pragma unroll
-            for (int jj = 0; jj < 4; ++jj) *reinterpret_cast<f4 *>(xs + 16 * jj) = xr[jj];
+            for (int jj = 0; jj < 4; ++jj) *reinterpret_cast<f32x4 *>(xs + 16 * jj) = xr[jj];
         }
-        f4 accX[4];
+        f32x4 accX[4];
 #pragma unroll
-        for (int t = 0; t < 4; ++t) accX[t] = f4{0.f, 0.f, 0.f, 0.f};
+        for (int t = 0; t < 4; ++t) accX[t] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int j = 0; j < NCH; ++j) {
             const int cb = c0 + j * kCW;
             if constexpr (DX) stage_chunk_transposed(Wx, c, cb, Wt);
-            f4 d[4];
+            f32x4 d[4];
             if (prow < pend) {
 #pragma unroll
                 for (int jj = 0; jj < 4; ++jj) {
                     const int o = j * kCW + 16 * jj + 4 * g;
-                    const f4 pp = *reinterpret_cast<const f4 *>(&pqt[0][o]), qq = *reinterpret_cast<const f4 *>(&pqt[1][o]),
-                             tt = *reinterpret_cast<const f4 *>(&pqt[2][o]);
+                    const f32x4 pp = *reinterpret_cast<const f32x4 *>(&pqt[0][o]), qq = *reinterpret_cast<const f32x4 *>(&pqt[1][o]),
+                             tt = *reinterpret_cast<const f32x4 *>(&pqt[2][o]);
 #pragma unroll
                     for (int e = 0; e < 4; ++e) d[jj][e] = fmaf(pp[e], gv[jj][e], fmaf(qq[e], yv[jj][e], tt[e]));
                 }
             } else {
 #pragma unroll
-                for (int jj = 0; jj < 4; ++jj) d[jj] = f4{0.f, 0.f, 0.f, 0.f};
+                for (int jj = 0; jj < 4; ++jj) d[jj] = f32x4{0.f, 0.f, 0.f, 0.f};
             }
             float *ds = Ds + (16 * wave + l15) * kTileLd + 4 * g;
 #pragma unroll
-            for (int jj = 0; jj < 4; ++jj) *reinterpret_cast<f4 *>(ds + 16 * jj) = d[jj];
+            for (int jj = 0; jj < 4; ++jj) *reinterpret_cast<f32x4 *>(ds + 16 * jj) = d[jj];
             __syncthreads();
             // the next chunk's (or the next step's first chunk's) rows of G and Y are on their way under the products
             if (j + 1 < NCH) load_gy(prow, cb + kCW);
@@ -312,17 +311,17 @@ __global__ void __launch_bounds__(kThreads) cloud_point_bwd_kernel(int n, int c,
 // thread (zq = wave, lane) adds the parts of quarter zq in ascending order, the four quarter sums are added in ascending order
 __global__ void __launch_bounds__(kThreads) cloud_point_reduce_w_kernel(int parts, long long len4, const float *__restrict__ ws,
                                                                         float *__restrict__ dWx) {
-    __shared__ f4 sh[kWaves][64];
+    __shared__ f32x4 sh[kWaves][64];
     const int lane = threadIdx.x & 63, zq = threadIdx.x >> 6;
     const long long e4 = (long long)blockIdx.x * 64 + lane;
     const int per = (parts + kWaves - 1) / kWaves, zbeg = min(zq * per, parts), zend = min(zbeg + per, parts);
-    const f4 *src = reinterpret_cast<const f4 *>(ws) + e4;
-    f4 v = {0.f, 0.f, 0.f, 0.f};
+    const f32x4 *src = reinterpret_cast<const f32x4 *>(ws) + e4;
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll 4
     for (int z = zbeg; z < zend; ++z) v += src[(size_t)z * len4];
     sh[zq][lane] = v;
     __syncthreads();
-    if (zq == 0) reinterpret_cast<f4 *>(dWx)[e4] = ((sh[0][lane] + sh[1][lane]) + sh[2][lane]) + sh[3][lane];
+    if (zq == 0) reinterpret_cast<f32x4 *>(dWx)[e4] = ((sh[0][lane] + sh[1][lane]) + sh[2][lane]) + sh[3][lane];
 }
 
 // dCtr[cloud][ch] = ws[cloud][0][ch] + ws[cloud][1][ch] + ... in ascending order

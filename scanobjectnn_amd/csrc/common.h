@@ -8,6 +8,7 @@
 #include <type_traits>
 
 #include "../../include/pcops.h"
+#include "device.h"
 
 #define PCOPS_REQUIRE_PTR(p) \
     do { if ((p) == nullptr) return PCOPS_ERR_NULL_POINTER; } while (0)
@@ -15,6 +16,18 @@
     do { if (!(cond)) return PCOPS_ERR_BAD_SHAPE; } while (0)
 #define PCOPS_REQUIRE_ARG(cond) \
     do { if (!(cond)) return PCOPS_ERR_BAD_ARGUMENT; } while (0)
+
+// The two readers of the environment.  A switch that is on by default is turned off by a leading '0', one that is off by
+// default is turned on by a leading '1'; anything else leaves the default.  Callers keep the value in a `static const`
+// where it is to be read once per process.
+static inline bool pcops_env_switch(const char *name, bool dflt) {
+    const char *e = getenv(name);
+    return dflt ? !(e && e[0] == '0') : (e && e[0] == '1');
+}
+static inline int pcops_env_int(const char *name, int dflt) {
+    const char *e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
 
 static inline int pcops_launch_status() {
     const hipError_t e = hipGetLastError();

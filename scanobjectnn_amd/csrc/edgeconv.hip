@@ -26,21 +26,6 @@
 
 namespace {
 
-typedef float f2 __attribute__((ext_vector_type(2)));
-typedef unsigned int ec_u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t ec_rsrc(const void *base, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), 0, bytes, 0x00020000);
-}
-__device__ __forceinline__ float4 ec_load4(__amdgpu_buffer_rsrc_t r, unsigned voff) {
-    const ec_u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, voff, 0, 0);
-    return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
-}
-__device__ __forceinline__ unsigned ec_load1(__amdgpu_buffer_rsrc_t r, unsigned voff) {
-    return __builtin_amdgcn_raw_buffer_load_b32(r, voff, 0, 0);
-}
-
-
 constexpr int kGB = 64;          // groups (forward) / points (walk) per workgroup
 constexpr int kSets = 16;        // 16-lane sets per 256-thread workgroup: one group / point each, four rounds
 
@@ -70,48 +55,48 @@ struct FwdArgs {
 // and one sequential fp32 sum carried that into SQ -- relative RMS 1.2e-6 .. 1.4e-6 against float64 at s = 128, 5e-7 folded.
 template <int MODE, bool UP, bool BLOCKED>
 __device__ __forceinline__ void ec_fwd_groups(const FwdArgs &a, const unsigned *offs, long long g0, int set, int quad,
-                                              unsigned tq, __amdgpu_buffer_rsrc_t rq, int ch, f2 (&s1)[2], f2 (&s2)[2]) {
+                                              unsigned tq, __amdgpu_buffer_rsrc_t rq, int ch, f32x2 (&s1)[2], f32x2 (&s2)[2]) {
     const int S = a.S, C = a.C;
     const float kf = (float)S;
-    f2 sg[2] = {{1.f, 1.f}, {1.f, 1.f}};
-    f2 qz[2] = {{0.f, 0.f}, {0.f, 0.f}}, cz[2] = {{0.f, 0.f}, {0.f, 0.f}}, pv[2] = {{0.f, 0.f}, {0.f, 0.f}};
+    f32x2 sg[2] = {{1.f, 1.f}, {1.f, 1.f}};
+    f32x2 qz[2] = {{0.f, 0.f}, {0.f, 0.f}}, cz[2] = {{0.f, 0.f}, {0.f, 0.f}}, pv[2] = {{0.f, 0.f}, {0.f, 0.f}};
     if (MODE == 0) {
         if (!UP) {
             const float4 ga = *reinterpret_cast<const float4 *>(a.gamma + ch);
-            sg[0] = f2{ga.x < 0.f ? -1.f : 1.f, ga.y < 0.f ? -1.f : 1.f};
-            sg[1] = f2{ga.z < 0.f ? -1.f : 1.f, ga.w < 0.f ? -1.f : 1.f};
+            sg[0] = f32x2{ga.x < 0.f ? -1.f : 1.f, ga.y < 0.f ? -1.f : 1.f};
+            sg[1] = f32x2{ga.z < 0.f ? -1.f : 1.f, ga.w < 0.f ? -1.f : 1.f};
         }
         if (a.stats) {
             const float4 q0 = *reinterpret_cast<const float4 *>(a.Q + ch);
             float4 p4 = make_float4(0.f, 0.f, 0.f, 0.f);
             if (a.pivot) p4 = *reinterpret_cast<const float4 *>(a.pivot + ch);
-            qz[0] = f2{q0.x, q0.y}; qz[1] = f2{q0.z, q0.w};
-            cz[0] = f2{q0.x - p4.x, q0.y - p4.y}; cz[1] = f2{q0.z - p4.z, q0.w - p4.w};
+            qz[0] = f32x2{q0.x, q0.y}; qz[1] = f32x2{q0.z, q0.w};
+            cz[0] = f32x2{q0.x - p4.x, q0.y - p4.y}; cz[1] = f32x2{q0.z - p4.z, q0.w - p4.w};
         }
     } else if (a.stats && a.pivot) {
         const float4 p4 = *reinterpret_cast<const float4 *>(a.pivot + ch);
-        pv[0] = f2{p4.x, p4.y}; pv[1] = f2{p4.z, p4.w};
+        pv[0] = f32x2{p4.x, p4.y}; pv[1] = f32x2{p4.z, p4.w};
     }
 #pragma unroll 1
     for (int r = 0; r < kGB / kSets; ++r) {
         const int gl = set + kSets * r;
         const long long g = g0 + gl;
         const float4 c4 = *reinterpret_cast<const float4 *>(a.Ctr + g * a.ldc + ch);
-        const f2 ct[2] = {{c4.x, c4.y}, {c4.z, c4.w}};
-        f2 sq[2] = {{0.f, 0.f}, {0.f, 0.f}}, sq2[2] = {{0.f, 0.f}, {0.f, 0.f}};
+        const f32x2 ct[2] = {{c4.x, c4.y}, {c4.z, c4.w}};
+        f32x2 sq[2] = {{0.f, 0.f}, {0.f, 0.f}}, sq2[2] = {{0.f, 0.f}, {0.f, 0.f}};
         float ex[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
         int ea[4] = {0, 0, 0, 0};
         float *yrow = MODE == 1 ? a.Y + g * S * (long long)C + ch : nullptr;
         const bool ynt = MODE == 1 && a.nt != 0;
         const unsigned *og = offs + gl * S;
         auto take = [&](const float4 &q, int s) {
-            const f2 qa = f2{q.x, q.y}, qb = f2{q.z, q.w};
+            const f32x2 qa = f32x2{q.x, q.y}, qb = f32x2{q.z, q.w};
             if (MODE == 0) {
-                const f2 da = qa - qz[0], db = qb - qz[1];
+                const f32x2 da = qa - qz[0], db = qb - qz[1];
                 sq[0] += da; sq[1] += db;
                 sq2[0] = __builtin_elementwise_fma(da, da, sq2[0]);
                 sq2[1] = __builtin_elementwise_fma(db, db, sq2[1]);
-                const f2 va = UP ? qa : qa * sg[0], vb = UP ? qb : qb * sg[1];
+                const f32x2 va = UP ? qa : qa * sg[0], vb = UP ? qb : qb * sg[1];
                 const float v[4] = {va.x, va.y, vb.x, vb.y};
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
@@ -120,41 +105,40 @@ __device__ __forceinline__ void ec_fwd_groups(const FwdArgs &a, const unsigned *
                     ex[e] = better ? v[e] : ex[e];                //  canonicalising multiply per loaded register pair)
                 }
             } else {
-                const f2 ya = ct[0] + qa, yb = ct[1] + qb;
+                const f32x2 ya = ct[0] + qa, yb = ct[1] + qb;
                 // (non-temporal for the big streams -- the T-Net's 2.7 GB: 748 -> 695 us; nothing reads Y back before it
                 // has left every cache anyway)
-                typedef float ec_f4 __attribute__((ext_vector_type(4)));
-                if (ynt) __builtin_nontemporal_store(ec_f4{ya.x, ya.y, yb.x, yb.y}, reinterpret_cast<ec_f4 *>(yrow + (long long)s * C));
+                if (ynt) __builtin_nontemporal_store(f32x4{ya.x, ya.y, yb.x, yb.y}, reinterpret_cast<f32x4 *>(yrow + (long long)s * C));
                 else *reinterpret_cast<float4 *>(yrow + (long long)s * C) = make_float4(ya.x, ya.y, yb.x, yb.y);
-                const f2 da = ya - pv[0], db = yb - pv[1];
+                const f32x2 da = ya - pv[0], db = yb - pv[1];
                 s1[0] += da; s1[1] += db;
                 s2[0] = __builtin_elementwise_fma(da, da, s2[0]);
                 s2[1] = __builtin_elementwise_fma(db, db, s2[1]);
             }
         };
         constexpr bool blocked = BLOCKED && MODE == 0;
-        f2 hq[2] = {{0.f, 0.f}, {0.f, 0.f}};
-        auto fold = [&]() { hq[0] += sq[0]; hq[1] += sq[1]; sq[0] = f2{0.f, 0.f}; sq[1] = f2{0.f, 0.f}; };
+        f32x2 hq[2] = {{0.f, 0.f}, {0.f, 0.f}};
+        auto fold = [&]() { hq[0] += sq[0]; hq[1] += sq[1]; sq[0] = f32x2{0.f, 0.f}; sq[1] = f32x2{0.f, 0.f}; };
         int s = 0;
         if ((S & 3) == 0) {
             for (; s + 8 <= S; s += 8) {
                 const uint4 o0 = *reinterpret_cast<const uint4 *>(og + s), o1 = *reinterpret_cast<const uint4 *>(og + s + 4);
-                const float4 q0 = ec_load4(rq, o0.x + tq), q1 = ec_load4(rq, o0.y + tq), q2 = ec_load4(rq, o0.z + tq),
-                             q3 = ec_load4(rq, o0.w + tq), q4 = ec_load4(rq, o1.x + tq), q5 = ec_load4(rq, o1.y + tq),
-                             q6 = ec_load4(rq, o1.z + tq), q7 = ec_load4(rq, o1.w + tq);
+                const float4 q0 = buf_load4(rq, o0.x + tq, 0), q1 = buf_load4(rq, o0.y + tq, 0), q2 = buf_load4(rq, o0.z + tq, 0),
+                             q3 = buf_load4(rq, o0.w + tq, 0), q4 = buf_load4(rq, o1.x + tq, 0), q5 = buf_load4(rq, o1.y + tq, 0),
+                             q6 = buf_load4(rq, o1.z + tq, 0), q7 = buf_load4(rq, o1.w + tq, 0);
                 take(q0, s); take(q1, s + 1); take(q2, s + 2); take(q3, s + 3);
                 take(q4, s + 4); take(q5, s + 5); take(q6, s + 6); take(q7, s + 7);
                 if (blocked && ((s + 8) & 15) == 0 && s + 8 < S) fold();
             }
             for (; s + 4 <= S; s += 4) {
                 const uint4 o0 = *reinterpret_cast<const uint4 *>(og + s);
-                const float4 q0 = ec_load4(rq, o0.x + tq), q1 = ec_load4(rq, o0.y + tq), q2 = ec_load4(rq, o0.z + tq),
-                             q3 = ec_load4(rq, o0.w + tq);
+                const float4 q0 = buf_load4(rq, o0.x + tq, 0), q1 = buf_load4(rq, o0.y + tq, 0), q2 = buf_load4(rq, o0.z + tq, 0),
+                             q3 = buf_load4(rq, o0.w + tq, 0);
                 take(q0, s); take(q1, s + 1); take(q2, s + 2); take(q3, s + 3);
             }
         }
         for (; s < S; ++s) {
-            take(ec_load4(rq, og[s] + tq), s);
+            take(buf_load4(rq, og[s] + tq, 0), s);
             if (blocked && (s & 15) == 15 && s + 1 < S) fold();
         }
         if (MODE == 0) {
@@ -169,10 +153,10 @@ __device__ __forceinline__ void ec_fwd_groups(const FwdArgs &a, const unsigned *
             a4.x = (unsigned char)ea[0]; a4.y = (unsigned char)ea[1]; a4.z = (unsigned char)ea[2]; a4.w = (unsigned char)ea[3];
             *reinterpret_cast<uchar4 *>(a.arg + g * C + ch) = a4;
             if (a.stats) {
-                const f2 k2 = f2{kf, kf};
+                const f32x2 k2 = f32x2{kf, kf};
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
-                    const f2 cv = ct[h] + cz[h];
+                    const f32x2 cv = ct[h] + cz[h];
                     s1[h] += __builtin_elementwise_fma(k2, cv, sq[h]);
                     s2[h] += __builtin_elementwise_fma(cv, __builtin_elementwise_fma(k2, cv, sq[h] + sq[h]), sq2[h]);
                 }
@@ -200,9 +184,9 @@ __global__ __launch_bounds__(256) void ec_fwd_kernel(FwdArgs a) {
     const unsigned c4 = (unsigned)a.ldq * 4u;
     for (int e = tid; e < kGB * S; e += 256) ec_sm[e] = (unsigned)ig[e] * c4 + base;
     __syncthreads();
-    const __amdgpu_buffer_rsrc_t rq = ec_rsrc(a.Q, (unsigned)((long long)a.b * a.n * a.ldq * 4));
+    const __amdgpu_buffer_rsrc_t rq = make_rsrc_u32(a.Q, (unsigned)((long long)a.b * a.n * a.ldq * 4));
     const unsigned tq = (unsigned)quad * 16u;
-    f2 s1[2] = {{0.f, 0.f}, {0.f, 0.f}}, s2[2] = {{0.f, 0.f}, {0.f, 0.f}};
+    f32x2 s1[2] = {{0.f, 0.f}, {0.f, 0.f}}, s2[2] = {{0.f, 0.f}, {0.f, 0.f}};
     bool up = true;
     if (MODE == 0) {
         const float4 ga = *reinterpret_cast<const float4 *>(a.gamma + ch);
@@ -360,9 +344,9 @@ __global__ __launch_bounds__(256) void ec_walk_kernel(WalkArgs a) {
     const unsigned c4 = (unsigned)C * 4u, cc4 = (unsigned)a.ldc * 4u, tq = ((unsigned)h * 64u + (unsigned)quad * 4u) * 4u;
     const int mS = a.m * S;
     // (the Ctr resource ends with the cloud's last row: a column-slice view shares its rows with Q, never with cloud b + 1)
-    const __amdgpu_buffer_rsrc_t rc = ec_rsrc(a.Ctr + (long long)b * a.m * a.ldc, (unsigned)(a.m - 1) * cc4 + c4);
-    const __amdgpu_buffer_rsrc_t rg = ec_rsrc(HAS_G ? a.G + (long long)b * mS * C : a.Ctr, HAS_G ? (unsigned)mS * c4 : 0u);
-    const __amdgpu_buffer_rsrc_t ro = ec_rsrc(a.order + (long long)b * mS, (unsigned)mS * 4u);
+    const __amdgpu_buffer_rsrc_t rc = make_rsrc_u32(a.Ctr + (long long)b * a.m * a.ldc, (unsigned)(a.m - 1) * cc4 + c4);
+    const __amdgpu_buffer_rsrc_t rg = make_rsrc_u32(HAS_G ? a.G + (long long)b * mS * C : a.Ctr, HAS_G ? (unsigned)mS * c4 : 0u);
+    const __amdgpu_buffer_rsrc_t ro = make_rsrc_u32(a.order + (long long)b * mS, (unsigned)mS * 4u);
     const int *sb = a.start + (long long)b * (a.n + 1);
     const float4 cq = *reinterpret_cast<const float4 *>(a.q + ch);
     const float4 ct = *reinterpret_cast<const float4 *>(a.t + ch);
@@ -374,24 +358,24 @@ __global__ __launch_bounds__(256) void ec_walk_kernel(WalkArgs a) {
         const int i = chunk * kGB + set + kSets * r;
         if (i >= a.n) break;
         const int k0 = sb[i], k1 = sb[i + 1];
-        f2 ac[2] = {{0.f, 0.f}, {0.f, 0.f}}, ag[2] = {{0.f, 0.f}, {0.f, 0.f}};
+        f32x2 ac[2] = {{0.f, 0.f}, {0.f, 0.f}}, ag[2] = {{0.f, 0.f}, {0.f, 0.f}};
         for (int k = k0; k < k1; k += 4) {
             unsigned w[4];
 #pragma unroll
-            for (int u = 0; u < 4; ++u) w[u] = ec_load1(ro, (unsigned)(k + u) * 4u);     // beyond the cloud's list: 0 ...
+            for (int u = 0; u < 4; ++u) w[u] = buf_load1(ro, (unsigned)(k + u) * 4u, 0);     // beyond the cloud's list: 0 ...
 #pragma unroll
             for (int u = 0; u < 4; ++u) w[u] = k + u < k1 ? w[u] : sentinel;             // ... beyond this list: sentinel
             float4 cc[4], gg[4];
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const unsigned g = w[u] >> 8;
-                cc[u] = ec_load4(rc, g * cc4 + tq);
-                if (HAS_G) gg[u] = ec_load4(rg, (g * (unsigned)S + (w[u] & 255u)) * c4 + tq);
+                cc[u] = buf_load4(rc, g * cc4 + tq, 0);
+                if (HAS_G) gg[u] = buf_load4(rg, (g * (unsigned)S + (w[u] & 255u)) * c4 + tq, 0);
             }
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
-                ac[0] += f2{cc[u].x, cc[u].y}; ac[1] += f2{cc[u].z, cc[u].w};
-                if (HAS_G) { ag[0] += f2{gg[u].x, gg[u].y}; ag[1] += f2{gg[u].z, gg[u].w}; }
+                ac[0] += f32x2{cc[u].x, cc[u].y}; ac[1] += f32x2{cc[u].z, cc[u].w};
+                if (HAS_G) { ag[0] += f32x2{gg[u].x, gg[u].y}; ag[1] += f32x2{gg[u].z, gg[u].w}; }
             }
         }
         const long long pt = (long long)b * a.n + i;
@@ -444,7 +428,7 @@ __global__ __launch_bounds__(256) void ec_tnet_ctr_kernel(CtrArgs a) {
     const unsigned c4 = (unsigned)a.ldq * 4u;
     for (int e = tid; e < kGB * S; e += 256) ec_sm[e] = (unsigned)ig[e] * c4 + base;
     __syncthreads();
-    const __amdgpu_buffer_rsrc_t rq = ec_rsrc(a.Q, (unsigned)((long long)a.b * a.n * a.ldq * 4));
+    const __amdgpu_buffer_rsrc_t rq = make_rsrc_u32(a.Q, (unsigned)((long long)a.b * a.n * a.ldq * 4));
     const unsigned tq = (unsigned)quad * 16u;
     const float4 cp = *reinterpret_cast<const float4 *>(a.p + ch);
     const float4 cq = *reinterpret_cast<const float4 *>(a.q + ch);
@@ -456,26 +440,26 @@ __global__ __launch_bounds__(256) void ec_tnet_ctr_kernel(CtrArgs a) {
         const long long g = g0 + gl;
         const unsigned *og = ec_sm + gl * S;
         const float *grow = a.G + g * S * (long long)C + ch;
-        f2 sq[2] = {{0.f, 0.f}, {0.f, 0.f}}, sgm[2] = {{0.f, 0.f}, {0.f, 0.f}};
+        f32x2 sq[2] = {{0.f, 0.f}, {0.f, 0.f}}, sgm[2] = {{0.f, 0.f}, {0.f, 0.f}};
         int s = 0;
         for (; s + 4 <= S; s += 4) {
             float4 qv[4], gv[4];
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
-                qv[u] = ec_load4(rq, og[s + u] + tq);
+                qv[u] = buf_load4(rq, og[s + u] + tq, 0);
                 gv[u] = *reinterpret_cast<const float4 *>(grow + (long long)(s + u) * C);
             }
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
-                sq[0] += f2{qv[u].x, qv[u].y}; sq[1] += f2{qv[u].z, qv[u].w};
-                sgm[0] += f2{gv[u].x, gv[u].y}; sgm[1] += f2{gv[u].z, gv[u].w};
+                sq[0] += f32x2{qv[u].x, qv[u].y}; sq[1] += f32x2{qv[u].z, qv[u].w};
+                sgm[0] += f32x2{gv[u].x, gv[u].y}; sgm[1] += f32x2{gv[u].z, gv[u].w};
             }
         }
         for (; s < S; ++s) {
-            const float4 qv = ec_load4(rq, og[s] + tq);
+            const float4 qv = buf_load4(rq, og[s] + tq, 0);
             const float4 gv = *reinterpret_cast<const float4 *>(grow + (long long)s * C);
-            sq[0] += f2{qv.x, qv.y}; sq[1] += f2{qv.z, qv.w};
-            sgm[0] += f2{gv.x, gv.y}; sgm[1] += f2{gv.z, gv.w};
+            sq[0] += f32x2{qv.x, qv.y}; sq[1] += f32x2{qv.z, qv.w};
+            sgm[0] += f32x2{gv.x, gv.y}; sgm[1] += f32x2{gv.z, gv.w};
         }
         const float4 c4v = *reinterpret_cast<const float4 *>(a.Ctr + g * a.ldc + ch);
         float4 d;
@@ -498,22 +482,22 @@ constexpr int kSliceCh = 16;
 // BLOCKED: as in ec_fwd_groups (more than 20 neighbours, always the in-line form: NI = 1 there)
 template <bool UP, int NI, bool BLOCKED>         // NI int4 index registers per group: S <= 4 NI in the prefetched form
 __device__ __forceinline__ void ec_fwd_lds_groups(const FwdArgs &a, const float4 *qs, int b, int quad, int cl, int ch,
-                                                  f2 (&s1)[2], f2 (&s2)[2]) {
+                                                  f32x2 (&s1)[2], f32x2 (&s2)[2]) {
     const int S = a.S, C = a.C, m = a.m;
     const float kf = (float)S;
-    f2 sg[2] = {{1.f, 1.f}, {1.f, 1.f}};
-    f2 qz[2] = {{0.f, 0.f}, {0.f, 0.f}}, cz[2] = {{0.f, 0.f}, {0.f, 0.f}};
+    f32x2 sg[2] = {{1.f, 1.f}, {1.f, 1.f}};
+    f32x2 qz[2] = {{0.f, 0.f}, {0.f, 0.f}}, cz[2] = {{0.f, 0.f}, {0.f, 0.f}};
     if (!UP) {
         const float4 ga = *reinterpret_cast<const float4 *>(a.gamma + ch);
-        sg[0] = f2{ga.x < 0.f ? -1.f : 1.f, ga.y < 0.f ? -1.f : 1.f};
-        sg[1] = f2{ga.z < 0.f ? -1.f : 1.f, ga.w < 0.f ? -1.f : 1.f};
+        sg[0] = f32x2{ga.x < 0.f ? -1.f : 1.f, ga.y < 0.f ? -1.f : 1.f};
+        sg[1] = f32x2{ga.z < 0.f ? -1.f : 1.f, ga.w < 0.f ? -1.f : 1.f};
     }
     if (a.stats) {
         const float4 q0 = *reinterpret_cast<const float4 *>(a.Q + ch);
         float4 p4 = make_float4(0.f, 0.f, 0.f, 0.f);
         if (a.pivot) p4 = *reinterpret_cast<const float4 *>(a.pivot + ch);
-        qz[0] = f2{q0.x, q0.y}; qz[1] = f2{q0.z, q0.w};
-        cz[0] = f2{q0.x - p4.x, q0.y - p4.y}; cz[1] = f2{q0.z - p4.z, q0.w - p4.w};
+        qz[0] = f32x2{q0.x, q0.y}; qz[1] = f32x2{q0.z, q0.w};
+        cz[0] = f32x2{q0.x - p4.x, q0.y - p4.y}; cz[1] = f32x2{q0.z - p4.z, q0.w - p4.w};
     }
     // the group's indices (and its Ctr quad) are loaded ONE GROUP AHEAD: counters of the first version showed the waves
     // parked at s_waitcnt 68 % of their cycles, a global-load latency per four neighbours (profiles/r05_ec_counters.txt)
@@ -543,17 +527,17 @@ __device__ __forceinline__ void ec_fwd_lds_groups(const FwdArgs &a, const float4
             }
             nxtc = *reinterpret_cast<const float4 *>(a.Ctr + (g + 256) * a.ldc + ch);
         }
-        const f2 ct[2] = {{curc.x, curc.y}, {curc.z, curc.w}};
-        f2 sq[2] = {{0.f, 0.f}, {0.f, 0.f}}, sq2[2] = {{0.f, 0.f}, {0.f, 0.f}};
+        const f32x2 ct[2] = {{curc.x, curc.y}, {curc.z, curc.w}};
+        f32x2 sq[2] = {{0.f, 0.f}, {0.f, 0.f}}, sq2[2] = {{0.f, 0.f}, {0.f, 0.f}};
         float ex[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
         int ea[4] = {0, 0, 0, 0};
         auto take = [&](const float4 &q, int s) {
-            const f2 qa = f2{q.x, q.y}, qb = f2{q.z, q.w};
-            const f2 da = qa - qz[0], db = qb - qz[1];
+            const f32x2 qa = f32x2{q.x, q.y}, qb = f32x2{q.z, q.w};
+            const f32x2 da = qa - qz[0], db = qb - qz[1];
             sq[0] += da; sq[1] += db;
             sq2[0] = __builtin_elementwise_fma(da, da, sq2[0]);
             sq2[1] = __builtin_elementwise_fma(db, db, sq2[1]);
-            const f2 va = UP ? qa : qa * sg[0], vb = UP ? qb : qb * sg[1];
+            const f32x2 va = UP ? qa : qa * sg[0], vb = UP ? qb : qb * sg[1];
             const float v[4] = {va.x, va.y, vb.x, vb.y};
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
@@ -573,12 +557,12 @@ __device__ __forceinline__ void ec_fwd_lds_groups(const FwdArgs &a, const float4
         } else {
             const int *ig = a.idx + g * S;
             if constexpr (BLOCKED) {
-                f2 hq[2] = {{0.f, 0.f}, {0.f, 0.f}};
+                f32x2 hq[2] = {{0.f, 0.f}, {0.f, 0.f}};
                 for (int s = 0; s < S; ++s) {
                     take(qs[ig[s] * 4 + cl], s);
                     if ((s & 15) == 15 && s + 1 < S) {
                         hq[0] += sq[0]; hq[1] += sq[1];
-                        sq[0] = f2{0.f, 0.f}; sq[1] = f2{0.f, 0.f};
+                        sq[0] = f32x2{0.f, 0.f}; sq[1] = f32x2{0.f, 0.f};
                     }
                 }
                 sq[0] += hq[0]; sq[1] += hq[1];
@@ -596,10 +580,10 @@ __device__ __forceinline__ void ec_fwd_lds_groups(const FwdArgs &a, const float4
         a4.x = (unsigned char)ea[0]; a4.y = (unsigned char)ea[1]; a4.z = (unsigned char)ea[2]; a4.w = (unsigned char)ea[3];
         *reinterpret_cast<uchar4 *>(a.arg + g * C + ch) = a4;
         if (a.stats) {
-            const f2 k2 = f2{kf, kf};
+            const f32x2 k2 = f32x2{kf, kf};
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
-                const f2 cv = ct[h] + cz[h];
+                const f32x2 cv = ct[h] + cz[h];
                 s1[h] += __builtin_elementwise_fma(k2, cv, sq[h]);
                 s2[h] += __builtin_elementwise_fma(cv, __builtin_elementwise_fma(k2, cv, sq[h] + sq[h]), sq2[h]);
             }
@@ -624,7 +608,7 @@ __global__ __launch_bounds__(1024) void ec_fwd_lds_kernel(FwdArgs a) {
         for (int i = quad; i < n; i += 256) ec_qs[i * 4 + cl] = *reinterpret_cast<const float4 *>(src + (long long)i * a.ldq);
     }
     __syncthreads();
-    f2 s1[2] = {{0.f, 0.f}, {0.f, 0.f}}, s2[2] = {{0.f, 0.f}, {0.f, 0.f}};
+    f32x2 s1[2] = {{0.f, 0.f}, {0.f, 0.f}}, s2[2] = {{0.f, 0.f}, {0.f, 0.f}};
     const float4 ga = *reinterpret_cast<const float4 *>(a.gamma + ch);
     const bool up = __all(!(ga.x < 0.f) && !(ga.y < 0.f) && !(ga.z < 0.f) && !(ga.w < 0.f)) != 0;
     // (five index registers: k <= 20 neighbours take the prefetched form, larger groups read their indices in line;
@@ -724,7 +708,7 @@ __global__ __launch_bounds__(1024) void ec_walk_lds_kernel(WalkLdsArgs wa) {
         const float4 q1 = *reinterpret_cast<const float4 *>(Qb + (long long)i * ldq + c1 * 4);
         const float4 o0 = *reinterpret_cast<const float4 *>(dQb + (long long)i * lddq + c0 * 4);
         const float4 o1 = *reinterpret_cast<const float4 *>(dQb + (long long)i * lddq + c1 * 4);
-        f2 a0[2] = {{0.f, 0.f}, {0.f, 0.f}}, a1[2] = {{0.f, 0.f}, {0.f, 0.f}};
+        f32x2 a0[2] = {{0.f, 0.f}, {0.f, 0.f}}, a1[2] = {{0.f, 0.f}, {0.f, 0.f}};
         int k = k0;
         for (; k + 4 <= k1; k += 4) {
             unsigned g[4];
@@ -733,15 +717,15 @@ __global__ __launch_bounds__(1024) void ec_walk_lds_kernel(WalkLdsArgs wa) {
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const float4 x0 = ec_cs[g[u] * 2 + c0], x1 = ec_cs[g[u] * 2 + c1];
-                a0[0] += f2{x0.x, x0.y}; a0[1] += f2{x0.z, x0.w};
-                a1[0] += f2{x1.x, x1.y}; a1[1] += f2{x1.z, x1.w};
+                a0[0] += f32x2{x0.x, x0.y}; a0[1] += f32x2{x0.z, x0.w};
+                a1[0] += f32x2{x1.x, x1.y}; a1[1] += f32x2{x1.z, x1.w};
             }
         }
         for (; k < k1; ++k) {
             const unsigned g = (unsigned)cs16[k] >> sbits;
             const float4 x0 = ec_cs[g * 2 + c0], x1 = ec_cs[g * 2 + c1];
-            a0[0] += f2{x0.x, x0.y}; a0[1] += f2{x0.z, x0.w};
-            a1[0] += f2{x1.x, x1.y}; a1[1] += f2{x1.z, x1.w};
+            a0[0] += f32x2{x0.x, x0.y}; a0[1] += f32x2{x0.z, x0.w};
+            a1[0] += f32x2{x1.x, x1.y}; a1[1] += f32x2{x1.z, x1.w};
         }
         const float kf = (float)(k1 - k0);
         float4 d0, d1;
@@ -765,7 +749,7 @@ int ec_sbits(int s) { int sb = 0; while ((1 << sb) < s) ++sb; return sb; }
 bool ec_codes16_ok(int m, int s) { return ((long long)m << ec_sbits(s)) <= 65536; }
 bool ec_lds_walk_ok(int n, int m, int s) { return ec_codes16_ok(m, s) && ec_lds_walk_bytes(n, m, s) <= kLdsMax; }
 bool ec_lds_on() {
-    static const bool on = [] { const char *e = getenv("PCOPS_EDGECONV_LDS"); return !(e && e[0] == '0'); }();
+    static const bool on = pcops_env_switch("PCOPS_EDGECONV_LDS", true);
     return on;
 }
 
@@ -979,7 +963,7 @@ __global__ __launch_bounds__(1024) void ec_bwd_lds_kernel(BwdLdsArgs a) {
             if (i < 0) continue;
             const int k0 = u ? pk0[1] : pk0[0], k1 = u ? pk1[1] : pk1[0];
             const float4 qi = u ? qc[1] : qc[0];
-            f2 sc0 = {0.f, 0.f}, sc1 = {0.f, 0.f};                       // sums of Ctr, channels (0 1) (2 3)
+            f32x2 sc0 = {0.f, 0.f}, sc1 = {0.f, 0.f};                       // sums of Ctr, channels (0 1) (2 3)
             float4 sv = make_float4(0.f, 0.f, 0.f, 0.f);                  // arg-row sums
             // an entry reads its group's Ctr row and arg word; the a row ONLY when one of the four arg bytes is its slot
             // (18 % of the lanes: the LDS moves bytes for active lanes only, and random-row reads are what bounds the walk)
@@ -987,8 +971,8 @@ __global__ __launch_bounds__(1024) void ec_bwd_lds_kernel(BwdLdsArgs a) {
                 const unsigned g = code >> sbits, s = code & smask;
                 const float4 x = ec_ca[g];
                 const unsigned z = ar[g] ^ (s * 0x01010101u);             // a zero byte where arg == slot
-                sc0 += f2{x.x, x.y};
-                sc1 += f2{x.z, x.w};
+                sc0 += f32x2{x.x, x.y};
+                sc1 += f32x2{x.z, x.w};
                 if ((z - 0x01010101u) & ~z & 0x80808080u) {
                     const float4 av = ec_ca[m + 1 + g];
                     sv.x += (z & 0x000000ffu) == 0u ? av.x : 0.f;
@@ -1195,7 +1179,7 @@ bool ec_bwd_fused_ok(int n, int m, int s, int c) {
     // 8-channel slice -- 32 bytes out of every 256-byte row of four matrices, ~10 000 L1 misses per workgroup at ~0.13 lines
     // per cycle and CU -- and two 4-channel walks take 27 000 each (VALU issue: 27 instructions per entry).  The walk itself
     // is what was hoped for (no atomics: 183 us per layer for both terms); row-major operands sliced this thin are not.
-    static const bool on = [] { const char *e = getenv("PCOPS_EDGECONV_BWD_FUSED"); return e && e[0] == '1'; }();
+    static const bool on = pcops_env_switch("PCOPS_EDGECONV_BWD_FUSED", false);
     return on && c % kBwdCh == 0 && m <= 512 * kBwdGP && s <= 255 && ec_codes16_ok(m, s) && ec_bwd_lds_bytes(m, s) <= kLdsMax &&
            n >= 1 && n <= 2048;
 }
@@ -1259,7 +1243,7 @@ extern "C" int pcops_ec_debug_prof(unsigned long long *out8) {
 #endif
 
 bool ec_enabled() {
-    static const bool on = [] { const char *e = getenv("PCOPS_EDGECONV_R5"); return !(e && e[0] == '0'); }();
+    static const bool on = pcops_env_switch("PCOPS_EDGECONV_R5", true);
     return on;
 }
 
@@ -1294,7 +1278,7 @@ int ec_edge_pool_fwd(int b, int n, int m, int s, int c, const float *Q, int ldq,
 
 int ec_gather_fwd(int b, int n, int m, int s, int c, const float *Q, int ldq, const float *Ctr, int ldc, const int *idx,
                   float *Y, float *stats, const float *pivot, bool ld_form, hipStream_t st) {
-    static const bool nt_on = [] { const char *e = getenv("PCOPS_NT_STORE"); return !(e && e[0] == '0'); }();   // kernel A/B only
+    static const bool nt_on = pcops_env_switch("PCOPS_NT_STORE", true);   // kernel A/B only
     FwdArgs a = {b, n, m, s, c, ldq, ldc, Q, Ctr, idx, nullptr, nullptr, nullptr, nullptr, Y, stats, pivot,
                  (nt_on && (long long)b * m * s * c * 4 >= (256ll << 20)) ? 1 : 0};
     const unsigned grid = (unsigned)((long long)b * (c / 64) * (m / kGB));

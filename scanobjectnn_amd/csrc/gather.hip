@@ -150,7 +150,7 @@ __global__ __launch_bounds__(256) void sa_gather_fwd_kernel(long long G, int n, 
                                                             float *__restrict__ moments, int groups_per_block,
                                                             const RowBlock *__restrict__ blocks,
                                                             const int *__restrict__ bstart, int nt) {
-    // nt: Y leaves with non-temporal stores (a stream of 256 MB and more that nothing reads back soon, mlp.hip buf_store4)
+    // nt: Y leaves with non-temporal stores (a stream of 256 MB and more that nothing reads back soon, device.h buf_store4)
     // blocks != NULL: compacted rows -- group g writes its first 16 (bstart[g+1] - bstart[g]) rows to rows
     // 16 bstart[g] ..., and its row 0 enters the statistics / moments with the weight of the copies left out
     extern __shared__ __attribute__((aligned(16))) float sm[];  // [RL][2][C] statistics scratch | staged rows
@@ -232,8 +232,7 @@ __global__ __launch_bounds__(256) void sa_gather_fwd_kernel(long long G, int n, 
                     if (Q) q = *reinterpret_cast<const float4 *>(Q + (b * n + __float_as_int(e.w)) * (long long)C + cq);
                     const float4 y = first_layer_quad(ctr, Q != nullptr, q, Wxyz != nullptr, e.x, e.y, e.z, w0, w1, w2);
                     if (Y) {                                                      // NULL: statistics only
-                        typedef float g_f4 __attribute__((ext_vector_type(4)));
-                        if (nt) __builtin_nontemporal_store(g_f4{y.x, y.y, y.z, y.w}, reinterpret_cast<g_f4 *>(Y + r * C + cq));
+                        if (nt) __builtin_nontemporal_store(f32x4{y.x, y.y, y.z, y.w}, reinterpret_cast<f32x4 *>(Y + r * C + cq));
                         else *reinterpret_cast<float4 *>(Y + r * C + cq) = y;
                     }
                     const float wt = s == 0 ? w0row : 1.f;
@@ -1246,7 +1245,6 @@ __global__ __launch_bounds__(256) void cloud_bias_fwd_kernel(long long rows, int
     const float4 ct = *reinterpret_cast<const float4 *>(Ctr + g * C + cq);
     const float4 pv = pivot ? *reinterpret_cast<const float4 *>(pivot + cq) : make_float4(0.f, 0.f, 0.f, 0.f);
     float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
-    typedef float cb_f4 __attribute__((ext_vector_type(4)));
     for (int i = rl; i < kCloudRows; i += 4 * RL) {
         float4 q[4];
 #pragma unroll
@@ -1259,7 +1257,7 @@ __global__ __launch_bounds__(256) void cloud_bias_fwd_kernel(long long rows, int
             const long long r = r0 + i + u * RL;
             if (!(i + u * RL < kCloudRows && r < rows)) continue;
             const float4 y = make_float4(q[u].x + ct.x, q[u].y + ct.y, q[u].z + ct.z, q[u].w + ct.w);
-            if (nt) __builtin_nontemporal_store(cb_f4{y.x, y.y, y.z, y.w}, reinterpret_cast<cb_f4 *>(Y + r * C + cq));
+            if (nt) __builtin_nontemporal_store(f32x4{y.x, y.y, y.z, y.w}, reinterpret_cast<f32x4 *>(Y + r * C + cq));
             else *reinterpret_cast<float4 *>(Y + r * C + cq) = y;
             const float d[4] = {y.x - pv.x, y.y - pv.y, y.z - pv.z, y.w - pv.w};
 #pragma unroll
@@ -1835,27 +1833,20 @@ __global__ __launch_bounds__(256) void sum_rows_kernel(int P, int L, const float
 
 }  // namespace
 
-// an on/off switch of the environment (its caller reads it once): "0" switches off what is on by default, "1" switches on
-// what is off
-static bool env_switch(const char *name, bool dflt) {
-    const char *e = getenv(name);
-    return dflt ? !(e && e[0] == '0') : (e && e[0] == '1');
-}
-
 static bool scatter_csr_enabled() {
-    static const bool on = env_switch("PCOPS_SCATTER_CSR", true);
+    static const bool on = pcops_env_switch("PCOPS_SCATTER_CSR", true);
     return on;
 }
 
 // owner walk outside deterministic mode: measured 2569 us against 592 us of the chunked form on the SA2 scatter of the
 // headline step (a few low-index points own lists hundreds of rows long and serialise their waves) -- off by default
 static bool scatter_owner_enabled() {
-    static const bool on = env_switch("PCOPS_SCATTER_OWNER", false);
+    static const bool on = pcops_env_switch("PCOPS_SCATTER_OWNER", false);
     return on;
 }
 
 static bool scatter_lds_enabled() {
-    static const bool on = env_switch("PCOPS_SCATTER_LDS", true);
+    static const bool on = pcops_env_switch("PCOPS_SCATTER_LDS", true);
     return on;
 }
 
@@ -2046,7 +2037,7 @@ int pcops_sa_gather_fwd_rows(int b, int n, int m, int s, int c, const float *Q, 
         case GatherFwdPlan::kKernel: break;
     }
     const int rl = 256 / (c / 4);
-    static const bool nt_on = env_switch("PCOPS_NT_STORE", true);   // kernel A/B only
+    static const bool nt_on = pcops_env_switch("PCOPS_NT_STORE", true);   // kernel A/B only
     const size_t staged = (size_t)(s >= 1024 ? s : 1024) * 4;      // floats: (dx, dy, dz, index) per staged row
     const size_t lds = ((size_t)rl * 2 * c + staged) * sizeof(float);
     if (lds > 64 * 1024) return PCOPS_ERR_UNSUPPORTED;
@@ -2322,7 +2313,7 @@ struct EdgeBwdPlan {
     size_t slice_lds;         // modes 1, 3
 };
 static EdgeBwdPlan edge_pool_bwd_plan(int b, int n, int m, int s, int c) {
-    static const bool owner = env_switch("PCOPS_EDGE_BWD_OWNER", true);
+    static const bool owner = pcops_env_switch("PCOPS_EDGE_BWD_OWNER", true);
     const bool det = pcops_get_deterministic() != 0, some = (long long)b * m > 0;
     EdgeBwdPlan pl = {PCOPS_OK, 0, c <= 256 ? c / 4 : 64, (size_t)n * kEdgeSlice * sizeof(float)};
     const bool use_owner = some && c % kEdgeSlice == 0 && (det || (owner && pl.slice_lds <= 160 * 1024));
@@ -2525,7 +2516,7 @@ int pcops_cloud_bias_fwd(long long rows, int rows_per_group, int c, const float 
     PCOPS_REQUIRE_PTR(Q); PCOPS_REQUIRE_PTR(Ctr); PCOPS_REQUIRE_PTR(Y);
     if (!pcops_cloud_bias_supported(rows, rows_per_group, c)) return PCOPS_ERR_UNSUPPORTED;
     if ((reinterpret_cast<uintptr_t>(Q) | reinterpret_cast<uintptr_t>(Ctr) | reinterpret_cast<uintptr_t>(Y)) & 15) return PCOPS_ERR_UNSUPPORTED;
-    static const bool nt_on = env_switch("PCOPS_NT_STORE", true);   // kernel A/B only
+    static const bool nt_on = pcops_env_switch("PCOPS_NT_STORE", true);   // kernel A/B only
     const int rl = 256 / (c / 4);
     hipLaunchKernelGGL(cloud_bias_fwd_kernel, dim3(pcops_cloud_bias_rows(rows)), dim3(256), (size_t)rl * 2 * c * sizeof(float),
                        as_stream(stream), rows, rows_per_group, c, Q, Ctr, Y, stats_partial, stats_partial ? stat_pivot : nullptr,

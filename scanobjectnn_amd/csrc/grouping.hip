@@ -142,7 +142,6 @@ __global__ __launch_bounds__(256) void qbp_kernel(int n, int m, int qpw, QbpArgs
 #pragma unroll
                 for (int w = 0; w < W; ++w) hb[s][w] = 0u;
             if (!full) {
-                typedef float f32x2 __attribute__((ext_vector_type(2)));
                 const f32x2 qx2 = {qx, qx}, qy2 = {qy, qy}, qz2 = {qz, qz};
 #pragma unroll
                 for (int i = 0; i < PL / 2; ++i) {

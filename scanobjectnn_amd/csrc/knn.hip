@@ -120,7 +120,6 @@ int launch_knn_graph(int b, int n, int c, int k, const float *x, int *nn_idx, hi
 //   * each lane keeps a sorted top-KL list in registers: insertion is one v_med3_f32 + one compare + two selects
 //     per slot; the two half-waves of a query (rows r and r+4 interleaved) are merged at the end with a
 //     (distance, index) lexicographic insertion.
-typedef float f32x16k __attribute__((ext_vector_type(16)));
 
 template <int KL>
 struct TopK {
@@ -424,7 +423,7 @@ __global__ __launch_bounds__(256, 2) void knn_mfma_kernel(int n, int c, int k, c
         }
         __syncthreads();
         for (int t = 0; t < (tn + 31) / 32; ++t) {
-            f32x16k acc;
+            f32x16 acc;
 #pragma unroll
             for (int v = 0; v < 16; ++v) acc[v] = 0.f;
             const float *arow = cs + (32 * t + li) * LD + half;
@@ -505,7 +504,6 @@ int launch_knn_mfma(int b, int n, int c, int k, const float *x, int *nn_idx, con
 // Workgroup: 8 waves (two per SIMD) = 256 queries on one candidate chunk; 32 queries per wave, two half-waves per
 // query as in knn_mfma_kernel (shared bound tau2).  c == 64 (DGCNN's feature
 // graphs), k <= 20; everything else takes knn_mfma_kernel.
-typedef _Float16 f16x8k __attribute__((ext_vector_type(8)));
 constexpr int kKnnPD = 32;             // pending survivors per lane; checked once per 32-row tile (<= 16 new entries each)
 // (A, B assume GRADUAL underflow in v_cvt_f16_f32 and in the fp16 MFMA -- a channel below 6.1e-5 keeps its subnormal value.  It
 // holds on gfx950: tests/test_knn_gpu.py "subnormal_mix" builds clouds whose graphs would lose neighbours by five times the
@@ -549,7 +547,7 @@ __global__ __launch_bounds__(512, 2) void knn_f16_kernel(int n, int k, const flo
     float sq = 0.f;
 #pragma unroll
     for (int l = 0; l < CP; ++l) sq = fmaf(xq[l], xq[l], sq);
-    f16x8k bh[CP / 16];
+    f16x8 bh[CP / 16];
 #pragma unroll
     for (int kk = 0; kk < CP / 16; ++kk)
 #pragma unroll
@@ -646,10 +644,9 @@ __global__ __launch_bounds__(512, 2) void knn_f16_kernel(int n, int k, const flo
             const int e4 = tid + 512 * u;
             const int r = e4 / (CP / 4), l = (e4 - r * (CP / 4)) * 4;
             *reinterpret_cast<float4 *>(cs + r * LD + l) = pre[u];
-            typedef _Float16 f16x4k __attribute__((ext_vector_type(4)));
-            f16x4k h;
+            f16x4 h;
             h[0] = (_Float16)pre[u].x; h[1] = (_Float16)pre[u].y; h[2] = (_Float16)pre[u].z; h[3] = (_Float16)pre[u].w;
-            *reinterpret_cast<f16x4k *>(chh + r * LH + l) = h;
+            *reinterpret_cast<f16x4 *>(chh + r * LH + l) = h;
             big |= (int)!(fabsf(pre[u].x) <= kF16Safe) | (int)!(fabsf(pre[u].y) <= kF16Safe) |
                    (int)!(fabsf(pre[u].z) <= kF16Safe) | (int)!(fabsf(pre[u].w) <= kF16Safe);
         }
@@ -669,13 +666,13 @@ __global__ __launch_bounds__(512, 2) void knn_f16_kernel(int n, int k, const flo
         __syncthreads();
         const int ntile = (tn + 31) / 32;
         for (int t = 0; t < ntile; ++t) {
-            f32x16k acc;
+            f32x16 acc;
 #pragma unroll
             for (int v = 0; v < 16; ++v) acc[v] = 0.f;
             const _Float16 *arow = chh + (32 * t + li) * LH + 8 * half;
 #pragma unroll
             for (int kk = 0; kk < CP / 16; ++kk)
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const f16x8k *>(arow + 16 * kk), bh[kk], acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const f16x8 *>(arow + 16 * kk), bh[kk], acc, 0, 0, 0);
             // acc[v]: candidate row 32 t + (v&3) + 8 (v>>2) + 4 half, query li
 #pragma unroll
             for (int g4 = 0; g4 < 4; ++g4) {
@@ -958,7 +955,7 @@ extern "C" int pcops_knn_graph(int b, int n, int c, int k, const float *x, int *
 }
 
 static bool knn_use_mfma() {
-    static const bool on = [] { const char *e = getenv("PCOPS_KNN_MFMA"); return !(e && e[0] == '0'); }();   // kernel A/B only
+    static const bool on = pcops_env_switch("PCOPS_KNN_MFMA", true);   // kernel A/B only
     return on;
 }
 static bool knn_takes_f16(int n, int c, int k, const float *x) {

@@ -29,7 +29,6 @@
 namespace {
 
 constexpr int kThreads = 256;
-typedef float f4 __attribute__((ext_vector_type(4)));
 
 // ------------------------------------------------------------------------------------------------------ representation
 constexpr int kFvRows = 20;
@@ -205,11 +204,11 @@ __global__ void __launch_bounds__(kThreads) conv3d_fwd_kernel(int B, int R, int 
     const int vc = v % R, vb = (v / R) % R, va = v / (R * R), h = ks / 2;
     const int wr = (wave >> 1) * 32, wc = (wave & 1) * 32;
     const bool live = row0 + wr < B && col0 + wc < Cout;     // wave-uniform: a quarter with no row or no column idles
-    f4 acc[2][2];
+    f32x4 acc[2][2];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int jj = 0; jj < 2; ++jj) acc[i][jj] = f4{0.f, 0.f, 0.f, 0.f};
+        for (int jj = 0; jj < 2; ++jj) acc[i][jj] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     for (int ta = max(0, h - va); ta < min(ks, R + h - va); ++ta)
         for (int tb = max(0, h - vb); tb < min(ks, R + h - vb); ++tb)
@@ -296,11 +295,11 @@ __global__ void __launch_bounds__(kThreads) conv3d_wgrad_kernel(int B, int R, in
     const bool do_db = db != nullptr && tap == (ks * ks * ks) / 2 && ci0 == 0;
     const int wr = (wave >> 1) * 32, wc = (wave & 1) * 32;
     const bool live = ci0 + wr < Cin && co0 + wc < Cout;
-    f4 acc[2][2];
+    f32x4 acc[2][2];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int jj = 0; jj < 2; ++jj) acc[i][jj] = f4{0.f, 0.f, 0.f, 0.f};
+        for (int jj = 0; jj < 2; ++jj) acc[i][jj] = f32x4{0.f, 0.f, 0.f, 0.f};
     float dbs = 0.f;
 
     for (int st = sbeg; st < send; ++st) {

@@ -55,38 +55,6 @@
 
 namespace pcops_mlp {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-// fp32 -> three bf16 pieces, x = h + m + l up to 2^-25 |x| (each residual is exact in fp32; round-to-nearest pieces carry
-// their own signs, so 3 x 8 significant bits cover the 24 of the operand; below 2^-100 the residuals turn denormal and the
-// identity holds to an absolute 2^-133 instead).  Products of two pieces are exact in fp32.  (tests/test_split_operands_cpu.py)
-// Written on PAIRS of values (round 6): one v_cvt_pk_bf16_f32 per pair and piece, the widening as shift / mask of the packed word,
-// the residuals as v_pk_add_f32 -- 36 instructions for eight values.  As a loop over single values hipcc paired what it could and
-// left 46 (17 conversions, ten of the sixteen subtractions unpacked); same arithmetic, bit for bit.
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void split3_pair(float a, float b, bf16x2 &h, bf16x2 &m, bf16x2 &l) {
-    const f32x2 v = {a, b};
-    h = __builtin_convertvector(v, bf16x2);
-    const f32x2 r1 = v - __builtin_convertvector(h, f32x2);
-    m = __builtin_convertvector(r1, bf16x2);
-    const f32x2 r2 = r1 - __builtin_convertvector(m, f32x2);
-    l = __builtin_convertvector(r2, bf16x2);
-}
-__device__ __forceinline__ void split3(const float4 &x0, const float4 &x1, bf16x8 &h, bf16x8 &m, bf16x8 &l) {
-    const float x[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        bf16x2 hh, mm, ll;
-        split3_pair(x[2 * p], x[2 * p + 1], hh, mm, ll);
-        h[2 * p] = hh.x; h[2 * p + 1] = hh.y;
-        m[2 * p] = mm.x; m[2 * p + 1] = mm.y;
-        l[2 * p] = ll.x; l[2 * p + 1] = ll.y;
-    }
-}
-
 constexpr int kBM = 128;   // rows per tile (4 waves x 32)
 constexpr int kBK = 32;    // K chunk
 constexpr int kLdA = 36;   // A tile row stride in floats (16 B aligned, conflict-free b128 reads)
@@ -128,37 +96,6 @@ __device__ __forceinline__ float xyz_y(float4 o, float w0, float w1, float w2, f
     return fmaf(o.z, w2, fmaf(o.y, w1, fmaf(o.x, w0, b)));
 }
 
-// ---- buffer-resource addressing (gfx950): ONE 32-bit VGPR offset per lane + a scalar offset per access, and the
-// hardware bounds check (offset >= num_records -> loads return 0, stores are dropped) replaces every row guard.
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void *base, long long bytes) {
-    const unsigned n = bytes <= 0 ? 0u : (bytes > 0xFFFFFFFFll ? 0xFFFFFFFFu : (unsigned)bytes);
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), 0, n, 0x00020000);
-}
-__device__ __forceinline__ float4 buf_load4(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-    // (aux 2 = non-temporal on the streamed operand reads: SSG 23.05 vs 23.05 k, DGCNN 9.85 vs 9.85 k -- nothing; stores: see buf_store4)
-    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0);
-    return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
-}
-// nt: non-temporal (aux bit 1 on gfx94x / gfx950): the output is a stream far larger than the L2 and the memory-side cache
-// that nothing reads back soon -- not allocating its lines measured 7 % on a pure 2.7 GB write stream (edgeconv.hip MODE 1)
-__device__ __forceinline__ void buf_store4(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff, float4 x, bool nt = false) {
-    u32x4 v;
-    v.x = __float_as_uint(x.x); v.y = __float_as_uint(x.y); v.z = __float_as_uint(x.z); v.w = __float_as_uint(x.w);
-    if (nt) __builtin_amdgcn_raw_buffer_store_b128(v, r, voff, soff, 2);
-    else __builtin_amdgcn_raw_buffer_store_b128(v, r, voff, soff, 0);
-    // gfx950 store-data hazard hipcc does not pad: a VALU write to the data registers of a 16-byte buffer store in the
-    // very next issue slot still reaches the store (observed: the .w word of the last four lanes of every 16-lane group
-    // took the NEXT row's value whenever a v_pk_add_f32 rewrote v[n+2:n+3] right behind the store).  LLVM's recogniser
-    // only pads MUBUF stores WITHOUT an SGPR soffset; these use one.  The statement below reads the four registers, so
-    // nothing can be allocated into them before it, and it carries the wait states itself.  (Round 2 met the same
-    // corruption when it unrolled the MFMA loop and put it down to a code-generation accident.)
-    asm volatile("s_nop 1" ::"v"(v.x), "v"(v.y), "v"(v.z), "v"(v.w) : "memory");
-}
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc_u32(const void *base, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), 0, bytes, 0x00020000);
-}
-constexpr unsigned kOOB = 0x7FFFFFF0u;   // a voffset no tensor reaches: forces the bounds check to fail
 enum EMode { E_FWD = 0, E_MASK = 1, E_PLAIN = 2, E_MASKX = 3, E_MASKA = 4 };
 // E_MASKX: E_MASK with the previous layer in xyz form
 // E_MASKA: E_MASK of  acc + addend[rowmap[row]] + vconst  -- the data gradient of a POOLED top layer in its algebraic
@@ -630,8 +567,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void gemm_ws_kernel(GemmArgs
             for (int j = 0; j < FPB; ++j)
 #pragma unroll
                 for (int e = 0; e < 8; ++e)
-                    wfr[8 * j + e] = __uint_as_float(
-                        __builtin_amdgcn_raw_buffer_load_b32(rw, wfoff[j], cbase + (unsigned)e * (unsigned)N * 4u, 0));
+                    wfr[8 * j + e] = __uint_as_float(buf_load1(rw, wfoff[j], cbase + (unsigned)e * (unsigned)N * 4u));
             return;
         }
 #pragma unroll
@@ -1590,7 +1526,7 @@ static int ws_bf3_mode() { return pcops_get_option(PCOPS_OPT_GEMM_SPLIT_BF16); }
 // for K >= 128 dY columns, 2: 128-column passes where the weight pieces fit (kernel A/B)
 static int dgrad_bf3_mode() { return pcops_get_option(PCOPS_OPT_DGRAD_SPLIT_BF16); }
 static int dgrad_bf3_kmin() {
-    static const int v = [] { const char *e = getenv("PCOPS_DGRAD_BF3_KMIN"); return e ? atoi(e) : 128; }();
+    static const int v = pcops_env_int("PCOPS_DGRAD_BF3_KMIN", 128);
     return v;
 }
 
@@ -1609,23 +1545,17 @@ static size_t ws_lds_bytes(int Kp, int kc, int bn, int waves, int eh) {
 }
 
 static bool ws_stream256_enabled() {
-    static const bool on = [] {
-        const char *e = getenv("PCOPS_WS_STREAM256");
-        return !(e && e[0] == '0');
-    }();
+    static const bool on = pcops_env_switch("PCOPS_WS_STREAM256", true);
     return on;
 }
 
 static bool ws_mask_bn64_enabled() {
-    static const bool on = [] { const char *e = getenv("PCOPS_WS_MASK_BN64"); return !(e && e[0] == '0'); }();   // kernel A/B only
+    static const bool on = pcops_env_switch("PCOPS_WS_MASK_BN64", true);   // kernel A/B only
     return on;
 }
 
 static bool ws_n96_enabled() {
-    static const bool on = [] {
-        const char *e = getenv("PCOPS_WS_N96");
-        return !(e && e[0] == '0');
-    }();
+    static const bool on = pcops_env_switch("PCOPS_WS_N96", true);
     return on;
 }
 
@@ -1636,10 +1566,7 @@ static bool ws_n96_enabled() {
 // 32 + 32 accumulator registers, and the weight pieces of 64 columns stay RESIDENT up to K = 256 (96 KB): no streaming, no
 // workgroup barrier; the two column blocks of a row group run on one XCD, so the second reader of a dY stripe hits its L2
 static int dgrad_top_bf3_cols() {
-    static const int v = [] {
-        const char *e = getenv("PCOPS_DGRAD_TOP_BF3");
-        return e ? atoi(e) : 128;
-    }();
+    static const int v = pcops_env_int("PCOPS_DGRAD_TOP_BF3", 128);
     return v;
 }
 // what ws_plan is asked for: 1 forward, 2 masked data gradient, 3 its xyz form, 4 / 5 the algebraic top-layer forms (masked / plain)
@@ -1683,8 +1610,8 @@ static bool ws_plan(const GemmArgs &a, int am, WsPlan *pl, int kind = 0) {
         pl->lds = ws_lds_bytes(Kp, pl->kc, pl->bn, pl->waves, pl->eh);
     }
     pl->bf3 = false;
-    static const int bf3_kmin = [] { const char *e = getenv("PCOPS_GEMM_BF3_KMIN"); return e ? atoi(e) : 0; }();
-    static const int bf3_kmax = [] { const char *e = getenv("PCOPS_GEMM_BF3_KMAX"); return e ? atoi(e) : 1 << 30; }();
+    static const int bf3_kmin = pcops_env_int("PCOPS_GEMM_BF3_KMIN", 0);
+    static const int bf3_kmax = pcops_env_int("PCOPS_GEMM_BF3_KMAX", 1 << 30);
     if (fwd && ws_bf3_mode() && !(reinterpret_cast<uintptr_t>(a.W) & 3) && a.K >= bf3_kmin && a.K <= bf3_kmax) {
         const int Kp3 = (a.K + 31) / 32 * 32;
         const int nc = ws_ncoef(am);
@@ -1747,7 +1674,7 @@ static bool ws_plan(const GemmArgs &a, int am, WsPlan *pl, int kind = 0) {
 }
 
 static bool nt_stores_enabled() {
-    static const bool on = [] { const char *e = getenv("PCOPS_NT_STORE"); return !(e && e[0] == '0'); }();   // kernel A/B only
+    static const bool on = pcops_env_switch("PCOPS_NT_STORE", true);   // kernel A/B only
     return on;
 }
 static int nt_for_bytes(long long bytes) { return (nt_stores_enabled() && bytes >= (256ll << 20)) ? 1 : 0; }
@@ -1764,7 +1691,7 @@ constexpr int ws_var(int wp, int base) {
 
 // PCOPS_POOL_FWD_ACC_STATS=0 (read once): the pooled forward without Y keeps the transposing kernel (kernel A/B; same bits)
 static bool pool_fwd_acc_stats_enabled() {
-    static const bool on = [] { const char *e = getenv("PCOPS_POOL_FWD_ACC_STATS"); return !(e && e[0] == '0'); }();
+    static const bool on = pcops_env_switch("PCOPS_POOL_FWD_ACC_STATS", true);
     return on;
 }
 
@@ -1871,10 +1798,7 @@ PCOPS_X_ int launch_gemm_ws<A_XYZ, E_FWD>(GemmArgs &, const WsPlan &, hipStream_
 extern "C" int pcops_mlp_stats_rows(int M);
 
 static bool ws_enabled() {
-    static const bool on = [] {
-        const char *e = getenv("PCOPS_GEMM_WS");
-        return !(e && e[0] == '0');
-    }();
+    static const bool on = pcops_env_switch("PCOPS_GEMM_WS", true);
     return on;
 }
 
@@ -3002,7 +2926,6 @@ __global__ __launch_bounds__(512, (TK * TN == 1) ? 2 : 1) void wgrad_pc_kernel(W
 //               the end (the large accumulator is then rounded once per 16 rows instead of once per 2: a long reduction
 //               -- 8 192 rows per workgroup at SA2's size -- is where that matters most).
 // Tile 128 x 128 (K or N beyond: more workgroups along y / z; the other operand is then read once per block).
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ void split3x4(float v0, float v1, float v2, float v3, bf16x4 &h, bf16x4 &m, bf16x4 &l) {
     const float x[4] = {v0, v1, v2, v3};
@@ -3639,31 +3562,28 @@ __global__ __launch_bounds__(512, 1) void bwd_fused_kernel(WgradArgs a) {
                     for (int i = 0; i < RW; ++i) { rh[i][e] = h[i]; rm[i][e] = m[i]; rl[i][e] = l[i]; }
                 }
                 if constexpr (RW == 4) {
-                    typedef __bf16 bf16x4_ __attribute__((ext_vector_type(4)));
-                    bf16x4_ hv = {h[0], h[1], h[2], h[3]}, mv = {m[0], m[1], m[2], m[3]}, lv = {l[0], l[1], l[2], l[3]};
-                    *reinterpret_cast<bf16x4_ *>(dstp) = hv;
-                    *reinterpret_cast<bf16x4_ *>(dstp + SLOTS * RSP) = mv;
-                    *reinterpret_cast<bf16x4_ *>(dstp + 2 * SLOTS * RSP) = lv;
+                    bf16x4 hv = {h[0], h[1], h[2], h[3]}, mv = {m[0], m[1], m[2], m[3]}, lv = {l[0], l[1], l[2], l[3]};
+                    *reinterpret_cast<bf16x4 *>(dstp) = hv;
+                    *reinterpret_cast<bf16x4 *>(dstp + SLOTS * RSP) = mv;
+                    *reinterpret_cast<bf16x4 *>(dstp + 2 * SLOTS * RSP) = lv;
                 } else {
-                    typedef __bf16 bf16x2_ __attribute__((ext_vector_type(2)));
                     static_assert(RW == 2, "two or four consecutive rows per lane");
-                    bf16x2_ hv = {h[0], h[1]}, mv = {m[0], m[1]}, lv = {l[0], l[1]};
-                    *reinterpret_cast<bf16x2_ *>(dstp) = hv;
-                    *reinterpret_cast<bf16x2_ *>(dstp + SLOTS * RSP) = mv;
-                    *reinterpret_cast<bf16x2_ *>(dstp + 2 * SLOTS * RSP) = lv;
+                    bf16x2 hv = {h[0], h[1]}, mv = {m[0], m[1]}, lv = {l[0], l[1]};
+                    *reinterpret_cast<bf16x2 *>(dstp) = hv;
+                    *reinterpret_cast<bf16x2 *>(dstp + SLOTS * RSP) = mv;
+                    *reinterpret_cast<bf16x2 *>(dstp + 2 * SLOTS * RSP) = lv;
                 }
             }
             if constexpr (RM) {
                 if (rb) {                                      // (the dY operand only)
-                    typedef __bf16 bf16x4r __attribute__((ext_vector_type(4)));
 #pragma unroll
                     for (int i = 0; i < RW; ++i) {
                         __bf16 *dr = rb + (r0 + i) * RLD + 4 * cq;
-                        const bf16x4r hv = {rh[i][0], rh[i][1], rh[i][2], rh[i][3]}, mv = {rm[i][0], rm[i][1], rm[i][2], rm[i][3]},
+                        const bf16x4 hv = {rh[i][0], rh[i][1], rh[i][2], rh[i][3]}, mv = {rm[i][0], rm[i][1], rm[i][2], rm[i][3]},
                                       lv = {rl[i][0], rl[i][1], rl[i][2], rl[i][3]};
-                        *reinterpret_cast<bf16x4r *>(dr) = hv;
-                        *reinterpret_cast<bf16x4r *>(dr + RS * RLD) = mv;
-                        *reinterpret_cast<bf16x4r *>(dr + 2 * RS * RLD) = lv;
+                        *reinterpret_cast<bf16x4 *>(dr) = hv;
+                        *reinterpret_cast<bf16x4 *>(dr + RS * RLD) = mv;
+                        *reinterpret_cast<bf16x4 *>(dr + 2 * RS * RLD) = lv;
                     }
                 }
             }
@@ -4500,7 +4420,6 @@ __global__ __launch_bounds__(512, 1) void gram_rows_bf3_kernel(GramArgs a) {
                 }
                 xt[j] = x;
             }
-            typedef __bf16 bf16x4_ __attribute__((ext_vector_type(4)));
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const float v0 = e == 0 ? xt[0].x : (e == 1 ? xt[0].y : (e == 2 ? xt[0].z : xt[0].w));
@@ -4511,10 +4430,10 @@ __global__ __launch_bounds__(512, 1) void gram_rows_bf3_kernel(GramArgs a) {
                 split3_pair(v0, v1, h0, m0, l0);
                 split3_pair(v2, v3, h1, m1, l1);
                 __bf16 *d = dst + (32 * e + (c >> 2)) * RSP + 4 * r0;
-                const bf16x4_ hv = {h0.x, h0.y, h1.x, h1.y}, mv = {m0.x, m0.y, m1.x, m1.y}, lv = {l0.x, l0.y, l1.x, l1.y};
-                *reinterpret_cast<bf16x4_ *>(d) = hv;
-                *reinterpret_cast<bf16x4_ *>(d + PSZ) = mv;
-                *reinterpret_cast<bf16x4_ *>(d + 2 * PSZ) = lv;
+                const bf16x4 hv = {h0.x, h0.y, h1.x, h1.y}, mv = {m0.x, m0.y, m1.x, m1.y}, lv = {l0.x, l0.y, l1.x, l1.y};
+                *reinterpret_cast<bf16x4 *>(d) = hv;
+                *reinterpret_cast<bf16x4 *>(d + PSZ) = mv;
+                *reinterpret_cast<bf16x4 *>(d + 2 * PSZ) = lv;
             }
         };
         // a stripe beyond the last one gets a descriptor of zero records (make_rsrc): its loads fetch nothing and return
@@ -4629,10 +4548,7 @@ static __global__ __launch_bounds__(256) void mirror_lower_kernel(int K, float *
 }
 
 static bool gram_full_on() {
-    static const bool on = [] {
-        const char *e = getenv("PCOPS_GRAM_FULL");
-        return !(e && e[0] == '0');
-    }();
+    static const bool on = pcops_env_switch("PCOPS_GRAM_FULL", true);
     return on;
 }
 
@@ -4649,17 +4565,11 @@ struct WgradPlan {
 };
 
 static bool wgrad_k96_enabled() {
-    static const bool on = [] {
-        const char *e = getenv("PCOPS_WGRAD_K96");
-        return !(e && e[0] == '0');
-    }();
+    static const bool on = pcops_env_switch("PCOPS_WGRAD_K96", true);
     return on;
 }
 static bool wgrad_pc_enabled() {
-    static const bool on = [] {
-        const char *e = getenv("PCOPS_WGRAD_PC");
-        return !(e && e[0] == '0');
-    }();
+    static const bool on = pcops_env_switch("PCOPS_WGRAD_PC", true);
     return on;
 }
 
@@ -4716,7 +4626,7 @@ static bool wgrad_bf3_plan(const WgradArgs &a, WgradPlan *pl) {
     if (!on || a.M < 32768 || a.K <= 64 || a.N <= 64 || !wgrad_operands_ok(a)) return false;
     pl->groups = clamp_groups(wgrad_bf3_tile(a.K, a.N, pl), (a.M + 31) / 32);
     // 65 .. 96 input channels behind a BN + ReLU (MSG's 96 -> 128): the 96 x 32 consumer layout (PCOPS_WGRAD_BF3_K96=0: off)
-    static const bool k96_on = [] { const char *e = getenv("PCOPS_WGRAD_BF3_K96"); return !(e && e[0] == '0'); }();
+    static const bool k96_on = pcops_env_switch("PCOPS_WGRAD_BF3_K96", true);
     pl->k96 = k96_on && a.K <= 96 && a.amode == A_BNRELU;
     return true;
 }
@@ -5906,10 +5816,7 @@ int wgrad_impl(WgradArgs &a, float *partial, float *dW, float *db, hipStream_t s
 
 #if PCOPS_PART(5)
 static bool nsk_on() {
-    static const bool on = [] {
-        const char *e = getenv("PCOPS_BWD_FUSED_NSKIP");
-        return !(e && e[0] == '0');
-    }();
+    static const bool on = pcops_env_switch("PCOPS_BWD_FUSED_NSKIP", true);
     return on;
 }
 
@@ -5989,7 +5896,7 @@ int bwd_fused_launch(WgradArgs &a, bool xyz, int groups, float *partial, float *
                      bool side, const float *gw_bias) {
     const int K = a.K, N = a.N;
 #ifdef PCOPS_BF_DEBUG
-    { const char *e = getenv("PCOPS_BF_DEBUG"); a.rows_per_block = e ? atoi(e) : 0; }      // tools/ablate_bwd_fused.py
+    a.rows_per_block = pcops_env_int("PCOPS_BF_DEBUG", 0);      // tools/ablate_bwd_fused.py
 #endif
     a.part = partial; a.dbpart = db ? partial + (long long)groups * K * N : nullptr;
     const BwdFusedPlan pl = bwd_fused_plan(a, xyz, side);
@@ -6119,7 +6026,7 @@ static int pool_s4_sub(int S) {
     return l / 32;
 }
 static bool pool_s4_enabled() {
-    static const bool on = [] { const char *e = getenv("PCOPS_POOL_S4"); return !(e && e[0] == '0'); }();   // kernel A/B only
+    static const bool on = pcops_env_switch("PCOPS_POOL_S4", true);   // kernel A/B only
     return on;
 }
 static void set_pool_group(GemmArgs &a, int S) {
@@ -6532,10 +6439,7 @@ int pcops_gather_stack_rows_supported(int b, int n, int m, int s, int has_q, int
 
 static int bwd_fused_groups(long long M, int K, int N, int S, int pooled) {
     if (!ws_enabled() || !wgrad_pc_enabled()) return 0;
-    static const bool on = [] {
-        const char *e = getenv("PCOPS_BWD_FUSED");
-        return !(e && e[0] == '0');
-    }();
+    static const bool on = pcops_env_switch("PCOPS_BWD_FUSED", true);
     if (!on) return 0;
     // the bandwidth-bound 64-wide layers only: wider ones are matrix-pipe bound in both kernels and gain nothing
     if (M < 65536 || M > 0x7fffff00ll || K > 64 || K % 4 != 0 || N > 128 || N % 4 != 0) return 0;

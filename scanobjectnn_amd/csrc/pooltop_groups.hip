@@ -18,14 +18,11 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int KP = 64;            // input width of the layer (the only one these kernels are built for)
 constexpr int TR = 64;            // rows per tile: two groups of 32 or one of 64
 constexpr int XLD = KP + 4;       // row stride of a staged tile in floats: 16-byte reads of whole rows without bank conflicts
 constexpr int NMAX = 256;         // widest layer
 constexpr int MW = NMAX / 32;     // mask words per row
-constexpr unsigned kOOB32 = 0x7FFFFFF0u;      // the 32-bit byte bound the other pool-top calls keep (mlp.hip kOOB)
 constexpr int kMaxGrid = 512;
 
 // what a thread holds of a tile between its request and its use: its four float4 of Yprev and the (group, channel) triples
@@ -244,7 +241,7 @@ __global__ __launch_bounds__(256) void dgrad_top_groups_kernel(long long M, int 
 // ------------------------------------------------------------------------------------------------ data gradient, N = 128
 // The same tile loop with the tile's addend as ONE product on the 16-bit matrix pipe: addend = P W^T, P [64][N] with
 // P[r][c] = cf[g(r)][c] where argmax[g(r)][c] == r, else 0.  Its cost is fixed -- it does not depend on how the hits are spread
-// over the rows -- where the walk above is serial in a row's hits.  Split operands (mlp.hip split3: x = h + m + l in bf16
+// over the rows -- where the walk above is serial in a row's hits.  Split operands (device.h split3_pair: x = h + m + l in bf16
 // pieces), six products hh | lh, mh, mm, hm, hl on v_mfma_f32_32x32x16_bf16, large and small terms in separate accumulators.
 //   B  W^T's pieces as ready fragments in LDS, split once per workgroup: [piece][k-step][column block][lane] x 8 bf16 (48 KB)
 //   A  built in registers: the triple owners store cf pre-split (three bf16 arrays) and the arg-max bytes per (group, channel);
@@ -254,24 +251,8 @@ __global__ __launch_bounds__(256) void dgrad_top_groups_kernel(long long M, int 
 // The wave that owns a 32 x 32 block holds X Mq and the addend in the same accumulator layout and writes (acc + v) + addend
 // into the tile image that held X (one more barrier; a thread's epilogue reads exactly the floats its next staging overwrites).
 // LDS 78.5 KB: two workgroups per CU.  N = 128 is the only width <= 128 the *_groups forms take (N >= 2 Kp).
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int NM = 128;           // the width of the matrix form
 constexpr int NKS = NM / 16;      // its k-steps
-
-// two fp32 values as three packed bf16 pairs (the arithmetic of mlp.hip's split3_pair)
-__device__ __forceinline__ void split3_pair(float a, float b, unsigned &h, unsigned &m, unsigned &l) {
-    const f32x2 v = {a, b};
-    const bf16x2 hh = __builtin_convertvector(v, bf16x2);
-    const f32x2 r1 = v - __builtin_convertvector(hh, f32x2);
-    const bf16x2 mm = __builtin_convertvector(r1, bf16x2);
-    const f32x2 r2 = r1 - __builtin_convertvector(mm, f32x2);
-    const bf16x2 ll = __builtin_convertvector(r2, bf16x2);
-    h = __builtin_bit_cast(unsigned, hh); m = __builtin_bit_cast(unsigned, mm); l = __builtin_bit_cast(unsigned, ll);
-}
 
 // Four arg-max bytes XORed with the lane's row (every byte < 128: the staged arg-max is clamped to 127, a row is < 64) -> 0xff
 // in the bytes that are zero, four bytes at a time: (x | 0x80) - 1 keeps bit 7 of a byte unless the byte was zero and never
@@ -615,7 +596,7 @@ __global__ __launch_bounds__(1024) void groups_sum_kernel(int P, int L, int N, c
 // what the kernels themselves take (the planner's answer adds a floor on M)
 bool groups_shape_ok(long long M, int Kp, int N, int S) {
     return Kp == KP && N % 32 == 0 && N >= 64 && N <= NMAX && N >= 2 * Kp && (S == 32 || S == 64) && M >= S && M % S == 0 &&
-           M * Kp * 4 < (long long)kOOB32;
+           M * Kp * 4 < (long long)kOOB;
 }
 
 int groups_grid(long long M) {
@@ -659,7 +640,7 @@ int pcops_mlp_dgrad_top_groups(int M, int Kp, int N, int S, const float *Yprev, 
     const int grid = pcops_mlp_stats_rows(M);
     if (grid < 1 || grid > kMaxGrid || grid > (M + TR - 1) / TR) return PCOPS_ERR_UNSUPPORTED;
     // PCOPS_POOL_TOP_GROUPS_MM = 1 (default): N = 128 takes the addend as a product on the 16-bit matrix pipe; 0: the walk
-    static const bool mm_on = [] { const char *e = getenv("PCOPS_POOL_TOP_GROUPS_MM"); return !(e && e[0] == '0'); }();   // kernel A/B only
+    static const bool mm_on = pcops_env_switch("PCOPS_POOL_TOP_GROUPS_MM", true);   // kernel A/B only
     if (mm_on && N == NM) {
         const size_t lds = (size_t)(3 * NKS * 2 * 64 * 4 + TR * XLD + 3 * KP + 3 * NMAX) * sizeof(float) + 3 * 2 * NM * 2 + 2 * NM +
                            4 * 2 * 64 * 16;

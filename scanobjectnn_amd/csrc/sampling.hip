@@ -75,7 +75,6 @@ __global__ __launch_bounds__(T) void fps_kernel(int n, int m, const float *__res
         } else {
             x1 = p[old * 3 + 0]; y1 = p[old * 3 + 1]; z1 = p[old * 3 + 2];
         }
-        typedef float f32x2 __attribute__((ext_vector_type(2)));
         unsigned hi = 0u;
         if (P >= 2) {
             const f32x2 qx = {x1, x1}, qy = {y1, y1}, qz = {z1, z1};

@@ -25,7 +25,6 @@ constexpr int kBN = 64;        // output columns per tile
 constexpr int kThreads = 256;
 constexpr int kTaylorBlocks = 256;   // partial rows of the dtheta reduction
 
-typedef float f4 __attribute__((ext_vector_type(4)));
 
 // phi_m(d), m in the order x y z xyz | xy yz xz | xx yy zz | xxy xyy xxz | xzz yyz yzz | xxx yyy zzz
 __device__ __forceinline__ void monomials(float X, float Y, float Z, float *ph) {
@@ -116,11 +115,11 @@ __global__ void __launch_bounds__(kThreads) conv_fwd_kernel(int n, int C, int k,
     const int row0 = blockIdx.x * kBM, col0 = blockIdx.y * kBN, cloud = blockIdx.z;
     const size_t cbase = (size_t)cloud * n;
     const int wr = (wave >> 1) * 32, wc = (wave & 1) * 32;
-    f4 acc[2][2];
+    f32x4 acc[2][2];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int jj = 0; jj < 2; ++jj) acc[i][jj] = f4{0.f, 0.f, 0.f, 0.f};
+        for (int jj = 0; jj < 2; ++jj) acc[i][jj] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     for (int j = 0; j < k; ++j) {
         __syncthreads();
@@ -199,9 +198,9 @@ __global__ void __launch_bounds__(kThreads) conv_wgrad_kernel(int P, int n, int 
     const int col0 = blockIdx.y * kBN, split = blockIdx.z;
     const int pbeg = split * chunk, pend = min(P, pbeg + chunk);
     const bool do_db = db != nullptr && blockIdx.x == 0;
-    f4 acc[5];
+    f32x4 acc[5];
 #pragma unroll
-    for (int mi = 0; mi < 5; ++mi) acc[mi] = f4{0.f, 0.f, 0.f, 0.f};
+    for (int mi = 0; mi < 5; ++mi) acc[mi] = f32x4{0.f, 0.f, 0.f, 0.f};
     float dbs = 0.f;
 
     for (int p0 = pbeg; p0 < pend; p0 += kBM) {
@@ -291,9 +290,9 @@ __global__ void __launch_bounds__(kThreads) conv_dgrad_kernel(int n, int C, int 
     }
     float dgacc[2] = {0.f, 0.f};     // entries e = tid, tid + 256 of the (64 x 5) dg tile
     for (int c0 = 0; c0 < C; c0 += kCB) {
-        f4 acc[5];
+        f32x4 acc[5];
 #pragma unroll
-        for (int mi = 0; mi < 5; ++mi) acc[mi] = f4{0.f, 0.f, 0.f, 0.f};
+        for (int mi = 0; mi < 5; ++mi) acc[mi] = f32x4{0.f, 0.f, 0.f, 0.f};
         const size_t wrow0 = ((size_t)j * C + c0) * kT;
         for (int o0 = 0; o0 < O; o0 += kBN) {
             __syncthreads();

@@ -30,13 +30,12 @@ constexpr int kPT = 64;           // backward: points per step (one 16-point til
 constexpr int kSplitCap = 16;     // backward: splits per cloud (a power of two)
 constexpr int kTargetWGs = 512;
 
-typedef float f4 __attribute__((ext_vector_type(4)));
 
 // M (64, 64) row-major -> LDS [64][68]
 __device__ __forceinline__ void stage_plain(const float *__restrict__ M, float *S) {
     for (int e = threadIdx.x; e < kK * kK / 4; e += kThreads) {
         const int i = e >> 4, j = (e & 15) * 4;
-        *reinterpret_cast<f4 *>(S + i * kLd + j) = reinterpret_cast<const f4 *>(M)[e];
+        *reinterpret_cast<f32x4 *>(S + i * kLd + j) = reinterpret_cast<const f32x4 *>(M)[e];
     }
 }
 
@@ -46,21 +45,21 @@ __device__ __forceinline__ void stage_transposed(const float *__restrict__ M, fl
 }
 
 // row p of a (n, 64) cloud as this lane's four 16-byte pieces: a[jj] = row[16 jj + 4 g .. + 3]; zeros past n
-__device__ __forceinline__ void load_row(const float *__restrict__ cloud, int p, int n, int g, f4 a[4]) {
+__device__ __forceinline__ void load_row(const float *__restrict__ cloud, int p, int n, int g, f32x4 a[4]) {
     if (p < n) {
-        const f4 *r = reinterpret_cast<const f4 *>(cloud + (size_t)p * kK);
+        const f32x4 *r = reinterpret_cast<const f32x4 *>(cloud + (size_t)p * kK);
 #pragma unroll
         for (int jj = 0; jj < 4; ++jj) a[jj] = r[4 * jj + g];
     } else {
 #pragma unroll
-        for (int jj = 0; jj < 4; ++jj) a[jj] = f4{0.f, 0.f, 0.f, 0.f};
+        for (int jj = 0; jj < 4; ++jj) a[jj] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
 }
 
 // acc[t][r] = sum_k row(l15)[k] M[k][16 t + l15] for the 16 rows the wave's lanes hold (D row = 4 g + r); M in LDS, stride 68
-__device__ __forceinline__ void rows_times(const f4 a[4], const float *M, int g, int l15, f4 acc[4]) {
+__device__ __forceinline__ void rows_times(const f32x4 a[4], const float *M, int g, int l15, f32x4 acc[4]) {
 #pragma unroll
-    for (int t = 0; t < 4; ++t) acc[t] = f4{0.f, 0.f, 0.f, 0.f};
+    for (int t = 0; t < 4; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int jj = 0; jj < 4; ++jj) {
 #pragma unroll
@@ -73,7 +72,7 @@ __device__ __forceinline__ void rows_times(const f4 a[4], const float *M, int g,
 }
 
 // the 16 x 64 tile of rows p0 .. p0 + 15 of a (n, 64) cloud from its D layout
-__device__ __forceinline__ void store_rows(float *__restrict__ cloud, int p0, int n, int g, int l15, const f4 acc[4]) {
+__device__ __forceinline__ void store_rows(float *__restrict__ cloud, int p0, int n, int g, int l15, const f32x4 acc[4]) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int p = p0 + 4 * g + r;
@@ -97,7 +96,7 @@ __global__ void __launch_bounds__(kThreads) transformk_fwd_kernel(int n, const f
     for (int tile = wave; tile < kFwdPoints / 16; tile += kWaves) {
         const int p0 = blockIdx.x * kFwdPoints + tile * 16;
         if (p0 >= n) break;
-        f4 a[4], acc[4];
+        f32x4 a[4], acc[4];
         load_row(Xc, p0 + l15, n, g, a);
         rows_times(a, Ts, g, l15, acc);
         store_rows(Oc, p0, n, g, l15, acc);
@@ -124,23 +123,23 @@ __global__ void __launch_bounds__(kThreads) transformk_bwd_kernel(int n, int chu
         __syncthreads();
     }
     const float *Xc = X + cloud * n * kK, *Gc = G + cloud * n * kK;
-    f4 accT[4];
+    f32x4 accT[4];
 #pragma unroll
-    for (int t = 0; t < 4; ++t) accT[t] = f4{0.f, 0.f, 0.f, 0.f};
+    for (int t = 0; t < 4; ++t) accT[t] = f32x4{0.f, 0.f, 0.f, 0.f};
     for (int p0 = pbeg; p0 < pend; p0 += kPT) {
         const int pw = p0 + 16 * wave;
-        f4 xr[4], gr[4];
+        f32x4 xr[4], gr[4];
         load_row(Xc, pw + l15, pend, g, xr);
         load_row(Gc, pw + l15, pend, g, gr);
         float *xs = Xs + (16 * wave + l15) * kTileLd + 4 * g, *gs = Gs + (16 * wave + l15) * kTileLd + 4 * g;
 #pragma unroll
         for (int jj = 0; jj < 4; ++jj) {
-            *reinterpret_cast<f4 *>(xs + 16 * jj) = xr[jj];
-            *reinterpret_cast<f4 *>(gs + 16 * jj) = gr[jj];
+            *reinterpret_cast<f32x4 *>(xs + 16 * jj) = xr[jj];
+            *reinterpret_cast<f32x4 *>(gs + 16 * jj) = gr[jj];
         }
         if constexpr (DX) {
             if (pw < pend) {
-                f4 acc[4];
+                f32x4 acc[4];
                 rows_times(gr, Tt, g, l15, acc);
                 store_rows(dX + cloud * n * kK, pw, pend, g, l15, acc);
             }
@@ -173,14 +172,14 @@ __global__ void __launch_bounds__(kThreads) transformk_reduce_kernel(long long l
     if (i >= len4) return;
     constexpr int kM4 = kK * kK / 4;
     const long long cloud = i / kM4, e = i - cloud * kM4;
-    const f4 *src = reinterpret_cast<const f4 *>(ws) + cloud * SPLITS * kM4 + e;
-    f4 part[SPLITS];
+    const f32x4 *src = reinterpret_cast<const f32x4 *>(ws) + cloud * SPLITS * kM4 + e;
+    f32x4 part[SPLITS];
 #pragma unroll
     for (int z = 0; z < SPLITS; ++z) part[z] = src[(size_t)z * kM4];
-    f4 v = {0.f, 0.f, 0.f, 0.f};
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int z = 0; z < SPLITS; ++z) v += part[z];
-    reinterpret_cast<f4 *>(dT)[i] = v;
+    reinterpret_cast<f32x4 *>(dT)[i] = v;
 }
 
 // ------------------------------------------------------------------------------------------------------------ regulariser
@@ -198,9 +197,9 @@ __global__ void __launch_bounds__(kThreads) ortho_reg_kernel(const float *__rest
     stage_plain(T + cloud * kK * kK, Ts);
     stage_transposed(T + cloud * kK * kK, Tt);
     __syncthreads();
-    f4 acc[4];
+    f32x4 acc[4];
 #pragma unroll
-    for (int t = 0; t < 4; ++t) acc[t] = f4{0.f, 0.f, 0.f, 0.f};
+    for (int t = 0; t < 4; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll 4
     for (int s = 0; s < kK / 4; ++s) {
         const float *row = Tt + (4 * s + g) * kLd + l15;
@@ -224,7 +223,7 @@ __global__ void __launch_bounds__(kThreads) ortho_reg_kernel(const float *__rest
     __syncthreads();
     if (threadIdx.x == 0) loss_parts[cloud] = weight * 0.5f * (((red[0] + red[1]) + red[2]) + red[3]);
 #pragma unroll
-    for (int t = 0; t < 4; ++t) acc[t] = f4{0.f, 0.f, 0.f, 0.f};
+    for (int t = 0; t < 4; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll 4
     for (int s = 0; s < kK / 4; ++s) {
         const int i2 = 4 * s + g;

@@ -46,7 +46,6 @@ constexpr int kTargetWGs = 512;
 constexpr int kOneGroupTiles = 16;  // forward / dgrad: up to this many channel tiles (c <= 256) one group walks them all
 constexpr int kGroupTiles = 8;      // ... beyond it ceil(tiles / 8) groups of at most 8 tiles
 
-typedef float f4 __attribute__((ext_vector_type(4)));
 
 struct Shape {
     int n, p, K, c1, c2, c, cd;   // points per cloud, representatives per cloud, neighbours, channels, c dm
@@ -98,10 +97,10 @@ __device__ __forceinline__ float load_x(const Shape &s, long long q, int kp, int
 }
 
 // T[k' = 4 g + reg][ch = c0 + l15] of point q; xa[j] = X[k' = l15][k = 4 j + g]
-__device__ __forceinline__ f4 xfin_tile(const Shape &s, long long q, int c0, int g, int l15, const float *xa,
+__device__ __forceinline__ f32x4 xfin_tile(const Shape &s, long long q, int c0, int g, int l15, const float *xa,
                                         const float *__restrict__ lifted, const float *__restrict__ fts,
                                         const int *__restrict__ idx) {
-    f4 acc = {0.f, 0.f, 0.f, 0.f};
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const float bv = load_fin(s, q, 4 * j + g, c0 + l15, lifted, fts, idx);
@@ -127,7 +126,7 @@ __global__ void __launch_bounds__(kThreads) xconv_fwd_kernel(Shape s, long long 
 #pragma unroll
         for (int j = 0; j < 4; ++j) xa[j] = load_x(s, q, l15, 4 * j + g, X);
         for (int c0 = sl.lo; c0 < sl.hi; c0 += kCT) {
-            const f4 t = xfin_tile(s, q, c0, g, l15, xa, lifted, fts, idx);
+            const f32x4 t = xfin_tile(s, q, c0, g, l15, xa, lifted, fts, idx);
             const int ch = c0 + l15;
             const bool ok = ch < sl.hi;
 #pragma unroll
@@ -175,10 +174,10 @@ __global__ void __launch_bounds__(kThreads) xconv_dgrad_kernel(Shape s, long lon
         float xt[4];                                   // A[row = k = l15][kk = g] of step j: X[k' = 4 j + g][k = l15]
 #pragma unroll
         for (int j = 0; j < 4; ++j) xt[j] = load_x(s, q, 4 * j + g, l15, X);
-        f4 accX = {0.f, 0.f, 0.f, 0.f};
+        f32x4 accX = {0.f, 0.f, 0.f, 0.f};
         for (int c0 = sl.lo; c0 < sl.hi; c0 += kCT) {
             // dFin[k = 4 g + reg][ch = c0 + l15] = sum_k' X[k',k] dT[k',ch]
-            f4 accF = {0.f, 0.f, 0.f, 0.f};
+            f32x4 accF = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int j = 0; j < 4; ++j)
                 accF = __builtin_amdgcn_mfma_f32_16x16x4f32(xt[j], dt_at<DM>(sl, wds, dyq, 4 * j + g, c0 + l15), accF, 0,
@@ -233,7 +232,7 @@ __global__ void __launch_bounds__(kThreads) xconv_wgrad_kernel(Shape s, long lon
         float xa[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) xa[j] = load_x(s, q, l15, 4 * j + g, X);
-        const f4 t = xfin_tile(s, q, c0, g, l15, xa, lifted, fts, idx);
+        const f32x4 t = xfin_tile(s, q, c0, g, l15, xa, lifted, fts, idx);
         if (ch < s.c) {
 #pragma unroll
             for (int m = 0; m < DM; ++m) {

@@ -28,18 +28,12 @@
 //     a fixed order): every wave builds the A operand for 32 rows instead of 64.
 //   * the halves run one phase apart (half 1 starts with a barrier of its own): while one half stages -- vector and LDS-store
 //     work -- the other is in its matrix phase, and a SIMD holds one wave of each.
-// Large (h h) and small products in separate accumulators; the small ones join the large once per tile.
+// Large (h h) and small products in separate accumulators (the split and the buffer loads are device.h's);
+// the small ones join the large once per tile.
 // No float atomics; every sum has a fixed order: two calls give the same bits.
 #include "common.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int KC = 64;                         // K == N == 64
 constexpr int TR = 64;                         // rows of a tile
@@ -50,40 +44,6 @@ constexpr int CO_OFF = WF_OFF + 3 * 8 * 64 * 16;   // p, q, t [64] each
 constexpr int LDS_BYTES = CO_OFF + 3 * KC * 4;
 constexpr int STAT_OFF = 8 * 2048 * 4;         // the final sums: dW copies [8 waves][2][32][32], then the statistics, then db
 constexpr int DB_OFF = STAT_OFF + 8 * 5 * 32 * 4;
-constexpr unsigned kOOB32 = 0x7FFFFFF0u;       // the 32-bit byte bound the pool-top calls keep (mlp.hip kOOB)
-
-// two fp32 values as three packed bf16 pairs (the arithmetic of mlp.hip's split3_pair)
-__device__ __forceinline__ void split3_pair(float a, float b, unsigned &h, unsigned &m, unsigned &l) {
-    const f32x2 v = {a, b};
-    const bf16x2 hh = __builtin_convertvector(v, bf16x2);
-    const f32x2 r1 = v - __builtin_convertvector(hh, f32x2);
-    const bf16x2 mm = __builtin_convertvector(r1, bf16x2);
-    const f32x2 r2 = r1 - __builtin_convertvector(mm, f32x2);
-    const bf16x2 ll = __builtin_convertvector(r2, bf16x2);
-    h = __builtin_bit_cast(unsigned, hh); m = __builtin_bit_cast(unsigned, mm); l = __builtin_bit_cast(unsigned, ll);
-}
-// eight values as the three pieces of one MFMA fragment
-__device__ __forceinline__ void split3_frag(const float (&x)[8], u32x4 &h, u32x4 &m, u32x4 &l) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        unsigned a, b, c;
-        split3_pair(x[2 * k], x[2 * k + 1], a, b, c);
-        h[k] = a; m[k] = b; l[k] = c;
-    }
-}
-__device__ __forceinline__ bf16x8 frag(const u32x4 &v) { return __builtin_bit_cast(bf16x8, v); }
-__device__ __forceinline__ f32x16 zero16() {
-    const f32x16 z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    return z;
-}
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const void *base, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), 0, bytes, 0x00020000);
-}
-__device__ __forceinline__ float4 load4(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0);
-    return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
-}
 
 struct Req {
     float4 g[4], y[4], o;          // the thread's four rows of G and Y (one column quad), one row of offsets
@@ -141,18 +101,18 @@ __global__ __launch_bounds__(512, 1) void xyz_bwd_tiles_kernel(int M, const floa
 
     // One descriptor per tensor and one 32-bit offset per thread: the tile's first row is a scalar offset, a thread's rows
     // immediates.  A row past M is out of the descriptor's range and reads as zeros (M 256 bytes < 2^31: the launcher).
-    const __amdgpu_buffer_rsrc_t rG = rsrc(G, (unsigned)M * (KC * 4u)), rY = rsrc(Y, (unsigned)M * (KC * 4u)),
-                                 rO = rsrc(off4, (unsigned)M * 16u);
+    const __amdgpu_buffer_rsrc_t rG = make_rsrc_u32(G, (unsigned)M * (KC * 4u)), rY = make_rsrc_u32(Y, (unsigned)M * (KC * 4u)),
+                                 rO = make_rsrc_u32(off4, (unsigned)M * 16u);
     const unsigned gvo = (unsigned)(4 * rg * KC + 4 * cq) * 4u, ovo = (unsigned)(ht & 63) * 16u;
     auto request = [&](Req &r, int step) {
         const int tile = 2 * step + hf;
         const unsigned row0 = (unsigned)(tile < ntiles ? tile : ntiles - 1) * TR;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            r.g[j] = load4(rG, gvo + j * KC * 4u, row0 * (KC * 4u));
-            r.y[j] = load4(rY, gvo + j * KC * 4u, row0 * (KC * 4u));
+            r.g[j] = buf_load4(rG, gvo + j * KC * 4u, row0 * (KC * 4u));
+            r.y[j] = buf_load4(rY, gvo + j * KC * 4u, row0 * (KC * 4u));
         }
-        r.o = load4(rO, ovo, row0 * 16u);
+        r.o = buf_load4(rO, ovo, row0 * 16u);
     };
 
     // FULL: all 64 rows of the tile exist -- thread-uniform, true for every tile but the last; a row past M is a zero row of dY,
@@ -384,8 +344,8 @@ __global__ __launch_bounds__(1024) void xyz_bwd_tiles_sum_kernel(int P, const fl
 
 // PCOPS_BWD_XYZ_TILES = 1 (default): the form above takes this kernel; 0: bwd_fused_kernel for every shape
 bool pcops_xyz_bwd_tiles_form(long long M, int K, int N) {
-    static const bool on = [] { const char *e = getenv("PCOPS_BWD_XYZ_TILES"); return !(e && e[0] == '0'); }();   // kernel A/B only
-    return on && K == KC && N == KC && M >= 65536 && M * KC * 4 < (long long)kOOB32;
+    static const bool on = pcops_env_switch("PCOPS_BWD_XYZ_TILES", true);   // kernel A/B only
+    return on && K == KC && N == KC && M >= 65536 && M * KC * 4 < (long long)kOOB;
 }
 
 int pcops_xyz_bwd_tiles_launch(long long M, int groups, const float *off4, const float *xyzw, const float *a_scale,

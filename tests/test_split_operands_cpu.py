@@ -1,7 +1,12 @@
-"""The algebra behind the split-operand kernels (csrc/mlp.hip `split3`), checked on the CPU with
-torch's bfloat16 (round-to-nearest-even, what v_cvt_pk_bf16_f32 does): an fp32 value is the sum of three bf16 pieces up to
-2^-25 of itself with EXACT fp32 residuals, the product of two pieces is exact in fp32, and the six products the kernels
-keep differ from the full product by at most ~2^-24 of it."""
+"""The algebra behind the split-operand kernels (csrc/device.h `split3_pair`), checked on the CPU
+with torch's bfloat16 (round-to-nearest-even, what v_cvt_pk_bf16_f32 does): an fp32 value is the sum of three bf16 pieces up
+to 2^-25 of itself with EXACT fp32 residuals, the product of two pieces is exact in fp32, and the six products the kernels
+keep differ from the full product by at most ~2^-24 of it.  The `split3` below restates the header's arithmetic; the last
+test compiles the header itself for the host and holds the two together bit for bit."""
+import os
+import subprocess
+
+import numpy as np
 import torch
 
 
@@ -86,3 +91,23 @@ def test_two_accumulators_beat_one_on_a_long_dot_product():
     e_two = ((two.double() - ref).pow(2).mean().sqrt() / scale).item()
     e_plain = ((plain.double() - ref).pow(2).mean().sqrt() / scale).item()
     assert e_two < 0.6 * e_one and e_two < 0.5 * e_plain, (e_two, e_one, e_plain)
+
+
+def test_device_header_split_matches_bit_for_bit(tmp_path):
+    """csrc/device.h's two split3_pair overloads, compiled for the host by the ROCm clang (the toolchain build() needs: a
+    missing compiler fails), against split3 above: the same three bf16 pieces, bit for bit, for every value"""
+    here = os.path.dirname(os.path.abspath(__file__))
+    clang = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", "clang++")
+    x = _values(200000, 1)
+    x = torch.cat([x, torch.zeros(x.numel() % 2)])
+    exe, fin, fout = str(tmp_path / "split3_host"), str(tmp_path / "in.f32"), str(tmp_path / "out.u32")
+    x.numpy().tofile(fin)
+    subprocess.check_call([clang, "-O2", "-std=c++17", "-ffp-contract=off", os.path.join(here, "split3_host.cpp"), "-o", exe])
+    subprocess.check_call([exe, fin, fout])
+    got = np.fromfile(fout, dtype=np.uint16).reshape(-1, 2, 3, 2)               # [pair][overload][piece][value of the pair]
+    assert got.shape[0] * 2 == x.numel()
+    want = np.stack([p.bfloat16().view(torch.int16).numpy().view(np.uint16) for p in split3(x)[:3]])    # [piece][value]
+    for o, name in enumerate(("bf16x2", "packed words")):
+        for k, piece in enumerate("hml"):
+            bad = int((got[:, o, k, :].reshape(-1) != want[k]).sum())
+            assert bad == 0, "%s overload: %d of %d values differ in piece %s" % (name, bad, x.numel(), piece)
