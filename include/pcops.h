@@ -1146,6 +1146,53 @@ int pcops_cloud_point_bwd(int b, int n, int k, int c, const float *G, const floa
                           const float *t, const float *X, const float *Wx, float *dX, float *dWx, float *dCtr, void *workspace,
                           pcops_stream_t stream);
 
+/* ---- Device-resident feed (feed.hip): one launch builds a training step's batch from a set that
+ * lives on the device -- it picks the clouds and their points, gathers labels and the per-point mask / parts, and applies the
+ * augmentation recipe with counter-based random numbers, so the launch replays unchanged inside a captured step.
+ *   set:    pts (P, 3) all clouds one after the other; offsets (K + 1) first point of every cloud, or NULL: a dense set of
+ *           ntot points per cloud (ntot is not read for a ragged set); labels (K); side: one value per point of pts (mask or
+ *           parts), or NULL.
+ *   epoch:  order (K) the epoch's cloud order, values in [0, K).  mode 0: output point j reads source point idx_pts[j]
+ *           (n values in [0, ntot), one list shared by every cloud; dense sets only).  mode 1: output point j reads source
+ *           point perm(j) of the cloud's own pseudo-random permutation (below; idx_pts is not read).
+ *   step:   params = four ints in DEVICE memory {first, step, epoch, 0}, read by the kernel (pcops_feed_set_params writes
+ *           them with an ordinary kernel whose values are launch arguments); seed, the recipe and its constants by value.
+ *   out:    x (B, n, 3), y (B), m (B, n) or NULL (with side == NULL neither is touched).
+ * Row r is cloud c = order[first + r].  A row with first + r >= K (or first + r < 0) is written as zeros with label -1, and
+ * nothing of the set is read for it.  An order / idx_pts entry outside its range is outside the contract; the kernel still
+ * reads nothing outside the set for it (the row, or the point, is written as zeros).
+ * min_points: the smallest cloud of the set, known to the host (ntot for a dense set): n > min_points is PCOPS_ERR_BAD_SHAPE.
+ * K, n <= 0, B < 0, ntot <= 0 for a dense set: PCOPS_ERR_BAD_SHAPE; mode / recipe outside their values, mode 0 on a ragged
+ * set, clip <= 0 or smin > smax with a recipe that reads them: PCOPS_ERR_BAD_ARGUMENT; B > 65535: PCOPS_ERR_UNSUPPORTED;
+ * B == 0: PCOPS_OK, nothing launched.  Nothing is written when a status other than PCOPS_OK comes back.
+ *
+ * Recipes (every product and sum a separate fp32 operation, in this order):
+ *   0  the gather only.
+ *   1  rotation about Y by theta = 2 pi u(w0) of the cloud's draw, x' = x c - z s, z' = x s + z c (provider.rotate_point_cloud's
+ *      row-vector convention), then the jitter.
+ *   2  per-axis scale s_k = smin + (smax - smin) u(w_k) of the cloud's draw, then per-axis translation
+ *      t_k = (2 u(w_k) - 1) tval of the cloud's second draw: v_k s_k + t_k; then the jitter (mfv3d_net_cls.augment).
+ *   jitter: v_k + min(max(sigma z_k, -clip), clip) with the point's normals z_0, z_1, z_2.
+ * Random numbers: Philox4x32-10 (multipliers 0xD2511F53 on word 0 and 0xCD9E8D57 on word 2, key increments 0x9E3779B9 and
+ * 0xBB67AE85), key = (seed & 0xffffffff, seed >> 32).  Counters, g = first + r being the GLOBAL position of the cloud in the
+ * epoch's order (a batch does not depend on how it is split over ranks):
+ *   the cloud's draws (g, step, 0, TAG_CLOUD) and (g, step, 1, TAG_CLOUD); the normals of output point j (g, step, j, TAG_JIT);
+ *   the permutation keys of cloud c (c, epoch, t, TAG_PERM), t = 0, 1 (key[0..3], key[4..7]).
+ * u(w) = ((w >> 9) + 0.5) 2^-23, exact in fp32 and never 0 or 1.  Normals by Box-Muller: z0 = sqrt(-2 ln u(w0)) cos(2 pi u(w1)),
+ * z1 = sqrt(-2 ln u(w0)) sin(2 pi u(w1)), z2 = sqrt(-2 ln u(w2)) cos(2 pi u(w3)).
+ * Permutation of a cloud of n_i points: an 8-round unbalanced Feistel network over bits = max(bit_length(n_i - 1), 2) bits
+ * with cycle walking.  a = bits / 2, b = bits - a, L = x >> b, R = x & (2^b - 1), (wl, wr) = (a, b); for r = 0..7:
+ * (L, R) <- (R, L ^ F(R, key[r], wl)), swap wl and wr; x' = (L << b) | R, repeated while x' >= n_i.
+ * F(v, k, w) in 32-bit arithmetic: v ^= k; v *= 0x9E3779B1; v ^= v >> 15; v *= 0x85EBCA6B; v ^= v >> 13; v & (2^w - 1). */
+#define PCOPS_FEED_TAG_CLOUD 0x434c4f55u   /* "CLOU" */
+#define PCOPS_FEED_TAG_JIT   0x4a495454u   /* "JITT" */
+#define PCOPS_FEED_TAG_PERM  0x5045524du   /* "PERM" */
+int pcops_feed_set_params(int first, int step, int epoch, int *params, pcops_stream_t stream);
+int pcops_feed_batch(int K, long long ntot, int B, int n, int mode, int recipe, long long min_points, const float *pts,
+                     const long long *offsets, const long long *labels, const long long *side, const int *order,
+                     const int *idx_pts, const int *params, unsigned long long seed, float sigma, float clip, float smin,
+                     float smax, float tval, float *x, long long *y, long long *m, pcops_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -43,7 +43,7 @@ def refusal(args, world, environ):
     if getattr(args, "sync_bn", False):
         return "--sync_bn exchanges the batch statistics between ranks inside the forward pass"
     path = getattr(args, "train_file", "") or ""
-    if path and not path.endswith(".npz") and ".h5" not in path:
+    if path and not path.endswith(".npz") and ".h5" not in path and not getattr(args, "device_feed", False):
         return "%s: a list of raw .bin objects is a ragged set sampled on the host every epoch" % path
     if args.model not in VERIFIED_MODELS:
         return ("--model %s is not on the list of families whose captured step is verified against their eager step (%s)"
@@ -66,21 +66,35 @@ def needs_capture(captured, wanted):
 class CapturedStep:
     """body(x, y, m, bn_decay, tot, update): one training step on the static inputs, adding its loss / correct / seen to
     `tot` and calling `update()` where the optimiser steps.  x (B,N,3) float32, y the labels, m the per-point mask or
-    parts (None for a classifier): examples that give the static buffers their shapes and dtypes."""
+    parts (None for a classifier): examples that give the static buffers their shapes and dtypes.
+    feed (device_feed.DeviceFeed, optional): the static inputs are the feed's buffers and its launch is the first node of the
+    captured body; x, y, m are then not read, and `step` moves the feed's parameters instead of copying a batch in."""
 
-    def __init__(self, body, net, fp, opt, x, y, m=None):
-        self.body, self.net, self.fp, self.opt = body, net, fp, opt
+    def __init__(self, body, net, fp, opt, x, y, m=None, feed=None):
+        self.net, self.fp, self.opt, self.feed = net, fp, opt, feed
+        self.body = body if feed is None else self._fed(body)
         dev = fp.flat.device
         self.adam = isinstance(opt, TU.TFAdam)
         if self.adam:
             opt.enable_device_lr()
-        self.x, self.y = torch.zeros_like(x, device=dev), torch.zeros_like(y, device=dev)
-        self.m = torch.zeros_like(m, device=dev) if m is not None else None
+        if feed is not None:
+            self.x, self.y, self.m = feed.x, feed.y, feed.m
+        else:
+            self.x, self.y = torch.zeros_like(x, device=dev), torch.zeros_like(y, device=dev)
+            self.m = torch.zeros_like(m, device=dev) if m is not None else None
         self.tot = torch.zeros(3, dtype=torch.float64, device=dev)      # loss sum, correct, seen: accumulated in the graph
         self.stream = torch.cuda.Stream(dev)                             # warm-up and capture: one stream, a linear graph
         self.graph = None
         self.baked = None
         self.captures = 0
+
+    def _fed(self, body):
+        """the feed's launch, then the step: it reads its parameters from device memory and changes none of them, so the
+        warm-up steps leave them as they found them"""
+        def fed(x, y, m, bn_decay, tot, update):
+            self.feed.launch()
+            body(x, y, m, bn_decay, tot, update)
+        return fed
 
     def _state(self):
         """every tensor a step changes that the next step reads"""
@@ -127,13 +141,17 @@ class CapturedStep:
         self.graph = graph
         self.captures += 1
 
-    def step(self, x, y, m, lr, bn_decay):
+    def step(self, x, y, m, lr, bn_decay, batch=None):
         """one training step on (x, y, m): into the static inputs, a new capture where the schedule asks for one, Adam's
-        step size into its device scalar, one replay"""
-        self.x.copy_(x)
-        self.y.copy_(y)
-        if self.m is not None:
-            self.m.copy_(m)
+        step size into its device scalar, one replay.  With a feed: batch = (first, step) into the feed's parameters, ahead
+        of a capture's warm-up steps as well, and no copy"""
+        if self.feed is not None:
+            self.feed.set_batch(*batch)
+        else:
+            self.x.copy_(x)
+            self.y.copy_(y)
+            if self.m is not None:
+                self.m.copy_(m)
         wanted = baked_values("adam" if self.adam else "momentum", lr, bn_decay)
         if needs_capture(self.baked, wanted):
             self.capture(lr, bn_decay)

@@ -109,6 +109,10 @@ def model_fn(args, device=None):
     return bind(gmm, device=device, weigth_decay=float(getattr(args, "weight_decay", 0.0)))
 
 
+# `augment` below as a recipe of the device-resident feed (device_feed.py, pcops_feed_batch): the same three steps and constants
+DEVICE_FEED_RECIPE = {"recipe": 2, "smin": 0.66, "smax": 1.5, "tval": 0.2, "sigma": 0.01, "clip": 0.05}
+
+
 def augment(batch, generator=None):
     """the model's training augmentation (3DmFV-Net/train.py:25,263-274): scale, translate, jitter -- no rotation"""
     batch = provider.scale_point_cloud(batch, smin=0.66, smax=1.5, generator=generator)

@@ -18,7 +18,9 @@ Per step: forward (training BN, dropout) -> loss -> backward -> ONE all-reduce o
 Adam / momentum with the staircase lr; bn_decay follows the reference schedule.  Loss and accuracy are accumulated
 on the device and read ONCE per epoch (no per-step host synchronisation).  `--graph` (single rank, the families listed in
 `captured_step.py`): that step is captured once as a HIP graph and replayed, with the input pipeline above staying outside
-the graph; evaluation, checkpoints and everything else are the same either way.  A checkpoint (`model.pt`, variables under
+the graph; evaluation, checkpoints and everything else are the same either way.  `--device_feed` (`device_feed.py`): that
+input pipeline as ONE launch per step on the resident set -- raw `.bin` split lists included, which then live on the device --
+with counter-based random numbers; under `--graph` the launch is part of the captured step.  A checkpoint (`model.pt`, variables under
 the reference's TF scope names) is written every epoch after the BN moving statistics were made rank 0's.
 """
 import argparse
@@ -30,7 +32,7 @@ import time
 import numpy as np
 import torch
 
-from .. import captured_step as CS, data_utils, dist as D, provider
+from .. import captured_step as CS, data_utils, device_feed as DF, dist as D, provider
 from .. import train_util as TU
 from ..graph import Model
 from ..synth import synth_clouds, synth_labels, synth_masks
@@ -144,6 +146,10 @@ def parse_args(argv=None):
     p.add_argument("--graph", action="store_true",
                    help="capture one training step as a HIP graph and replay it every step (captured_step.py); a run that "
                    "cannot be captured says why in one line and trains eagerly")
+    p.add_argument("--device_feed", action="store_true",
+                   help="build every step's batch on the device in one launch (device_feed.py): selection, labels, mask and "
+                   "the augmentation, with counter-based random numbers; raw .bin sets then live on the device and may train "
+                   "under --graph.  A run it cannot feed says why in one line and trains on the host-fed path")
     add_model_flags(p)
     args = resolve_model_flags(p.parse_args(argv))
     mod = importlib.import_module(MODELS[args.model])
@@ -288,6 +294,18 @@ def train(args, state=None):
                 tot[1] += (scores(EV.split_output(out)[0]).argmax(dim=1) == y).sum()
                 tot[2] += per_rank
 
+    feed = test_feed = None                          # --device_feed: the step's batch from one launch on the resident set
+    if getattr(args, "device_feed", False):
+        why = DF.refusal(args, mod, own, dev.type)        # decided here, before anything runs
+        if why is not None:
+            print("--device_feed refused, training on the host-fed path: %s" % why, flush=True)
+            args.device_feed = False                      # (what captured_step.refusal reads below)
+        else:
+            recipe, consts = DF.recipe_of(args, mod)
+            feed = DF.DeviceFeed(train_data, train_lab, train_mask, args.num_point, per_rank, args.seed + 1000, recipe,
+                                 consts, dev)
+            if isinstance(test_data, list):               # a ragged evaluation set: its epoch views come from a feed as well
+                test_feed = DF.DeviceFeed(test_data, test_lab, None, args.num_point, 1, args.seed + 2000, 0, consts, dev)
     captured = None                                  # --graph: the step as one captured HIP graph, built at the first batch
     use_graph = bool(getattr(args, "graph", False))
     if use_graph:
@@ -296,33 +314,44 @@ def train(args, state=None):
             print("--graph refused, training eagerly: %s" % why, flush=True)
             use_graph = False
     for epoch in range(args.max_epoch):
-        cur, lab, msk = epoch_view(train_data, train_lab, train_mask, args.num_point, rng, dev)
-        nb = cur.shape[0] // args.batch_size
+        if feed is not None:                                       # the host draws the epoch's order (and shared point list)
+            feed.begin_epoch(rng, epoch)
+            nb = feed.K // args.batch_size
+        else:
+            cur, lab, msk = epoch_view(train_data, train_lab, train_mask, args.num_point, rng, dev)
+            nb = cur.shape[0] // args.batch_size
         t0 = time.time()
         tot = torch.zeros(3, dtype=torch.float64, device=dev)      # loss sum, correct, seen -- read once per epoch
         if captured is not None:
             tot = captured.tot.zero_()                             # ... accumulated inside the graph
         for b in range(nb):
-            sl = slice(b * args.batch_size + lo, b * args.batch_size + hi)
-            x = cur[sl]
-            if not args.no_augment and augment is not None:           # a family with its own augmentation (3DmFV-Net)
-                x = augment(x, generator=gen)
-            elif not args.no_augment:
-                x = provider.jitter_point_cloud(provider.rotate_point_cloud(x, generator=gen), generator=gen)
-            x = x.contiguous()
-            y = lab[sl]
             if own:                                                   # the model's schedule (PointCNN: in steps) on the same flags
                 lr = own.learning_rate(step)
             else:
                 lr = TU.get_learning_rate(step, args.batch_size, args.learning_rate, args.decay_step, args.decay_rate)
             bn_decay = TU.get_bn_decay(step, args.batch_size, float(args.decay_step))
-            m = msk[sl] if with_mask else None
+            if feed is not None:                # x, y, m from one launch: this rank's first cloud by its position in the order
+                batch = (b * args.batch_size + lo, step)
+                x = y = m = None
+            else:
+                sl = slice(b * args.batch_size + lo, b * args.batch_size + hi)
+                x = cur[sl]
+                if not args.no_augment and augment is not None:           # a family with its own augmentation (3DmFV-Net)
+                    x = augment(x, generator=gen)
+                elif not args.no_augment:
+                    x = provider.jitter_point_cloud(provider.rotate_point_cloud(x, generator=gen), generator=gen)
+                x = x.contiguous()
+                y = lab[sl]
+                m = msk[sl] if with_mask else None
             if use_graph:
                 if captured is None:
-                    captured = CS.CapturedStep(step_body, net, fp, opt, x, y, m)
+                    captured = CS.CapturedStep(step_body, net, fp, opt, x, y, m, feed=feed)
                     tot = captured.tot
-                captured.step(x, y, m, lr, bn_decay)
+                captured.step(x, y, m, lr, bn_decay, batch=batch if feed is not None else None)
             else:
+                if feed is not None:
+                    feed.set_batch(*batch)
+                    x, y, m = feed.launch()
                 step_body(x, y, m, bn_decay, tot, lambda: opt.step(lr))
             step += 1
         if D.dist.is_initialized() and world > 1:
@@ -332,7 +361,11 @@ def train(args, state=None):
         D.broadcast_buffers_(net)                # per-rank BN moving statistics -> rank 0's, before eval / checkpoint
         # the reference draws a FRESH point subset and cloud order for every evaluation from the same global stream
         # as the training epochs (`train.py:275`: get_current_data_h5 on TEST_DATA) -- same here, same `rng`
-        td, tl, tm = epoch_view(test_data, test_lab, test_mask, args.num_point, rng, dev)
+        if test_feed is not None:                # ragged: the order from `rng`, every cloud's subset from the feed's permutation
+            test_feed.begin_epoch(rng, epoch)
+            td, tl, tm = test_feed.epoch_view()
+        else:
+            td, tl, tm = epoch_view(test_data, test_lab, test_mask, args.num_point, rng, dev)
         if partseg:
             ev = EV.eval_partseg_one_epoch(net, td, tm, per_rank, device=dev)
         elif with_mask:
