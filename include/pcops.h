@@ -138,6 +138,7 @@ int pcops_last_launch_pipe(void);
  *                 [2] rows of stats_partial written (0 without statistics);  [3] 1 for the statistics-from-moments route
  *                 (sa_gather_offsets_kernel + xyz_stats_from_moments_kernel);  [4] 4 compacted rows
  *              17 pcops_mlp_bwd_fused_xyz_rows on the all-wave tile kernel (csrc/xyz_bwd_tiles.hip): [1] = 2, [2] = 64
+ *              18 pcops_mlp_bwd_tiles_rows (csrc/bwd_tiles128.hip): [1] = 2, [2] = 128, [4] = 4 over compacted rows
  *   [1] split  1 when the operands are split into bf16 pieces (the one-pass backward: 1 its dX half, 2 both halves)
  *   [2] bn     output columns per block (64, 96, 128; the weight gradients: columns of their dW tile; 0 tiled)
  *   [3] wst    1 when the weights are streamed rather than resident in LDS
@@ -574,6 +575,24 @@ int pcops_mlp_bwd_fused_xyz_rows(long long M, int K, int N, const float *off4, c
                                  const float *t, const float *gpool, const unsigned char *argmax, int S, const float *W,
                                  float *partial, float *dW, float *db, float *stats_partial, float *xyz_stats,
                                  const pcops_rows_t *rows, pcops_stream_t stream);
+/* The one-pass backward of a 128 -> 128 layer whose input rows are read (csrc/bwd_tiles128.hip): what
+ * pcops_mlp_gemm_dgrad_rows (with Yprev) followed by pcops_mlp_wgrad_rows compute for  Y = relu(bn(Yprev)) W + b,  every tensor
+ * read once -- Gprev [M][K] = mask . (dY W^T), stats_partial [groups][2][K] = (sum Gprev, sum Gprev Yprev), dW, db.  Both
+ * products run on the bf16 matrix pipe with split operands (six products, large and small terms in separate accumulators;
+ * pcops_last_launch_pipe() 1, plan path 18 with [1] = 2, [2] = 128, [4] = 4 over compacted rows).  No float atomics: the
+ * workgroups' partial copies are added in a fixed order, two calls give the same bits, deterministic mode takes the same kernel.
+ *   pcops_mlp_bwd_tiles_groups  the launcher's own answer: 0 when (M, K, N) is not taken (K == N == 128, 64 <= M, M * 512 bytes
+ *                               below 2^31), otherwise the number of partial copies: partial = groups * (K N + N) floats,
+ *                               stats_partial rows = groups.  PCOPS_BWD_TILES128=0 in the environment, read once by the
+ *                               library, makes it answer 0 for every shape.  pcops_mlp_bwd_fused_groups is not affected.
+ *   rows  NULL or a compacted row set (M = the allocated row count): the row that opens a block has dY = p.G + w (q.Y + t)
+ *         with the block's weight w, exactly as the two _rows entry points above form it; Gprev rows past the device row
+ *         count are not written.  Yprev, G, Y, W, Gprev 16-byte aligned (else PCOPS_ERR_UNSUPPORTED). */
+int pcops_mlp_bwd_tiles_groups(long long M, int K, int N);
+int pcops_mlp_bwd_tiles_rows(long long M, int K, int N, const float *Yprev, const float *a_scale, const float *a_shift,
+                             const float *G, const float *Y, const float *p, const float *q, const float *t, const float *W,
+                             float *partial, float *dW, float *db, float *Gprev, float *stats_partial, const pcops_rows_t *rows,
+                             pcops_stream_t stream);
 int pcops_mlp_gemm_fwd_xyz(int M, int K, int N, const float *off4, const float *xyzw, const float *pro_scale,
                            const float *pro_shift, const float *W, const float *bias, float *Y,
                            float *stats_partial, const float *stat_pivot, pcops_stream_t stream);

@@ -83,9 +83,15 @@ B_TOP, B_SPLIT, B_SPLIT_XYZ = "top", "split", "split_xyz"
 B_ONEPASS, B_ONEPASS_XYZ, B_ONEPASS_GW, B_ONEPASS_EDGE, B_ONEPASS_EDGE_GW = (
     "onepass", "onepass_xyz", "onepass_gw", "onepass_edge", "onepass_edge_gw")
 _ONEPASS = (B_ONEPASS, B_ONEPASS_XYZ, B_ONEPASS_GW, B_ONEPASS_EDGE, B_ONEPASS_EDGE_GW)
+# ... and the all-wave tile kernel of a 128 -> 128 layer (pcops_mlp_bwd_tiles_rows), planned from TILES_MIN_ROWS allocated rows
+# upward.  Reasoned, not measured: up to 262 144 rows G, Y and Yprev total at most 0.4 GB (under 0.3 GB compacted) and the second
+# read of the two-kernel path comes largely from the 256 MB cache level; at the floor they are twice that level.  (262 144 itself
+# stays with the two kernels: tests/test_pool_top_rows_gpu.py pins the data-gradient launch of an SA2 stack of that size.)
+B_ONEPASS_TILES = "onepass_tiles"
+TILES_MIN_ROWS = 524288
 # the arms that read the layer's own stored Y / the Y of the layer below
-_READS_Y = (B_CLOUD, B_CLOUD_POINT, B_SCATTER, B_SCATTER_ID, B_SPLIT, B_SPLIT_XYZ) + _ONEPASS
-_READS_Y_BELOW = (B_TOP, B_SPLIT, B_ONEPASS, B_ONEPASS_GW, B_ONEPASS_EDGE, B_ONEPASS_EDGE_GW)
+_READS_Y = (B_CLOUD, B_CLOUD_POINT, B_SCATTER, B_SCATTER_ID, B_SPLIT, B_SPLIT_XYZ, B_ONEPASS_TILES) + _ONEPASS
+_READS_Y_BELOW = (B_TOP, B_SPLIT, B_ONEPASS, B_ONEPASS_GW, B_ONEPASS_EDGE, B_ONEPASS_EDGE_GW, B_ONEPASS_TILES)
 
 
 class LayerPlan(NamedTuple):
@@ -211,6 +217,9 @@ def plan_stack(*, R, S, K0, widths, pool, training, need_grad, need_dx, sync, w_
                 bwd = ((B_ONEPASS_EDGE_GW if gw else B_ONEPASS_EDGE) if use_edge else B_ONEPASS_GW if gw
                        else B_ONEPASS_XYZ if xyz_prev else B_ONEPASS)
                 count = onepass
+            elif (need_grad and l > 0 and not xyz_prev and not top and not pooled and w_aligned[l] and R >= TILES_MIN_ROWS
+                    and lib.pcops_mlp_bwd_tiles_groups(R, K, N)):
+                bwd, count = B_ONEPASS_TILES, lib.pcops_mlp_bwd_tiles_groups(R, K, N)
             elif need_grad:
                 bwd, count = (B_SPLIT_XYZ if xyz_prev else B_SPLIT), lib.pcops_mlp_wgrad_splits(R, K, N)
         layers.append(LayerPlan(fwd, K, N, bool(store_y), pooled, bwd, int(count), bool(bwd == B_TOP and groups)))
@@ -402,6 +411,8 @@ class FusedMLPStack(torch.autograd.Function):
                 _pool_top_backward(dn, l, lp, p, q, t)
             elif lp.bwd in _ONEPASS:
                 _bwd_onepass(dn, l, lp, p, q, t, top)
+            elif lp.bwd == B_ONEPASS_TILES:
+                _bwd_onepass_tiles(dn, l, lp, p, q, t)
             else:
                 _bwd_split(dn, l, lp, p, q, t, top)
         d0, d1, dwxyz, dbias = first if gather else (dn.Gm, None, None, None)
@@ -721,6 +732,22 @@ def _bwd_onepass(dn, l, lp, p, q, t, top):
                   sv.shifts[l - 1].data_ptr(), Gptr, Y.data_ptr(), p.data_ptr(), q.data_ptr(), t.data_ptr(),
                   gp, am, S, W.data_ptr(), scratch.data_ptr(), dW.data_ptr(), db.data_ptr(),
                   Gprev.data_ptr(), part.data_ptr(), dn.rref)
+    dn.grads[6 * l + 0] = dW
+    dn.grads[6 * l + 1] = db
+    dn.Gm, dn.P, dn.part = Gprev, groups, part
+
+
+def _bwd_onepass_tiles(dn, l, lp, p, q, t):
+    """data and weight gradient of a 128 -> 128 layer in one pass of the all-wave tile kernel (pcops_mlp_bwd_tiles_rows)"""
+    sv, dev, R = dn.sv, dn.dev, dn.R
+    K, N, groups = lp.K, lp.N, lp.count
+    scratch = _f32(groups * (K * N + N), dev)
+    dW, db = _f32((K, N), dev), _f32(N, dev)
+    part = _f32((groups, 2, K), dev)
+    Gprev = _f32((R, K), dev)
+    _lib.call("pcops_mlp_bwd_tiles_rows", R, K, N, sv.Ys[l - 1].data_ptr(), sv.scales[l - 1].data_ptr(),
+              sv.shifts[l - 1].data_ptr(), _p(dn.Gm), sv.Ys[l].data_ptr(), p.data_ptr(), q.data_ptr(), t.data_ptr(),
+              sv.Ws[l].data_ptr(), scratch.data_ptr(), dW.data_ptr(), db.data_ptr(), Gprev.data_ptr(), part.data_ptr(), dn.rref)
     dn.grads[6 * l + 0] = dW
     dn.grads[6 * l + 1] = db
     dn.Gm, dn.P, dn.part = Gprev, groups, part

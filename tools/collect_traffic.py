@@ -49,6 +49,7 @@ KEYS = [
     ("bwd_fused_kernel<2, 4, false, false", None, "pcops_mlp_bwd_fused(4194304, 64, 128)"),            # round 3: one pass for ...
     ("bwd_fused_kernel<1, 2, true, false", None, "pcops_mlp_bwd_fused_xyz(4194304, 64, 64)"),      # PCOPS_BWD_XYZ_TILES=0
     ("xyz_bwd_tiles_kernel", None, "pcops_mlp_bwd_fused_xyz(4194304, 64, 64)"),                     # the default
+    ("bwd_tiles128_kernel", None, "pcops_mlp_bwd_tiles(2097152, 128, 128, 'compacted')"),           # SA2's middle layer, one pass
     ("wgrad_pc_kernel<1, 2, 1, 4, false>", None, "pcops_mlp_wgrad(4194304, 64, 128)"),                   # ... these four (PCOPS_BWD_FUSED=0)
     ("gemm_ws_kernel<2, 4, 1, 64, 8, 1, 0>", None, "pcops_mlp_gemm_dgrad(4194304, 128, 64)"),
     ("gemm_ws_kernel<2, 2, 3, 64, 8, 1, 0>", None, "pcops_mlp_gemm_dgrad_xyz(4194304, 64, 64)"),
