@@ -98,6 +98,31 @@ int pcops_xyz_bwd_tiles_launch(long long M, int groups, const float *off4, const
                                const float *t, const float *W, float *partial, float *dW, float *db, float *stats_partial,
                                float *xyz_stats, hipStream_t st);
 
+// ---- what the translation units of the MLP family share (mlp.hip: the matrix products; mlp_bn.hip: the per-channel and
+// elementwise passes around them; pooltop_sparse.hip: the sparse halves of the pooled top layer's algebraic backward)
+namespace pcops_mlp {
+constexpr int kBlk = 16;          // rows per block of a compacted row set
+}  // namespace pcops_mlp
+// a compacted row set as an argument of an entry point (NULL: all rows)
+static inline int rows_ok(const pcops_rows_t *rows) {
+    if (!rows) return PCOPS_OK;
+    PCOPS_REQUIRE_PTR(rows->blocks); PCOPS_REQUIRE_PTR(rows->block_start); PCOPS_REQUIRE_PTR(rows->rows);
+    if (reinterpret_cast<uintptr_t>(rows->blocks) & 15) return PCOPS_ERR_UNSUPPORTED;
+    return PCOPS_OK;
+}
+constexpr int kTopRowsWs = 512;   // workgroups (= partial copies) of pool_top_wsparse_rows_kernel
+// what the two addend kernels over compacted rows need of the shape (the addend is indexed by the compacted row: at most M
+// rows of Kp floats behind a 32-bit offset); pcops_mlp_pool_top_rows_supported (mlp.hip) adds what the other three calls need
+static inline bool addend_rows_shape_ok(int M, int Kp, int N, int S) {
+    return S % pcops_mlp::kBlk == 0 && S <= 128 && (Kp == 64 || Kp == 128) && N <= 256 && N % 32 == 0 &&
+           (long long)M * Kp * 4 < (long long)kOOB;
+}
+// mlp_bn.hip: sum_partials2_kernel on the stream -- out [L] = the sum of the P copies part [P][L] and, when out2 is not NULL,
+// out2 [L2] = that of part2 [P][L2], in a fixed order.  What closes every product kernel that writes a partial copy per workgroup.
+#define PCOPS_HIDDEN __attribute__((visibility("hidden")))      // crosses translation units, not part of the C ABI
+PCOPS_HIDDEN int pcops_mlp_sum_partials2(int P, long long L, const float *part, float *out, long long L2, const float *part2,
+                                         float *out2, hipStream_t st);
+
 constexpr int kWave = 64;  // CDNA wavefront
 
 // Asymmetric STATIC wave priority (round 4; MI355X_MICROARCH.md "Two waves per SIMD").  Two co-resident waves that run

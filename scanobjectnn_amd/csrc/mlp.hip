@@ -32,6 +32,11 @@
 // turned into template arguments by pcops_dispatch and the LDS ceiling raised by pcops_launch_lds (common.h).  A dispatch
 // names only the instantiations a build part emits today: a combination nobody launches is `if constexpr`-ed away, never
 // compiled.  The shape queries of the C ABI (pcops_mlp_wgrad_splits, the *_supported calls) ask the same planners.
+//
+// This file holds the matrix products only: the templated kernel families (gemm_rt, gemm_ws, wgrad_*, bwd_fused, gram_*), their
+// planners, launchers and entry points.  What surrounds a product lives in translation units of its own: mlp_bn.hip (statistics
+// -> BN coefficients, pooling, the elementwise passes, the sums of partial copies, the transpose), pooltop_sparse.hip (the
+// sparse halves of the pooled top layer's algebraic backward), small_gemm.hip (the weights x weights products).
 #include <stdlib.h>
 
 #include "common.h"
@@ -39,15 +44,18 @@
 #include <type_traits>
 
 // ---- build parts.  This file is compiled SEVEN times (Makefile: -DPCOPS_MLP_PART=0..6, in parallel): every part parses the
-// whole file, but only emits its share of the kernel instantiations -- part 0 the C ABI and the small kernels, parts
-// 1, 2, 3, 6 the wave-stream / tiled GEMM launchers by (operand, epilogue) mode, part 4 the weight-gradient kernels,
-// part 5 the one-pass backward and the Gram kernel.  The launchers are the only symbols that cross parts (hidden
-// visibility: none of them is part of the C ABI).  Without the macro (tools/ builds) everything is one translation unit.
+// whole file, but only emits its share of the kernel instantiations, and no kernel is emitted by a part that does not launch it:
+//   part 0          the C ABI of the products, the planners' shape queries, mirror_lower_kernel (gram_finish)
+//   parts 1 2 3 6   the wave-stream / tiled GEMM launchers by (operand, epilogue) mode (the `extern template` table below)
+//   part 4          the weight-gradient kernels (wgrad_impl)
+//   part 5          the one-pass backward with bwd_fused_gw_finish_kernel, the Gram kernels (bwd_fused_launch, gram_*_launch)
+// The launchers are the only symbols that cross parts (PCOPS_HIDDEN: none of them is part of the C ABI); the sum of the
+// partial copies that closes parts 0, 4 and 5 is pcops_mlp_sum_partials2 of mlp_bn.hip, declared in common.h.  Without the
+// macro (tools/ builds) the file is one translation unit.
 #ifndef PCOPS_MLP_PART
 #define PCOPS_MLP_PART (-1)
 #endif
 #define PCOPS_PART(p_) (PCOPS_MLP_PART < 0 || PCOPS_MLP_PART == (p_))
-#define PCOPS_HIDDEN __attribute__((visibility("hidden")))
 
 #ifndef PCOPS_BF_RM
 #define PCOPS_BF_RM 1      // one-pass backward with the split-operand dW half, EdgeConv (SIDE) form: dY's pieces row-major as well (bwd_fused_kernel, RM)
@@ -70,7 +78,6 @@ constexpr int A_DYPOOLB = 6;
 // that the uncompacted instantiations carry none of it (the 64 x 64 tile lives on a 128-register budget)
 constexpr int A_DYW = 7;
 constexpr bool is_pool(int am) { return am == A_DYPOOL || am == A_DYPOOLU || am == A_DYPOOLB; }
-constexpr int kBlk = 16;        // rows per block of a compacted row set
 struct RowBlock { int g, s0; float w; int pad; };   // group, row-in-group of the block's first row, weight of that row
 // A block record read at a WAVE-UNIFORM index, through the constant address space: one s_load_dwordx4 on the scalar unit.  As
 // a plain global read hipcc issues a vector load (the table may alias the kernel's stores for all it knows), and the
@@ -1832,411 +1839,6 @@ static int launch_gemm_ws_only(GemmArgs &a, hipStream_t st) {
     return launch_gemm_ws_resolved<AM, EM>(a, pl, st);
 }
 
-// ---------------------------------------------------------------------------------------------
-// column reduction of partial statistics [P][2][N] -> double [2][N], two stages, deterministic
-constexpr int kRedSlices = 32;
-namespace {   // (non-template kernels: internal linkage, every build part carries its own copy)
-
-__global__ __launch_bounds__(256) void colreduce_stage1(int P, int N, const float *__restrict__ part,
-                                                        double *__restrict__ ws) {
-    // grid (ceil(N/32), 2, kRedSlices); thread (c = tid%32, g = tid/32)
-    __shared__ double sm[8][32];
-    const int c = blockIdx.x * 32 + (threadIdx.x & 31), g = threadIdx.x >> 5;
-    const int which = blockIdx.y, slice = blockIdx.z;
-    const int per = (P + kRedSlices - 1) / kRedSlices;
-    const int p0 = slice * per, p1 = min(P, p0 + per);
-    double s = 0.0;
-    if (c < N)
-        for (int p = p0 + g; p < p1; p += 8) s += (double)part[((long long)p * 2 + which) * N + c];
-    sm[g][threadIdx.x & 31] = s;
-    __syncthreads();
-    if (g == 0 && c < N) {
-        double t = 0.0;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) t += sm[i][threadIdx.x];
-        ws[((long long)slice * 2 + which) * N + c] = t;
-    }
-}
-
-// forward BN: statistics -> (mean, rstd, scale, shift) and the moving-average update
-__global__ __launch_bounds__(256) void bn_finalize_kernel(int N, double R, const double *__restrict__ ws,
-                                                          const float *__restrict__ pivot,
-                                                          const float *__restrict__ gamma,
-                                                          const float *__restrict__ beta, float eps,
-                                                          float decay, int unbiased,
-                                                          float *__restrict__ moving_mean,
-                                                          float *__restrict__ moving_var,
-                                                          float *__restrict__ mean_o, float *__restrict__ rstd_o,
-                                                          float *__restrict__ scale_o, float *__restrict__ shift_o) {
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= N) return;
-    double s1 = 0.0, s2 = 0.0;
-    for (int s = 0; s < kRedSlices; ++s) {
-        s1 += ws[((long long)s * 2 + 0) * N + c];
-        s2 += ws[((long long)s * 2 + 1) * N + c];
-    }
-    // the sums are those of (y - pivot) and (y - pivot)^2: the shift leaves the variance untouched and is added back
-    // to the mean; with the pivot near the mean the subtraction below no longer cancels leading digits
-    const double dm = s1 / R;
-    const double mean = dm + (pivot ? (double)pivot[c] : 0.0);
-    double var = s2 / R - dm * dm;
-    if (var < 0.0) var = 0.0;
-    const float rstd = (float)(1.0 / sqrt(var + (double)eps));
-    const float sc = gamma[c] * rstd;
-    mean_o[c] = (float)mean;
-    rstd_o[c] = rstd;
-    scale_o[c] = sc;
-    shift_o[c] = beta[c] - (float)mean * sc;
-    if (moving_mean) {
-        const double uv = (unbiased && R > 1.0) ? var * (R / (R - 1.0)) : var;
-        moving_mean[c] = decay * moving_mean[c] + (1.f - decay) * (float)mean;
-        moving_var[c] = decay * moving_var[c] + (1.f - decay) * (float)uv;
-    }
-}
-
-// eval-mode BN: moving statistics -> (scale, shift)
-__global__ __launch_bounds__(256) void bn_eval_coeffs_kernel(int N, const float *__restrict__ gamma,
-                                                             const float *__restrict__ beta,
-                                                             const float *__restrict__ mm,
-                                                             const float *__restrict__ mv, float eps,
-                                                             float *__restrict__ scale_o,
-                                                             float *__restrict__ shift_o) {
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= N) return;
-    const float sc = gamma[c] * (1.0f / sqrtf(mv[c] + eps));
-    scale_o[c] = sc;
-    shift_o[c] = beta[c] - mm[c] * sc;
-}
-
-// backward BN: sums (sum G, sum G*Y) -> dgamma, dbeta and the dY = p*G + q*Y + t coefficient vectors
-__global__ __launch_bounds__(256) void bn_bwd_coeffs_kernel(int N, double R, const double *__restrict__ ws,
-                                                            const float *__restrict__ gamma,
-                                                            const float *__restrict__ mean,
-                                                            const float *__restrict__ rstd,
-                                                            float *__restrict__ dgamma, float *__restrict__ dbeta,
-                                                            float *__restrict__ p_o, float *__restrict__ q_o,
-                                                            float *__restrict__ t_o) {
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= N) return;
-    double sg = 0.0, sgy = 0.0;
-    for (int s = 0; s < kRedSlices; ++s) {
-        sg += ws[((long long)s * 2 + 0) * N + c];
-        sgy += ws[((long long)s * 2 + 1) * N + c];
-    }
-    const double mu = mean[c], rs = rstd[c], g = gamma[c];
-    const double dga = (sgy - mu * sg) * rs;
-    const double p = g * rs;
-    const double q = -p * rs * dga / R;
-    const double t = -p * sg / R - q * mu;
-    dgamma[c] = (float)dga;
-    dbeta[c] = (float)sg;
-    p_o[c] = (float)p;
-    q_o[c] = (float)q;
-    t_o[c] = (float)t;
-}
-
-// ---------------------------------------------------------------------------------------------
-// out[g][c] = max_s relu(scale[c]*Y[g*S+s][c] + shift[c]); argmax = first s reaching it
-__global__ __launch_bounds__(256) void bn_relu_maxpool_kernel(long long G, int S, int C,
-                                                              const float *__restrict__ Y,
-                                                              const float *__restrict__ scale,
-                                                              const float *__restrict__ shift,
-                                                              float *__restrict__ out,
-                                                              unsigned char *__restrict__ argmax,
-                                                              float *__restrict__ ysel) {
-    const int c4n = C / 4;
-    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < G * c4n; e += (long long)gridDim.x * 256) {
-        const long long g = e / c4n;
-        const int c = (int)(e - g * c4n) * 4;
-        const float4 sc = *reinterpret_cast<const float4 *>(scale + c);
-        const float4 sh = *reinterpret_cast<const float4 *>(shift + c);
-        float m[4] = {-1.f, -1.f, -1.f, -1.f};
-        float ys[4] = {0.f, 0.f, 0.f, 0.f};
-        int am[4] = {0, 0, 0, 0};
-        const float *base = Y + (g * S) * C + c;
-        for (int s = 0; s < S; ++s) {
-            const float4 y = *reinterpret_cast<const float4 *>(base + (long long)s * C);
-            const float a0 = fmaxf(fmaf(y.x, sc.x, sh.x), 0.f), a1 = fmaxf(fmaf(y.y, sc.y, sh.y), 0.f);
-            const float a2 = fmaxf(fmaf(y.z, sc.z, sh.z), 0.f), a3 = fmaxf(fmaf(y.w, sc.w, sh.w), 0.f);
-            if (a0 > m[0]) { m[0] = a0; am[0] = s; ys[0] = y.x; }
-            if (a1 > m[1]) { m[1] = a1; am[1] = s; ys[1] = y.y; }
-            if (a2 > m[2]) { m[2] = a2; am[2] = s; ys[2] = y.z; }
-            if (a3 > m[3]) { m[3] = a3; am[3] = s; ys[3] = y.w; }
-        }
-        *reinterpret_cast<float4 *>(out + g * C + c) = make_float4(m[0], m[1], m[2], m[3]);
-        if (argmax) {
-            uchar4 q;
-            q.x = (unsigned char)am[0]; q.y = (unsigned char)am[1];
-            q.z = (unsigned char)am[2]; q.w = (unsigned char)am[3];
-            *reinterpret_cast<uchar4 *>(argmax + g * C + c) = q;
-        }
-        if (ysel) *reinterpret_cast<float4 *>(ysel + g * C + c) = make_float4(ys[0], ys[1], ys[2], ys[3]);
-    }
-}
-
-// the same over COMPACTED rows: group g owns rows 16 bstart[g] .. 16 bstart[g+1] - 1 (its real members followed by
-// copies of member 0 up to the block boundary; the first maximiser wins, so a copy is never the arg-max)
-__global__ __launch_bounds__(256) void bn_relu_maxpool_rows_kernel(long long G, int C, const float *__restrict__ Y,
-                                                                   const float *__restrict__ scale,
-                                                                   const float *__restrict__ shift,
-                                                                   const int *__restrict__ bstart,
-                                                                   float *__restrict__ out,
-                                                                   unsigned char *__restrict__ argmax,
-                                                                   float *__restrict__ ysel) {
-    const int c4n = C / 4;
-    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < G * c4n; e += (long long)gridDim.x * 256) {
-        const long long g = e / c4n;
-        const int c = (int)(e - g * c4n) * 4;
-        const float4 sc = *reinterpret_cast<const float4 *>(scale + c);
-        const float4 sh = *reinterpret_cast<const float4 *>(shift + c);
-        float m[4] = {-1.f, -1.f, -1.f, -1.f};
-        float ys[4] = {0.f, 0.f, 0.f, 0.f};
-        int am[4] = {0, 0, 0, 0};
-        const long long r0 = (long long)bstart[g] * kBlk;
-        const int S = (bstart[g + 1] - bstart[g]) * kBlk;
-        const float *base = Y + r0 * C + c;
-        // S is a multiple of 16: eight rows are requested before the first is looked at (a row-at-a-time loop has ONE
-        // 16-byte load in flight per lane and spends 93 % of its wave cycles in s_waitcnt)
-        for (int s0 = 0; s0 < S; s0 += 8) {
-            float4 yv[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) yv[u] = *reinterpret_cast<const float4 *>(base + (long long)(s0 + u) * C);
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const float4 y = yv[u];
-                const int s = s0 + u;
-                const float a0 = fmaxf(fmaf(y.x, sc.x, sh.x), 0.f), a1 = fmaxf(fmaf(y.y, sc.y, sh.y), 0.f);
-                const float a2 = fmaxf(fmaf(y.z, sc.z, sh.z), 0.f), a3 = fmaxf(fmaf(y.w, sc.w, sh.w), 0.f);
-                if (a0 > m[0]) { m[0] = a0; am[0] = s; ys[0] = y.x; }
-                if (a1 > m[1]) { m[1] = a1; am[1] = s; ys[1] = y.y; }
-                if (a2 > m[2]) { m[2] = a2; am[2] = s; ys[2] = y.z; }
-                if (a3 > m[3]) { m[3] = a3; am[3] = s; ys[3] = y.w; }
-            }
-        }
-        *reinterpret_cast<float4 *>(out + g * C + c) = make_float4(m[0], m[1], m[2], m[3]);
-        if (argmax) {
-            uchar4 q;
-            q.x = (unsigned char)am[0]; q.y = (unsigned char)am[1];
-            q.z = (unsigned char)am[2]; q.w = (unsigned char)am[3];
-            *reinterpret_cast<uchar4 *>(argmax + g * C + c) = q;
-        }
-        if (ysel) *reinterpret_cast<float4 *>(ysel + g * C + c) = make_float4(ys[0], ys[1], ys[2], ys[3]);
-    }
-}
-
-// compacted rows: per group the best of its blocks' partial extrema (written by the fused epilogue per 16-row block:
-// the selected raw value and its row-in-group); sign(gamma) decides between max and min, the first block wins ties
-// (blocks are in row order) -> ysel, arg-max, out = relu(scale * ysel + shift)
-__global__ __launch_bounds__(256) void pool_combine_rows_kernel(long long total, int C, const float *__restrict__ ypart,
-                                                                const unsigned char *__restrict__ ppart,
-                                                                const float *__restrict__ gamma,
-                                                                const float *__restrict__ scale,
-                                                                const float *__restrict__ shift,
-                                                                const int *__restrict__ bstart, float *__restrict__ out,
-                                                                unsigned char *__restrict__ argmax,
-                                                                float *__restrict__ ysel) {
-    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
-        const long long g = e / C;
-        const int c = (int)(e - g * C);
-        const float sg = gamma[c] < 0.f ? -1.f : 1.f;
-        const int b0 = bstart[g], b1 = bstart[g + 1];
-        float best = ypart[(long long)b0 * C + c];
-        int arg = ppart[(long long)b0 * C + c];
-        for (int bk = b0 + 1; bk < b1; ++bk) {
-            const float y = ypart[(long long)bk * C + c];
-            if (y * sg > best * sg) { best = y; arg = ppart[(long long)bk * C + c]; }
-        }
-        out[e] = fmaxf(fmaf(best, scale[c], shift[c]), 0.f);
-        if (argmax) argmax[e] = (unsigned char)arg;
-        if (ysel) ysel[e] = best;
-    }
-}
-
-// pooled output from the fused epilogue's selected raw values: out = relu(scale * ysel + shift)
-__global__ __launch_bounds__(256) void pool_select_kernel(long long total, int C, const float *__restrict__ ysel,
-                                                          const float *__restrict__ scale,
-                                                          const float *__restrict__ shift, float *__restrict__ out) {
-    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
-        const int c = (int)(e % C);
-        out[e] = fmaxf(fmaf(ysel[e], scale[c], shift[c]), 0.f);
-    }
-}
-
-// the two BN-backward sums of a max-pooled layer from (gpool, y at the selected row): stats [P][2][C];
-// one workgroup per `groups_per_block` groups, threads = (row lane, column quad), 16-byte loads
-__global__ __launch_bounds__(256) void pool_bwd_stats_sel_kernel(long long G, int C, const float *__restrict__ gpool,
-                                                                 const float *__restrict__ ysel,
-                                                                 const float *__restrict__ scale,
-                                                                 const float *__restrict__ shift,
-                                                                 float *__restrict__ stats, int groups_per_block,
-                                                                 float *__restrict__ gmasked) {
-    extern __shared__ float sm[];                     // [RL][2][C]
-    const int c4n = C / 4;
-    const int RL = c4n >= 256 ? 1 : 256 / c4n;
-    const int rl = c4n >= 256 ? 0 : threadIdx.x / c4n;
-    const long long g0 = (long long)blockIdx.x * groups_per_block;
-    const long long g1 = min(G, g0 + groups_per_block);
-    for (int cq = threadIdx.x % (c4n >= 256 ? 256 : c4n); cq < c4n; cq += 256) {
-        const int c = cq * 4;
-        const float4 sc = *reinterpret_cast<const float4 *>(scale + c);
-        const float4 sh = *reinterpret_cast<const float4 *>(shift + c);
-        float a1[4] = {0.f, 0.f, 0.f, 0.f}, a2[4] = {0.f, 0.f, 0.f, 0.f};
-        if (rl < RL)
-            for (long long g = g0 + rl; g < g1; g += RL) {
-                const float4 y = *reinterpret_cast<const float4 *>(ysel + g * C + c);
-                const float4 gp = *reinterpret_cast<const float4 *>(gpool + g * C + c);
-                const float gm0 = fmaf(y.x, sc.x, sh.x) > 0.f ? gp.x : 0.f;
-                const float gm1 = fmaf(y.y, sc.y, sh.y) > 0.f ? gp.y : 0.f;
-                const float gm2 = fmaf(y.z, sc.z, sh.z) > 0.f ? gp.z : 0.f;
-                const float gm3 = fmaf(y.w, sc.w, sh.w) > 0.f ? gp.w : 0.f;
-                if (gmasked) *reinterpret_cast<float4 *>(gmasked + g * C + c) = make_float4(gm0, gm1, gm2, gm3);
-                a1[0] += gm0; a1[1] += gm1; a1[2] += gm2; a1[3] += gm3;
-                a2[0] = fmaf(gm0, y.x, a2[0]); a2[1] = fmaf(gm1, y.y, a2[1]);
-                a2[2] = fmaf(gm2, y.z, a2[2]); a2[3] = fmaf(gm3, y.w, a2[3]);
-            }
-        if (rl < RL) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                sm[(rl * 2 + 0) * C + c + e] = a1[e];
-                sm[(rl * 2 + 1) * C + c + e] = a2[e];
-            }
-        }
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < 2 * C; i += 256) {
-        const int which = i / C, c = i % C;
-        float t = 0.f;
-        for (int l = 0; l < RL; ++l) t += sm[(l * 2 + which) * C + c];
-        stats[((long long)blockIdx.x * 2 + which) * C + c] = t;
-    }
-}
-
-// ... of a pooled gradient that arrives in TWO pieces and / or strided (an EdgeConv output that feeds the next layer and a column
-// block of the concatenation, dgcnn.py:39-81: autograd's sum was a 134 MB launch of its own, a strided piece a copy): the pieces
-// are added while the sums are taken and leave as ONE contiguous tensor gsum [G][C] for the data-gradient kernel behind
-__global__ __launch_bounds__(256) void pool_bwd_stats_sum_kernel(long long G, int C, const float *__restrict__ ga, long long lda,
-                                                                 const float *__restrict__ gb, long long ldb,
-                                                                 const float *__restrict__ ysel,
-                                                                 const float *__restrict__ scale,
-                                                                 const float *__restrict__ shift,
-                                                                 float *__restrict__ stats, int groups_per_block,
-                                                                 float *__restrict__ gsum) {
-    extern __shared__ float sm[];                     // [RL][2][C]
-    const int c4n = C / 4;
-    const int RL = c4n >= 256 ? 1 : 256 / c4n;
-    const int rl = c4n >= 256 ? 0 : threadIdx.x / c4n;
-    const long long g0 = (long long)blockIdx.x * groups_per_block;
-    const long long g1 = min(G, g0 + groups_per_block);
-    for (int cq = threadIdx.x % (c4n >= 256 ? 256 : c4n); cq < c4n; cq += 256) {
-        const int c = cq * 4;
-        const float4 sc = *reinterpret_cast<const float4 *>(scale + c);
-        const float4 sh = *reinterpret_cast<const float4 *>(shift + c);
-        float a1[4] = {0.f, 0.f, 0.f, 0.f}, a2[4] = {0.f, 0.f, 0.f, 0.f};
-        if (rl < RL)
-            for (long long g = g0 + rl; g < g1; g += RL) {
-                const float4 y = *reinterpret_cast<const float4 *>(ysel + g * C + c);
-                float4 gp = *reinterpret_cast<const float4 *>(ga + g * lda + c);
-                if (gb) {
-                    const float4 g2 = *reinterpret_cast<const float4 *>(gb + g * ldb + c);
-                    gp.x += g2.x; gp.y += g2.y; gp.z += g2.z; gp.w += g2.w;
-                }
-                *reinterpret_cast<float4 *>(gsum + g * C + c) = gp;
-                const float gm0 = fmaf(y.x, sc.x, sh.x) > 0.f ? gp.x : 0.f;
-                const float gm1 = fmaf(y.y, sc.y, sh.y) > 0.f ? gp.y : 0.f;
-                const float gm2 = fmaf(y.z, sc.z, sh.z) > 0.f ? gp.z : 0.f;
-                const float gm3 = fmaf(y.w, sc.w, sh.w) > 0.f ? gp.w : 0.f;
-                a1[0] += gm0; a1[1] += gm1; a1[2] += gm2; a1[3] += gm3;
-                a2[0] = fmaf(gm0, y.x, a2[0]); a2[1] = fmaf(gm1, y.y, a2[1]);
-                a2[2] = fmaf(gm2, y.z, a2[2]); a2[3] = fmaf(gm3, y.w, a2[3]);
-            }
-        if (rl < RL) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                sm[(rl * 2 + 0) * C + c + e] = a1[e];
-                sm[(rl * 2 + 1) * C + c + e] = a2[e];
-            }
-        }
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < 2 * C; i += 256) {
-        const int which = i / C, c = i % C;
-        float t = 0.f;
-        for (int l = 0; l < RL; ++l) t += sm[(l * 2 + which) * C + c];
-        stats[((long long)blockIdx.x * 2 + which) * C + c] = t;
-    }
-}
-
-// A[r][c] = relu(scale[c]*Y[r][c] + shift[c])   (stack output without pooling)
-__global__ __launch_bounds__(256) void bn_relu_apply_kernel(long long total4, int C,
-                                                            const float *__restrict__ Y,
-                                                            const float *__restrict__ scale,
-                                                            const float *__restrict__ shift,
-                                                            float *__restrict__ out) {
-    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total4; e += (long long)gridDim.x * 256) {
-        const int c = (int)((e * 4) % C);
-        const float4 y = reinterpret_cast<const float4 *>(Y)[e];
-        const float4 sc = *reinterpret_cast<const float4 *>(scale + c);
-        const float4 sh = *reinterpret_cast<const float4 *>(shift + c);
-        float4 o;
-        o.x = fmaxf(fmaf(y.x, sc.x, sh.x), 0.f);
-        o.y = fmaxf(fmaf(y.y, sc.y, sh.y), 0.f);
-        o.z = fmaxf(fmaf(y.z, sc.z, sh.z), 0.f);
-        o.w = fmaxf(fmaf(y.w, sc.w, sh.w), 0.f);
-        reinterpret_cast<float4 *>(out)[e] = o;
-    }
-}
-
-// backward of relu(bn(Y)) for a materialised upstream grad Gout: Gm = Gout*[a>0], partial sums
-// (sum Gm, sum Gm*Y) per 128-row tile: stats [P][2][C]
-__global__ __launch_bounds__(256) void relu_mask_stats_kernel(long long R, int C, const float *__restrict__ Gout,
-                                                              const float *__restrict__ Y,
-                                                              const float *__restrict__ scale,
-                                                              const float *__restrict__ shift,
-                                                              float *__restrict__ Gm, float *__restrict__ stats,
-                                                              int rows_per_block) {
-    // block: 256 threads = (C/4 column-quads) x (256/(C/4)) row lanes ... generic: thread owns column quad
-    // cq = tid % c4n and strides rows by 256 / c4n; requires c4n <= 256 and 256 % c4n == 0 or loops columns.
-    extern __shared__ float sm[];  // [rl][2][C]
-    const int c4n = C / 4;
-    const int rl = max(1, 256 / c4n);  // row lanes
-    const long long r0 = (long long)blockIdx.x * rows_per_block;
-    const long long r1 = min(R, r0 + rows_per_block);
-    for (int cq = threadIdx.x % min(c4n, 256); cq < c4n; cq += 256) {
-        const int c = cq * 4;
-        const float4 sc = *reinterpret_cast<const float4 *>(scale + c);
-        const float4 sh = *reinterpret_cast<const float4 *>(shift + c);
-        float a1[4] = {0, 0, 0, 0}, a2[4] = {0, 0, 0, 0};
-        const int lane_r = (c4n >= 256) ? 0 : threadIdx.x / c4n;
-        if (lane_r < rl) {
-            for (long long r = r0 + lane_r; r < r1; r += rl) {
-                const float4 g = *reinterpret_cast<const float4 *>(Gout + r * C + c);
-                const float4 y = *reinterpret_cast<const float4 *>(Y + r * C + c);
-                float4 o;
-                o.x = fmaf(y.x, sc.x, sh.x) > 0.f ? g.x : 0.f;
-                o.y = fmaf(y.y, sc.y, sh.y) > 0.f ? g.y : 0.f;
-                o.z = fmaf(y.z, sc.z, sh.z) > 0.f ? g.z : 0.f;
-                o.w = fmaf(y.w, sc.w, sh.w) > 0.f ? g.w : 0.f;
-                *reinterpret_cast<float4 *>(Gm + r * C + c) = o;
-                a1[0] += o.x; a1[1] += o.y; a1[2] += o.z; a1[3] += o.w;
-                a2[0] = fmaf(o.x, y.x, a2[0]); a2[1] = fmaf(o.y, y.y, a2[1]);
-                a2[2] = fmaf(o.z, y.z, a2[2]); a2[3] = fmaf(o.w, y.w, a2[3]);
-            }
-            for (int e = 0; e < 4; ++e) {
-                sm[(lane_r * 2 + 0) * C + c + e] = a1[e];
-                sm[(lane_r * 2 + 1) * C + c + e] = a2[e];
-            }
-        }
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < 2 * C; i += 256) {
-        const int which = i / C, c = i % C;
-        float t = 0.f;
-        for (int l = 0; l < rl; ++l) t += sm[(l * 2 + which) * C + c];
-        stats[((long long)blockIdx.x * 2 + which) * C + c] = t;
-    }
-}
-
-}  // namespace
 // ---------------------------------------------------------------------------------------------
 // wgrad: dW[K][N] (+)= A^T dY over a slice of rows; both operands rebuilt from raw tensors and loaded
 // fragment-shaped straight from HBM (lane = (row parity, channel group); VK/VN consecutive channels per
@@ -4541,11 +4143,13 @@ __global__ __launch_bounds__(512, 1) void gram_rows_bf3_kernel(GramArgs a) {
     }
 }
 
-// lower triangle of a symmetric K x K result from its upper one
+// lower triangle of a symmetric K x K result from its upper one (launched by gram_finish: part 0)
+#if PCOPS_PART(0)
 static __global__ __launch_bounds__(256) void mirror_lower_kernel(int K, float *__restrict__ g) {
     const int i = blockIdx.x, tid = threadIdx.x;
     for (int j = tid; j < i; j += 256) g[(long long)i * K + j] = g[(long long)j * K + i];
 }
+#endif
 
 static bool gram_full_on() {
     static const bool on = pcops_env_switch("PCOPS_GRAM_FULL", true);
@@ -4659,242 +4263,13 @@ static bool wgrad_pc_shape_ok(long long M, int K, int N, int ldx, bool narrow = 
     return wgrad_pc_plan(a, &pl, narrow);
 }
 
-namespace {
-// sum partials [P][L] -> out[L] (deterministic): 64 consecutive elements x 4 partial lanes per workgroup
-__global__ __launch_bounds__(256) void sum_partials_kernel(int P, long long L, const float *__restrict__ part,
-                                                           float *__restrict__ out) {
-    __shared__ double sm[4][64];
-    const int c = threadIdx.x & 63, pl = threadIdx.x >> 6;
-    const long long i = (long long)blockIdx.x * 64 + c;
-    double s = 0.0;
-    if (i < L)
-        for (int p = pl; p < P; p += 4) s += (double)part[(long long)p * L + i];
-    sm[pl][c] = s;
-    __syncthreads();
-    if (pl == 0 && i < L) out[i] = (float)((sm[0][c] + sm[1][c]) + (sm[2][c] + sm[3][c]));
-}
-
-// two adjacent reductions in one launch: blocks [0, ceil(L/64)) sum part -> out, the rest sum part2 -> out2
-__global__ __launch_bounds__(1024) void sum_partials2_kernel(int P, long long L, const float *__restrict__ part,
-                                                             float *__restrict__ out, long long L2,
-                                                             const float *__restrict__ part2,
-                                                             float *__restrict__ out2) {
-    __shared__ double sm[16][64];
-    const long long nb1 = (L + 63) / 64;
-    const bool second = (long long)blockIdx.x >= nb1;
-    const long long len = second ? L2 : L;
-    const float *src = second ? part2 : part;
-    float *dst = second ? out2 : out;
-    const int c = threadIdx.x & 63, pl = threadIdx.x >> 6;
-    const long long i = ((long long)blockIdx.x - (second ? nb1 : 0)) * 64 + c;
-    double s = 0.0;
-    if (i < len)
-        for (int p = pl; p < P; p += 16) s += (double)src[(long long)p * len + i];
-    sm[pl][c] = s;
-    __syncthreads();
-    if (pl == 0 && i < len) {
-        double t = 0.0;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) t += sm[k][c];
-        dst[i] = (float)t;
-    }
-}
-
-// Wt[n][k] = W[k][n]
-__global__ __launch_bounds__(256) void transpose_kernel(int K, int N, const float *__restrict__ W,
-                                                        float *__restrict__ Wt) {
-    __shared__ float t[32][33];
-    const int k0 = blockIdx.y * 32, n0 = blockIdx.x * 32;
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-    for (int i = ty; i < 32; i += 8)
-        if (k0 + i < K && n0 + tx < N) t[i][tx] = W[(long long)(k0 + i) * N + n0 + tx];
-    __syncthreads();
-    for (int i = ty; i < 32; i += 8)
-        if (n0 + i < N && k0 + tx < K) Wt[(long long)(n0 + i) * K + k0 + tx] = t[tx][i];
-}
-
-// dY = (t + p.G) + q.Y over whole rows (the data gradient of a first layer whose "gather" is the identity: the whole-cloud
-// group of sample_and_group_all, pointnet_util.py:59-84) -- it was an addcmul and an in-place addcmul over the tensor
-__global__ __launch_bounds__(256) void dy_apply_kernel(long long total4, int N4, const float4 *__restrict__ G,
-                                                       const float4 *__restrict__ Y, const float4 *__restrict__ p,
-                                                       const float4 *__restrict__ q, const float4 *__restrict__ t,
-                                                       float4 *__restrict__ out) {
-    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total4; e += (long long)gridDim.x * 256) {
-        const int c = (int)(e % N4);
-        const float4 g = G[e], y = Y[e], pp = p[c], qq = q[c], tt = t[c];
-        out[e] = make_float4((tt.x + g.x * pp.x) + y.x * qq.x, (tt.y + g.y * pp.y) + y.y * qq.y,
-                             (tt.z + g.z * pp.z) + y.z * qq.z, (tt.w + g.w * pp.w) + y.w * qq.w);
-    }
-}
-
-// The algebraic top layer's small operands in ONE launch (they were a transpose, an elementwise product, an addcmul and a
-// matrix-vector launch of the small-GEMM kernel):
-//   Wt[n][k] = W[k][n],  Wq[k][n] = W[k][n] q[n],  u[n] = q[n] b[n] + t[n]  (tile row 0 writes u),
-//   v[k] = sum_n W[k][n] u[n]  (the workgroups behind the tiles: eight rows each, a row per half-wave pair, lanes over n)
-__global__ __launch_bounds__(256) void pool_top_prep_kernel(int K, int N, const float *__restrict__ W,
-                                                            const float *__restrict__ b, const float *__restrict__ q,
-                                                            const float *__restrict__ tt, float *__restrict__ Wt,
-                                                            float *__restrict__ Wq, float *__restrict__ u,
-                                                            float *__restrict__ v) {
-    __shared__ float t[32][33];
-    const int tiles_y = (K + 31) / 32;
-    if ((int)blockIdx.y >= tiles_y) {                    // v: eight rows per workgroup, numbered along x then y
-        if (v == nullptr) return;
-        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-        const int vb = ((int)blockIdx.y - tiles_y) * (int)gridDim.x + (int)blockIdx.x;
-        for (int rr = 0; rr < 2; ++rr) {
-            const int k = vb * 8 + wave * 2 + rr;
-            if (k >= K) continue;                        // (wave-uniform)
-            float acc = 0.f;
-            for (int n = lane; n < N; n += 64) acc = fmaf(W[(long long)k * N + n], q[n] * b[n] + tt[n], acc);
-#pragma unroll
-            for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, 64);
-            if (lane == 0) v[k] = acc;
-        }
-        return;
-    }
-    const int k0 = blockIdx.y * 32, n0 = blockIdx.x * 32;
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-    const float qn = n0 + tx < N ? q[n0 + tx] : 0.f;
-    for (int i = ty; i < 32; i += 8)
-        if (k0 + i < K && n0 + tx < N) {
-            const float w = W[(long long)(k0 + i) * N + n0 + tx];
-            t[i][tx] = w;
-            Wq[(long long)(k0 + i) * N + n0 + tx] = w * qn;
-        }
-    if (blockIdx.y == 0 && ty == 0 && n0 + tx < N) u[n0 + tx] = qn * b[n0 + tx] + tt[n0 + tx];
-    __syncthreads();
-    for (int i = ty; i < 32; i += 8)
-        if (n0 + i < N && k0 + tx < K) Wt[(long long)(n0 + i) * K + k0 + tx] = t[tx][i];
-}
-
-// ... and the sums that close its weight and bias gradient (an in-place add, an outer product, six vector launches and the
-// matrix-vector launch for xw = xsum^T W, which the first row of workgroups now adds up per column, k ascending):
-//   dW[k][n] = (dW[k][n] + Ssp[k][n]) + xsum[k] u[n],   db[n] = (cfsum[n] + q[n] (xw[n] + R b[n])) + R t[n]
-__global__ __launch_bounds__(256) void pool_top_finish_kernel(int K, int N, float R, float *__restrict__ dW,
-                                                              const float *__restrict__ Ssp, const float *__restrict__ xsum,
-                                                              const float *__restrict__ u, const float *__restrict__ cfsum,
-                                                              const float *__restrict__ q, const float *__restrict__ W,
-                                                              const float *__restrict__ b, const float *__restrict__ tt,
-                                                              float *__restrict__ db) {
-    if (blockIdx.y < 8) {
-        // db: 32 columns per workgroup (block 8 x + y of the 256-column strip x), eight lanes of k per column, four chains each
-        // (a column's K loads would otherwise wait on one another: 61 us for K = 512 with one thread per column)
-        __shared__ float red[8][32];
-        const int c = threadIdx.x & 31, kl = threadIdx.x >> 5;
-        const int n = (blockIdx.x * 8 + blockIdx.y) * 32 + c;
-        float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-        if (n < N) {
-            int k = kl;
-            for (; k + 24 < K; k += 32) {
-                a0 = fmaf(xsum[k], W[(long long)k * N + n], a0);
-                a1 = fmaf(xsum[k + 8], W[(long long)(k + 8) * N + n], a1);
-                a2 = fmaf(xsum[k + 16], W[(long long)(k + 16) * N + n], a2);
-                a3 = fmaf(xsum[k + 24], W[(long long)(k + 24) * N + n], a3);
-            }
-            for (; k < K; k += 8) a0 = fmaf(xsum[k], W[(long long)k * N + n], a0);
-        }
-        red[kl][c] = (a0 + a1) + (a2 + a3);
-        __syncthreads();
-        if (kl == 0 && n < N) {
-            const float xw = ((red[0][c] + red[1][c]) + (red[2][c] + red[3][c])) + ((red[4][c] + red[5][c]) + (red[6][c] + red[7][c]));
-            db[n] = (cfsum[n] + q[n] * (xw + R * b[n])) + R * tt[n];
-        }
-        return;
-    }
-    const int n = blockIdx.x * 256 + threadIdx.x;
-    if (n >= N) return;
-    const float un = u[n];
-    const int kb = ((int)blockIdx.y - 8) * 8;
-    for (int k = kb; k < min(K, kb + 8); ++k) {
-        const long long e = (long long)k * N + n;
-        dW[e] = (dW[e] + Ssp[e]) + xsum[k] * un;
-    }
-}
-
-// few partial rows (P <= kFusedRows): column reduction and the per-channel finalisation in ONE launch.
-// block = 32 columns x 32 row lanes; the row-lane totals meet in LDS in a fixed order (deterministic)
-[[maybe_unused]] constexpr int kFusedRows = 1024;
-
-__device__ __forceinline__ bool fused_col_sums(int P, int N, const float *__restrict__ part, double &s1, double &s2,
-                                               int &c) {
-    __shared__ double sm[2][32][32];
-    c = blockIdx.x * 32 + (threadIdx.x & 31);
-    const int g = threadIdx.x >> 5;
-    double a1 = 0.0, a2 = 0.0;
-    if (c < N)
-        for (int p = g; p < P; p += 32) {
-            a1 += (double)part[((long long)p * 2 + 0) * N + c];
-            a2 += (double)part[((long long)p * 2 + 1) * N + c];
-        }
-    sm[0][g][threadIdx.x & 31] = a1;
-    sm[1][g][threadIdx.x & 31] = a2;
-    __syncthreads();
-    if (g != 0 || c >= N) return false;
-    s1 = s2 = 0.0;
-#pragma unroll
-    for (int i = 0; i < 32; ++i) { s1 += sm[0][i][threadIdx.x]; s2 += sm[1][i][threadIdx.x]; }
-    return true;
-}
-
-__global__ __launch_bounds__(1024) void bn_finalize_fused_kernel(int P, int N, double R, const float *__restrict__ part,
-                                                                const float *__restrict__ pivot,
-                                                                const float *__restrict__ gamma,
-                                                                const float *__restrict__ beta, float eps,
-                                                                float decay, int unbiased,
-                                                                float *__restrict__ moving_mean,
-                                                                float *__restrict__ moving_var,
-                                                                float *__restrict__ mean_o,
-                                                                float *__restrict__ rstd_o,
-                                                                float *__restrict__ scale_o,
-                                                                float *__restrict__ shift_o) {
-    double s1, s2;
-    int c;
-    if (!fused_col_sums(P, N, part, s1, s2, c)) return;
-    const double dm = s1 / R;                                    // sums of (y - pivot), (y - pivot)^2: see bn_finalize_kernel
-    const double mean = dm + (pivot ? (double)pivot[c] : 0.0);
-    double var = s2 / R - dm * dm;
-    if (var < 0.0) var = 0.0;
-    const float rstd = (float)(1.0 / sqrt(var + (double)eps));
-    const float sc = gamma[c] * rstd;
-    mean_o[c] = (float)mean;
-    rstd_o[c] = rstd;
-    scale_o[c] = sc;
-    shift_o[c] = beta[c] - (float)mean * sc;
-    if (moving_mean) {
-        const double uv = (unbiased && R > 1.0) ? var * (R / (R - 1.0)) : var;
-        moving_mean[c] = decay * moving_mean[c] + (1.f - decay) * (float)mean;
-        moving_var[c] = decay * moving_var[c] + (1.f - decay) * (float)uv;
-    }
-}
-
-__global__ __launch_bounds__(1024) void bn_bwd_coeffs_fused_kernel(int P, int N, double R,
-                                                                  const float *__restrict__ part,
-                                                                  const float *__restrict__ gamma,
-                                                                  const float *__restrict__ mean,
-                                                                  const float *__restrict__ rstd,
-                                                                  float *__restrict__ dgamma,
-                                                                  float *__restrict__ dbeta, float *__restrict__ p_o,
-                                                                  float *__restrict__ q_o, float *__restrict__ t_o) {
-    double sg, sgy;
-    int c;
-    if (!fused_col_sums(P, N, part, sg, sgy, c)) return;
-    const double mu = mean[c], rs = rstd[c], g = gamma[c];
-    const double dga = (sgy - mu * sg) * rs;
-    const double p = g * rs;
-    const double q = -p * rs * dga / R;
-    const double t = -p * sg / R - q * mu;
-    dgamma[c] = (float)dga;
-    dbeta[c] = (float)sg;
-    p_o[c] = (float)p;
-    q_o[c] = (float)q;
-    t_o[c] = (float)t;
-}
-
 // Gram form of the one-pass backward's weight gradient (bwd_fused_kernel<..., GW>): the P workgroups' partials of
 // S = X^T (p.G) [K][N], Gr = X^T X [K][K], xs = X^T 1 [K] and db [N] are summed in a fixed order (in double) and combined,
 //   dW[k][n] = S[k][n] + q[n] sum_j Gr[k][j] W[j][n] + xs[k] (q[n] b[n] + t[n]),
-// one workgroup per (row k, 128 columns): K <= 64.
+// one workgroup per (row k, 128 columns): K <= 64.  (Launched by bwd_fused_launch: part 5.  The unnamed namespace is part of
+// the name the profiles know it by.)
+#if PCOPS_PART(5)
+namespace {
 __global__ __launch_bounds__(128) void bwd_fused_gw_finish_kernel(int P, int K, int N, const float *__restrict__ spart,
                                                                   const float *__restrict__ dbpart,
                                                                   const float *__restrict__ gpart,
@@ -4937,734 +4312,10 @@ __global__ __launch_bounds__(128) void bwd_fused_gw_finish_kernel(int P, int K, 
         }
     }
 }
-
-int reduce_stats(int P, int N, const float *part, double *ws, hipStream_t st) {
-    hipLaunchKernelGGL(colreduce_stage1, dim3((N + 31) / 32, 2, kRedSlices), dim3(256), 0, st, P, N, part, ws);
-    return pcops_launch_status();
-}
-
 }  // namespace
+#endif
 }  // namespace pcops_mlp
 using namespace pcops_mlp;
-
-#if PCOPS_PART(0)
-
-// ---------------------------------------------------------------------------------------------
-// Algebraic backward of a POOLED top layer  Y = X W + b,  X = relu(bn(Yprev)),  out = max_group relu(bn(Y)).
-// Its dY = p.G + q.Y + t has a DENSE part that is affine in X and a SPARSE part (one row per group and channel):
-//   dX = (p.G) W^T + X (W diag(q) W^T) + 1 (W (q.b + t))^T
-//   dW = X^T (p.G) + (X^T X) (W diag(q)) + (X^T 1) (q.b + t)^T
-// so neither gradient needs Y, and the two big products shrink from K x N to K x K (N = 2K in every SA module, N = 3.2K
-// .. 8K for the layers pooled over whole clouds).  The sparse parts are G x N row operations:
-//   pool_top_addend_kernel   per group: arg-max rows -> compact addend rows  sum_c cf[c] Wt[c][:]  + the row -> slot map
-//   pool_top_wsparse_kernel per channel: sum over the groups of cf X[arg row][:]
-// cf[g][c] = p[c] gout[g][c] [relu(bn(ysel[g][c])) > 0].  Sums run in ascending channel / group order (deterministic).
-template <int NT>      // threads: 1024 for few large groups (a wave set per segment needs the waves), 256 otherwise
-__global__ __launch_bounds__(NT) void pool_top_addend_kernel(int S, int C, int Kp, int slots_per_group,
-                                                              const float *__restrict__ gout,
-                                                              const float *__restrict__ ysel,
-                                                              const unsigned char *__restrict__ arg,
-                                                              const float *__restrict__ sc, const float *__restrict__ sh,
-                                                              const float *__restrict__ p, const float *__restrict__ Wt,
-                                                              float *__restrict__ addend, int *__restrict__ rowmap) {
-    // hit-driven: the (row, channel) pairs with a non-zero coefficient are compacted, sorted by (row, channel) with a
-    // bitonic network in LDS (<= 1024 keys), cut into one segment per row, and a 16-lane set per segment adds the
-    // segment's Wt rows in ascending channel order.  Work is O(hits log hits), not O(S C).
-    __shared__ float cf[1024];
-    __shared__ unsigned key[1024];                 // row << 10 | channel, 0xFFFFFFFF padding
-    __shared__ int segstart[1025];                 // first sorted position of segment i
-    __shared__ int wcount[16];
-    constexpr int CPT = 1024 / NT, NW = NT / 64;     // channels per thread, waves
-    const long long g = blockIdx.x;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    for (int s = tid; s < S; s += NT) rowmap[g * S + s] = -1;
-    // ---- coefficients and compaction of the hits (C <= 1024: four channels per thread)
-    float v[CPT];
-    unsigned row[CPT];
-    unsigned long long hm[CPT];
-#pragma unroll
-    for (int i = 0; i < CPT; ++i) {
-        const int c = i * NT + tid;
-        v[i] = 0.f;
-        row[i] = 0;
-        if (c < C) {
-            const long long e = g * C + c;
-            v[i] = fmaf(ysel[e], sc[c], sh[c]) > 0.f ? p[c] * gout[e] : 0.f;
-            row[i] = arg[e];
-            cf[c] = v[i];
-        }
-        hm[i] = __ballot(v[i] != 0.f);
-        if (lane == 0) wcount[i * NW + wave] = __popcll(hm[i]);
-        key[c] = 0xFFFFFFFFu;
-    }
-    __syncthreads();
-    int nh = 0, base[CPT];
-#pragma unroll
-    for (int i = 0; i < CPT; ++i)
-        for (int w = 0; w < NW; ++w) {
-            if (w == wave) base[i] = nh;
-            nh += wcount[i * NW + w];
-        }
-    if (nh == 0) return;                           // a chunk that won no channel (layers pooled over whole clouds)
-#pragma unroll
-    for (int i = 0; i < CPT; ++i)
-        if (v[i] != 0.f)
-            key[base[i] + __popcll(hm[i] & ((1ull << lane) - 1ull))] = (row[i] << 10) | (unsigned)(i * NT + tid);
-    int n2 = 64;
-    while (n2 < nh) n2 <<= 1;
-    // ---- bitonic sort of key[0 .. n2): n2 / 2 compare-exchanges per stage
-    for (int k = 2; k <= n2; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            __syncthreads();
-            for (int t = tid; t < n2 / 2; t += NT) {
-                const int lo = ((t & ~(j - 1)) << 1) | (t & (j - 1)), hi = lo | j;
-                const unsigned a = key[lo], b = key[hi];
-                if ((a > b) == ((lo & k) == 0)) { key[lo] = b; key[hi] = a; }
-            }
-        }
-    __syncthreads();
-    // ---- segments: a new one wherever the row changes (positions i * 256 + tid, i.e. ascending over (i, wave, lane))
-    bool first[CPT];
-    unsigned long long fm[CPT];
-    unsigned mykey[CPT];
-#pragma unroll
-    for (int i = 0; i < CPT; ++i) {
-        const int pos = i * NT + tid;
-        mykey[i] = pos < nh ? key[pos] : 0u;
-        first[i] = pos < nh && (pos == 0 || (key[pos - 1] >> 10) != (mykey[i] >> 10));
-        fm[i] = __ballot(first[i]);
-    }
-    __syncthreads();                               // wcount is reused
-    if (lane == 0)
-#pragma unroll
-        for (int i = 0; i < CPT; ++i) wcount[i * NW + wave] = __popcll(fm[i]);
-    __syncthreads();
-    int nseg = 0, sbase[CPT];
-#pragma unroll
-    for (int i = 0; i < CPT; ++i)
-        for (int w = 0; w < NW; ++w) {
-            if (w == wave) sbase[i] = nseg;
-            nseg += wcount[i * NW + w];
-        }
-#pragma unroll
-    for (int i = 0; i < CPT; ++i)
-        if (first[i]) {
-            const int si = sbase[i] + __popcll(fm[i] & ((1ull << lane) - 1ull));
-            segstart[si] = i * NT + tid;
-            rowmap[g * S + (mykey[i] >> 10)] = (int)(g * slots_per_group) + si;
-        }
-    if (tid == 0) segstart[nseg] = nh;
-    __syncthreads();
-    // ---- a 16-lane set per segment; lane q of the set owns the float4 columns q, q + 16, ... of the Kp-wide row
-    constexpr int KQ = 8;                          // Kp <= 512
-    const int sub = lane >> 4, q = lane & 15;
-    const int kq = (Kp + 63) / 64;
-    for (int si = wave * 4 + sub; si < nseg; si += NW * 4) {
-        const int e0 = segstart[si], e1 = segstart[si + 1];
-        float4 acc[KQ];
-#pragma unroll
-        for (int i = 0; i < KQ; ++i) acc[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-        for (int e = e0; e < e1; ++e) {
-            const int c = key[e] & 1023u;
-            const float w = cf[c];
-            const float *src = Wt + (long long)c * Kp;
-#pragma unroll
-            for (int i = 0; i < KQ; ++i) {
-                const int k = (i * 16 + q) * 4;
-                if (i < kq && k < Kp) {
-                    const float4 wt = *reinterpret_cast<const float4 *>(src + k);
-                    acc[i].x = fmaf(w, wt.x, acc[i].x); acc[i].y = fmaf(w, wt.y, acc[i].y);
-                    acc[i].z = fmaf(w, wt.z, acc[i].z); acc[i].w = fmaf(w, wt.w, acc[i].w);
-                }
-            }
-        }
-        float *dst = addend + (g * slots_per_group + si) * (long long)Kp;
-#pragma unroll
-        for (int i = 0; i < KQ; ++i) {
-            const int k = (i * 16 + q) * 4;
-            if (i < kq && k < Kp) *reinterpret_cast<float4 *>(dst + k) = acc[i];
-        }
-    }
-}
-
-// one workgroup per channel c, its 4 waves take a quarter of the groups each:
-//   Ssp[k][c] = sum_g cf[g][c] X[g S + arg[g][c]][k],  cfsum[c] = sum_g cf[g][c]      (wave partials added in order)
-__global__ __launch_bounds__(256) void pool_top_wsparse_kernel(long long G, int S, int C, int Kp,
-                                                               const float *__restrict__ gout,
-                                                               const float *__restrict__ ysel,
-                                                               const unsigned char *__restrict__ arg,
-                                                               const float *__restrict__ sc, const float *__restrict__ sh,
-                                                               const float *__restrict__ p,
-                                                               const float *__restrict__ Yprev,
-                                                               const float *__restrict__ psc, const float *__restrict__ psh,
-                                                               float *__restrict__ Ssp, float *__restrict__ cfsum) {
-    constexpr int KR = 8, U = 8;                                    // Kp <= 64 KR; hit rows in flight
-    __shared__ float red[4][64 * KR + 1];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int c = blockIdx.x;
-    const float scc = sc[c], shc = sh[c], pc = p[c];
-    const int kr = (Kp + 63) / 64;                                  // registers in use (wave-uniform)
-    float asc[KR], ash[KR], acc[KR];
-#pragma unroll
-    for (int i = 0; i < KR; ++i) {
-        const int k = lane + 64 * i;
-        asc[i] = (k < Kp && psc) ? psc[k] : 1.f;
-        ash[i] = (k < Kp && psc) ? psh[k] : 0.f;
-        acc[i] = 0.f;
-    }
-    float csum = 0.f;
-    const long long gq = (G + 3) / 4;
-    const long long gend = (wave + 1) * gq < G ? (wave + 1) * gq : G;
-    for (long long g0 = wave * gq; g0 < gend; g0 += 64) {
-        const long long g = g0 + lane;
-        float cf = 0.f;
-        int row = 0;
-        if (g < gend) {
-            const long long e = g * C + c;
-            cf = fmaf(ysel[e], scc, shc) > 0.f ? pc * gout[e] : 0.f;
-            row = arg[e];
-        }
-        unsigned long long hits = __ballot(cf != 0.f);
-        while (hits) {                                              // wave-uniform: U hit groups at a time
-            float w[U];
-            long long r[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                w[u] = 0.f;
-                r[u] = 0;
-                if (hits) {
-                    const int l = __builtin_ctzll(hits);
-                    hits &= hits - 1;
-                    w[u] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, cf), l));
-                    r[u] = (g0 + l) * S + __builtin_amdgcn_readlane(row, l);
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < KR; ++i) {
-                if (i >= kr) break;
-                const int k = lane + 64 * i;
-                float x[U];
-#pragma unroll
-                for (int u = 0; u < U; ++u) x[u] = (k < Kp) ? Yprev[r[u] * Kp + k] : 0.f;
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    const float xv = psc ? fmaxf(fmaf(x[u], asc[i], ash[i]), 0.f) : x[u];
-                    acc[i] = fmaf(w[u], xv, acc[i]);
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) csum += w[u];
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < KR; ++i) red[wave][lane + 64 * i] = acc[i];
-    if (lane == 0) red[wave][64 * KR] = csum;
-    __syncthreads();
-    for (int k = threadIdx.x; k < Kp; k += 256)
-        Ssp[(long long)k * C + c] = (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]);
-    if (threadIdx.x == 0)
-        cfsum[c] = (red[0][64 * KR] + red[1][64 * KR]) + (red[2][64 * KR] + red[3][64 * KR]);
-}
-
-// ---- the two sparse halves over COMPACTED rows, for MANY SMALL groups (the grouped stacks: 32 768 groups of <= 64 rows at
-// the SSG config's second level).  The kernels above give a workgroup to a group / a channel and fetch a Kp-wide row of W^T /
-// of X per hit through L2 -- 4.3 GB of 512-byte gathers each at that shape.  Here the reused operand sits in LDS:
-//   pool_top_addend_rows_kernel   W^T [C][KP] resident (128 KB), persistent workgroups, four groups per round
-//   pool_top_wsparse_rows_kernel  group-major: a group's rows of X (contiguous in the compacted stack) staged once
-// The row of slot (g, a) is 16 block_start[g] + a; argmax is the row-in-group in compacted numbering.  Sums in a fixed order.
-//
-// addend (PCOPS_OPT_POOL_TOP_ROWS_PIPELINED = 0; 1 takes pool_top_addend_rows_pipe_kernel below): a quarter of the workgroup
-// (256 threads = the C <= 256 channels) owns one group per round.  The channels that
-// picked row r are a C-bit mask in LDS (integer OR: the result does not depend on the order); KP / 4 lanes per row then add
-// cf[c] Wt[c][:] over the set bits in ascending channel order and write the row ONCE.  The addend is indexed by the
-// compacted row itself (slot = row), rowmap [row] = row or -1.
-template <int KP>
-__global__ __launch_bounds__(1024) void pool_top_addend_rows_kernel(int G, int C, const float *__restrict__ gout,
-                                                                    const float *__restrict__ ysel,
-                                                                    const unsigned char *__restrict__ arg,
-                                                                    const float *__restrict__ sc, const float *__restrict__ sh,
-                                                                    const float *__restrict__ p, const float *__restrict__ Wt,
-                                                                    const int *__restrict__ block_start,
-                                                                    float *__restrict__ addend, int *__restrict__ rowmap) {
-    constexpr int LPR = KP / 4, RPP = 256 / LPR;      // lanes per row (a float4 each), rows per pass of a quarter
-    constexpr int MAXR = 128, MW = 8;                 // rows per group, mask words per row (C <= 256)
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    float *Ws = lds;                                  // [C][KP]
-    float *cf = Ws + (size_t)C * KP;                  // [4][256]
-    unsigned *mask = reinterpret_cast<unsigned *>(cf + 4 * 256);      // [4][MAXR][MW]
-    const int tid = threadIdx.x, sub = tid >> 8, c = tid & 255;
-    for (int e = tid; e < C * (KP / 4); e += 1024)
-        reinterpret_cast<float4 *>(Ws)[e] = reinterpret_cast<const float4 *>(Wt)[e];
-    const float scc = c < C ? sc[c] : 0.f, shc = c < C ? sh[c] : 0.f, pc = c < C ? p[c] : 0.f;
-    float *mycf = cf + sub * 256;
-    unsigned *mymask = mask + sub * MAXR * MW;
-    const int q = c % LPR, rsub = c / LPR;
-    float v = 0.f;
-    int row = 0, base = 0, nrows = 0;
-    auto fetch = [&](long long g) {
-        v = 0.f; row = 0; base = 0; nrows = 0;
-        if (g < G) {
-            const int b0 = block_start[g];
-            base = kBlk * b0;
-            nrows = kBlk * (block_start[g + 1] - b0);
-            nrows = nrows < MAXR ? nrows : MAXR;
-            if (c < C) {
-                const long long e = g * C + c;
-                v = fmaf(ysel[e], scc, shc) > 0.f ? pc * gout[e] : 0.f;
-                row = arg[e];
-            }
-        }
-    };
-    fetch((long long)blockIdx.x * 4 + sub);
-    for (long long g0 = (long long)blockIdx.x * 4; g0 < G; g0 += (long long)gridDim.x * 4) {
-        const float cv = v;
-        const int crow = row, cbase = base, cnrows = nrows;
-        __syncthreads();                              // the previous round's rows are written (and Ws is there)
-        mycf[c] = cv;
-#pragma unroll
-        for (int i = 0; i < MAXR * MW / 256; ++i) mymask[c + 256 * i] = 0u;
-        __syncthreads();
-        if (cv != 0.f && crow < cnrows) atomicOr(&mymask[crow * MW + (c >> 5)], 1u << (c & 31));
-        __syncthreads();
-        fetch(g0 + (long long)gridDim.x * 4 + sub);  // the next round's coefficients fly under this round's rows
-        for (int r = rsub; r < cnrows; r += RPP) {
-            float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-            bool any = false;
-#pragma unroll
-            for (int w = 0; w < MW; ++w) {
-                unsigned mm = mymask[r * MW + w];
-                any = any || mm != 0u;
-                while (mm) {
-                    const int ch = 32 * w + __builtin_ctz(mm);
-                    mm &= mm - 1u;
-                    const float cw = mycf[ch];
-                    const float4 wt = *reinterpret_cast<const float4 *>(&Ws[ch * KP + 4 * q]);
-                    acc.x = fmaf(cw, wt.x, acc.x); acc.y = fmaf(cw, wt.y, acc.y);
-                    acc.z = fmaf(cw, wt.z, acc.z); acc.w = fmaf(cw, wt.w, acc.w);
-                }
-            }
-            const long long ri = (long long)cbase + r;
-            if (any) *reinterpret_cast<float4 *>(&addend[ri * KP + 4 * q]) = acc;
-            if (q == 0) rowmap[ri] = any ? (int)ri : -1;
-        }
-    }
-}
-
-// addend, software-pipelined (PCOPS_OPT_POOL_TOP_ROWS_PIPELINED = 1): a WAVE owns a group, so nothing of the walk crosses a wave
-// and the loop holds no barrier at all (one __syncthreads behind the staging of W^T).  Lane l keeps the coefficient and the
-// arg-max row of the channels l, l + 64, l + 128, l + 192 in registers; the channels that picked row r are then the ballots
-// of (row == r), one 64-bit scalar per 64 channels, bit order = channel order -- no mask in LDS, no atomic, nothing to zero.
-// The 64 lanes hold one row (KP / 64 floats each): the hit sequence is wave-uniform, so the bit scan, the loop control and the
-// coefficient (v_readlane) are scalar work and a hit costs the vector pipe an address, a read and one fmaf (v_pk_fma at KP = 128).
-// Pipeline: the first hit of each 64-channel word is a SLOT -- the four W^T reads of row r + 1 are issued (named register
-// sets A / B, the loop written two rows per trip) before the fmaf of row r.  An empty word's bit scan gives -1: its slot
-// reads the row in FRONT of the word's first channel (W^T is staged behind one spare row for word 0) and the coefficient of
-// lane 63, without a select (scalar instructions issue once in four cycles per SIMD: they, not the vector pipe, set this
-// kernel's pace), and its fmaf is skipped by a wave-uniform branch.  A word's second and later hits (256 channels spread
-// over the group's rows: 0.6 per row at the SSG shape) follow in a plain loop.  Per row and column the fmaf chain is the
-// former kernel's: the row's hits in ascending channel order from 0 -- the same bits.  The next group's (gout, ysel, arg)
-// are requested before this group's rows, the block_start pair of the group after it one trip earlier.
-template <int KP, int MAXR>
-__global__ __launch_bounds__(1024) void pool_top_addend_rows_pipe_kernel(int G, int C, const float *__restrict__ gout,
-                                                                         const float *__restrict__ ysel,
-                                                                         const unsigned char *__restrict__ arg,
-                                                                         const float *__restrict__ sc, const float *__restrict__ sh,
-                                                                         const float *__restrict__ p, const float *__restrict__ Wt,
-                                                                         const int *__restrict__ block_start,
-                                                                         float *__restrict__ addend, int *__restrict__ rowmap) {
-    constexpr int VEC = KP / 64, NW = 4;              // floats of a row per lane; 64-channel words (C <= 256)
-    static_assert(VEC == 1 || VEC == 2, "a row is one or two floats per lane");
-    static_assert(MAXR == 64 || MAXR == 128, "lane l answers for the rows l and l + 64 of a group");
-    typedef float rowv_t __attribute__((ext_vector_type(VEC)));
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    float *Ws = lds + KP;                             // [C][KP] behind one spare row ("channel -1": read, never used)
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);       // wave-uniform: the group index stays scalar
-    for (int e = tid; e < C * (KP / 4); e += 1024)
-        reinterpret_cast<float4 *>(Ws)[e] = reinterpret_cast<const float4 *>(Wt)[e];
-    if (tid < KP) lds[tid] = 0.f;
-    float scc[NW], shc[NW], pc[NW];
-#pragma unroll
-    for (int k = 0; k < NW; ++k) {
-        const int c = lane + 64 * k;
-        scc[k] = c < C ? sc[c] : 0.f; shc[k] = c < C ? sh[c] : 0.f; pc[k] = c < C ? p[c] : 0.f;
-    }
-    __syncthreads();                                  // W^T is there; the only barrier
-    // the group in flight: its raw triples (the coefficient is formed at use) and its rows
-    float fy[NW], fg[NW];
-    int fa[NW], fbase = 0, fn = 0;
-    int nb0 = 0, nb1 = 0;                             // block_start pair of the group fetch() takes next (scalar loads)
-    auto pair = [&](long long g) {
-        if (g < G) { nb0 = block_start[g]; nb1 = block_start[g + 1]; }
-    };
-    auto fetch = [&](long long g) {
-        fbase = 0; fn = 0;
-        if (g < G) {
-            fbase = kBlk * nb0;
-            fn = kBlk * (nb1 - nb0);
-            fn = fn < MAXR ? fn : MAXR;
-        }
-#pragma unroll
-        for (int k = 0; k < NW; ++k) {
-            const int c = lane + 64 * k;
-            fy[k] = 0.f; fg[k] = 0.f; fa[k] = 0;
-            if (g < G && c < C) {
-                const long long e = g * C + c;
-                fy[k] = ysel[e]; fg[k] = gout[e]; fa[k] = arg[e];
-            }
-        }
-    };
-    const long long stride = (long long)gridDim.x * 16;
-    long long g = (long long)blockIdx.x * 16 + wave;
-    // s_ff1_i32_b64: the lowest set bit, -1 for an empty word (__builtin_ctzll leaves that case undefined)
-    auto ff1 = [](unsigned long long m) {
-        int l;
-        asm("s_ff1_i32_b64 %0, %1" : "=s"(l) : "s"(m));
-        return l;
-    };
-    // one scalar instruction each (as C++ the mask is built with a 64-bit shift and, for the hit rows, kept in vector registers)
-    auto bit_clear = [](unsigned long long &m, int l) { asm("s_bitset0_b64 %0, %1" : "+s"(m) : "s"(l)); };
-    auto bit_set = [](unsigned long long &m, int l) { asm("s_bitset1_b64 %0, %1" : "+s"(m) : "s"(l)); };
-    // lane l's bytes of the row in front of word k's first channel: slot address = wbase[k] + (bit + 1) * KP * 4
-    // (signed: word 0's base is -KP * 4 bytes from Ws, the spare row)
-    int wbase[NW];
-#pragma unroll
-    for (int k = 0; k < NW; ++k) wbase[k] = ((64 * k - 1) * KP + VEC * lane) * 4;
-    auto wrow = [&](int k, int l) {
-        return *reinterpret_cast<const rowv_t *>(reinterpret_cast<const char *>(Ws) + (wbase[k] + (l + 1) * (KP * 4)));
-    };
-    pair(g);
-    fetch(g);
-    pair(g + stride);
-    for (; g < G; g += stride) {
-        int t0 = 0, t1 = 0;                           // the pair of the group after the next: requested here, waited for in
-        if (g + 2 * stride < G) {                     // front of the row loop, whose lgkmcnt waits then count LDS reads only
-            t0 = block_start[g + 2 * stride];
-            t1 = block_start[g + 2 * stride + 1];
-        }
-        float cfv[NW];
-        int rowv[NW];                                 // the row a channel adds to; -1: none (no coefficient, or beyond the group)
-#pragma unroll
-        for (int k = 0; k < NW; ++k) {
-            cfv[k] = fmaf(fy[k], scc[k], shc[k]) > 0.f ? pc[k] * fg[k] : 0.f;
-            rowv[k] = (cfv[k] != 0.f && fa[k] < fn) ? fa[k] : -1;
-        }
-        const int base = fbase, nrows = fn;
-        fetch(g + stride);                            // the next group's coefficients fly under this group's rows
-        nb0 = t0; nb1 = t1;
-        asm volatile("" ::"s"(nb0), "s"(nb1));
-        // a register set: per word the hits, the first of them (-1: none), its W^T read and its coefficient
-        struct Set {
-            rowv_t w[NW];
-            float cf[NW];
-            unsigned long long m[NW];
-            int l[NW];
-        };
-        auto coef = [&](int k, int l) {
-            return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, cfv[k]), l));
-        };
-        auto issue = [&](int r, Set &s) {
-#pragma unroll
-            for (int k = 0; k < NW; ++k) {
-                s.m[k] = __ballot(rowv[k] == r);
-                s.l[k] = ff1(s.m[k]);
-                s.cf[k] = coef(k, s.l[k]);
-                s.w[k] = wrow(k, s.l[k]);
-            }
-        };
-        unsigned long long anylo = 0ull, anyhi = 0ull; // the rows of the group with a hit (scalar)
-        // the addend within a 32-bit byte offset: checked by the launcher
-        char *const dst = reinterpret_cast<char *>(addend) + VEC * 4 * lane;
-        auto finish = [&](int r, const Set &s) {
-            rowv_t acc = 0.f;
-            bool any = false;
-#pragma unroll
-            for (int k = 0; k < NW; ++k) {
-                if (s.l[k] >= 0) {
-                    asm volatile("" ::: "memory");    // a branch, not a select: an empty slot costs the vector pipe nothing
-                    any = true;
-#pragma unroll
-                    for (int i = 0; i < VEC; ++i) acc[i] = fmaf(s.cf[k], s.w[k][i], acc[i]);
-                    unsigned long long mm = s.m[k];
-                    bit_clear(mm, s.l[k]);
-                    while (mm) {
-                        const int l = ff1(mm);
-                        bit_clear(mm, l);
-                        const float cw = coef(k, l);
-                        const rowv_t wt = wrow(k, l);
-#pragma unroll
-                        for (int i = 0; i < VEC; ++i) acc[i] = fmaf(cw, wt[i], acc[i]);
-                    }
-                }
-            }
-            if (any) {
-                *reinterpret_cast<rowv_t *>(dst + (unsigned)(base + r) * (unsigned)(KP * 4)) = acc;
-                if (MAXR == 64 || r < 64) bit_set(anylo, r); else bit_set(anyhi, r - 64);
-            }
-        };
-        Set A, B;
-        issue(0, A);
-        for (int r = 0; r < nrows; r += 2) {
-            issue(r + 1, B);                          // a row beyond the group has no hit: dead channels carry row -1
-            finish(r, A);
-            issue(r + 2, A);
-            if (r + 1 < nrows) finish(r + 1, B);
-        }
-        // rowmap [row] = row or -1 for every row of the group: lane l writes row l (and l + 64)
-        if (lane < nrows) rowmap[(long long)base + lane] = (anylo >> lane) & 1ull ? base + lane : -1;
-        if (MAXR > 64 && lane + 64 < nrows) rowmap[(long long)base + lane + 64] = (anyhi >> lane) & 1ull ? base + lane + 64 : -1;
-    }
-}
-
-// wsparse: thread = channel, KP accumulators in registers; a workgroup walks its share of the groups, stages the group's
-// rows of relu(bn(X)) (row stride KP + 1: the lanes of a wave read DIFFERENT rows at the same k -- conflict-free) and adds
-// cf[g][c] X_g[arg][:].  part [gridDim.x][KP][C], part2 [gridDim.x][C]: summed in a fixed order by sum_partials2_kernel.
-template <int KP>
-__global__ __launch_bounds__(256) void pool_top_wsparse_rows_kernel(int G, int C, int maxr, const float *__restrict__ gout,
-                                                                    const float *__restrict__ ysel,
-                                                                    const unsigned char *__restrict__ arg,
-                                                                    const float *__restrict__ sc, const float *__restrict__ sh,
-                                                                    const float *__restrict__ p,
-                                                                    const float *__restrict__ Yprev,
-                                                                    const float *__restrict__ psc, const float *__restrict__ psh,
-                                                                    const int *__restrict__ block_start,
-                                                                    float *__restrict__ part, float *__restrict__ part2) {
-    constexpr int LD = KP + 1, K4 = KP / 4;
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    float *Xs = lds;                                  // [maxr][LD]
-    const int tid = threadIdx.x, c = tid;             // C <= 256
-    const float scc = c < C ? sc[c] : 0.f, shc = c < C ? sh[c] : 0.f, pc = c < C ? p[c] : 0.f;
-    // a thread stages the column quad tid % K4 of the rows tid / K4, + 256 / K4, ...: its BN coefficients are fixed
-    const int k4 = tid % K4, r0 = tid / K4;
-    const float4 asc = *reinterpret_cast<const float4 *>(psc + 4 * k4), ash = *reinterpret_cast<const float4 *>(psh + 4 * k4);
-    float acc[KP];
-#pragma unroll
-    for (int k = 0; k < KP; ++k) acc[k] = 0.f;
-    float csum = 0.f;
-    for (int g = blockIdx.x; g < G; g += gridDim.x) {
-        const int b0 = block_start[g];
-        int nrows = kBlk * (block_start[g + 1] - b0);
-        nrows = nrows < maxr ? nrows : maxr;
-        const float *src = Yprev + (long long)kBlk * b0 * KP;
-        float cfv = 0.f;
-        int row = 0;
-        if (c < C) {
-            const long long e = (long long)g * C + c;
-            cfv = fmaf(ysel[e], scc, shc) > 0.f ? pc * gout[e] : 0.f;
-            row = arg[e];
-            if (row >= nrows) { row = 0; cfv = 0.f; }
-        }
-        __syncthreads();                              // the previous group's rows are consumed
-        for (int r = r0; r < nrows; r += 256 / K4) {
-            float4 x = *reinterpret_cast<const float4 *>(src + (long long)r * KP + 4 * k4);
-            x.x = fmaxf(fmaf(x.x, asc.x, ash.x), 0.f); x.y = fmaxf(fmaf(x.y, asc.y, ash.y), 0.f);
-            x.z = fmaxf(fmaf(x.z, asc.z, ash.z), 0.f); x.w = fmaxf(fmaf(x.w, asc.w, ash.w), 0.f);
-            float *d = &Xs[r * LD + 4 * k4];
-            d[0] = x.x; d[1] = x.y; d[2] = x.z; d[3] = x.w;
-        }
-        __syncthreads();
-        const float *xr = &Xs[row * LD];
-#pragma unroll
-        for (int k = 0; k < KP; ++k) acc[k] = fmaf(cfv, xr[k], acc[k]);
-        csum += cfv;
-    }
-    if (c < C) {
-        float *dst = part + (long long)blockIdx.x * KP * C + c;
-#pragma unroll
-        for (int k = 0; k < KP; ++k) dst[(long long)k * C] = acc[k];
-        part2[(long long)blockIdx.x * C + c] = csum;
-    }
-}
-
-// wsparse, software-pipelined (PCOPS_OPT_POOL_TOP_ROWS_PIPELINED = 1): the same thread = channel walk, but the NEXT group's rows
-// (NR float4 per thread), its (gout, ysel, arg) triple and the block_start pair of the group after it are requested into
-// registers before this group's accumulation, the LDS image is double-buffered (ONE barrier per group: a buffer is rewritten two
-// groups later, behind the barrier that follows its last read), and a hit row is read with KP / 4 ds_read_b128 -- row stride
-// KP + 4 floats = an odd number of 16-byte units, so the lanes of a read group that hold different rows mod 16 meet different
-// units of the bank row (KP + 1 is the stride for ds_read_b32).  Same partition of the groups over the grid, same partial layout.
-template <int KP, int NR>
-__global__ __launch_bounds__(256) void pool_top_wsparse_rows_pipe_kernel(int G, int C, int maxr, const float *__restrict__ gout,
-                                                                         const float *__restrict__ ysel,
-                                                                         const unsigned char *__restrict__ arg,
-                                                                         const float *__restrict__ sc, const float *__restrict__ sh,
-                                                                         const float *__restrict__ p,
-                                                                         const float *__restrict__ Yprev,
-                                                                         const float *__restrict__ psc, const float *__restrict__ psh,
-                                                                         const int *__restrict__ block_start,
-                                                                         float *__restrict__ part, float *__restrict__ part2) {
-    constexpr int LD = KP + 4, K4 = KP / 4, RPP = 256 / K4;       // rows staged per pass of the workgroup
-    static_assert(NR * RPP == 64 || NR * RPP == 128, "the launcher sizes an LDS image at 64 or 128 rows (maxr <= NR RPP)");
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int tid = threadIdx.x, c = tid;                         // C <= 256
-    const float scc = c < C ? sc[c] : 0.f, shc = c < C ? sh[c] : 0.f, pc = c < C ? p[c] : 0.f;
-    const int k4 = tid % K4, r0 = tid / K4;
-    const float4 asc = *reinterpret_cast<const float4 *>(psc + 4 * k4), ash = *reinterpret_cast<const float4 *>(psh + 4 * k4);
-    float acc[KP];
-#pragma unroll
-    for (int k = 0; k < KP; ++k) acc[k] = 0.f;
-    float csum = 0.f;
-    const int grid = gridDim.x;
-    // the group in flight: its rows, its raw triple (the coefficient is formed at use, not behind the load) and its row count
-    float4 px[NR];
-    float fy = 0.f, fg = 0.f;
-    int fa = 0, fn = 0;
-    int nb0 = 0, nb1 = 0;                                         // block_start pair of the group fetch() takes next
-    auto pair = [&](int g) {
-        if (g < G) { nb0 = block_start[g]; nb1 = block_start[g + 1]; }
-    };
-    // every request is unconditional: rows beyond the group's (and every row of a group beyond the last) lie outside the
-    // buffer descriptor and read as zeros, the triple is read at a clamped index and dropped at use (fn == 0, c >= C)
-    auto fetch = [&](int g) {
-        const int n = g < G ? kBlk * (nb1 - nb0) : 0;
-        fn = n < maxr ? n : maxr;
-        const __amdgpu_buffer_rsrc_t rx = make_rsrc(Yprev + (long long)kBlk * (g < G ? nb0 : 0) * KP, (long long)fn * KP * 4);
-#pragma unroll
-        for (int j = 0; j < NR; ++j) px[j] = buf_load4(rx, (unsigned)((r0 + RPP * j) * KP + 4 * k4) * 4u, 0u);
-        const long long e = (long long)(g < G ? g : G - 1) * C + (c < C ? c : C - 1);
-        fy = ysel[e]; fg = gout[e]; fa = arg[e];
-    };
-    int g = blockIdx.x;
-    pair(g);
-    fetch(g);
-    pair(g + grid);
-    int buf = 0;
-    for (; g < G; g += grid) {
-        float *Xs = lds + buf * (NR * RPP * LD);                  // [NR RPP][LD]: a row beyond the group's arrives as zeros and is stored as relu(shift); never read (row < fn below)
-        int t0 = 0, t1 = 0;                                       // block_start pair of the group after the next (scalar loads: requested
-        if (g + 2 * grid < G) {                                   // here, so that the barrier below does not wait for them)
-            t0 = block_start[g + 2 * grid];
-            t1 = block_start[g + 2 * grid + 1];
-        }
-#pragma unroll
-        for (int j = 0; j < NR; ++j) {
-            const int r = r0 + RPP * j;
-            float4 x = px[j];
-            x.x = fmaxf(fmaf(x.x, asc.x, ash.x), 0.f); x.y = fmaxf(fmaf(x.y, asc.y, ash.y), 0.f);
-            x.z = fmaxf(fmaf(x.z, asc.z, ash.z), 0.f); x.w = fmaxf(fmaf(x.w, asc.w, ash.w), 0.f);
-            *reinterpret_cast<float4 *>(&Xs[r * LD + 4 * k4]) = x;
-        }
-        float cfv = fmaf(fy, scc, shc) > 0.f ? pc * fg : 0.f;
-        int row = fa;
-        if (row >= fn || c >= C) { row = 0; cfv = 0.f; }
-        fetch(g + grid);                                          // the next group flies under this group's accumulation
-        nb0 = t0; nb1 = t1;
-        __syncthreads();
-        const float *xr = &Xs[row * LD];
-#pragma unroll
-        for (int q = 0; q < K4; ++q) {
-            const float4 v = *reinterpret_cast<const float4 *>(xr + 4 * q);
-            acc[4 * q] = fmaf(cfv, v.x, acc[4 * q]); acc[4 * q + 1] = fmaf(cfv, v.y, acc[4 * q + 1]);
-            acc[4 * q + 2] = fmaf(cfv, v.z, acc[4 * q + 2]); acc[4 * q + 3] = fmaf(cfv, v.w, acc[4 * q + 3]);
-        }
-        csum += cfv;
-        buf ^= 1;
-    }
-    if (c < C) {
-        float *dst = part + (long long)blockIdx.x * KP * C + c;
-#pragma unroll
-        for (int k = 0; k < KP; ++k) dst[(long long)k * C] = acc[k];
-        part2[(long long)blockIdx.x * C + c] = csum;
-    }
-}
-
-// C [M][N] = A [M][K] B [K][N] for the SMALL products around the big kernels (weights x weights: K x K Gram algebra,
-// matrix-vector rows).  One 32 x 32 tile per workgroup so that even a 512 x 512 result fills the chip; the 4 waves split
-// K and add their accumulators through LDS in a fixed order.  (Eight waves over K for the long reductions -- the partial tiles
-// meeting in the staging area -- were measured in round 6: the SSG and DGCNN steps within noise, 24.55 / 24.46 / 24.63 against
-// 24.47 / 24.44 / 25.03 k clouds/s; not kept.  Three chunks per wave in flight instead of one, 48 more registers: 19.4 against
-// 15.5 us per launch in the SSG step, profiles/r06_tail_fold_ab.txt; not kept either.)
-__device__ __forceinline__ void small_gemm_tile(int bx, int by, int M, int K, int N, const float *__restrict__ A, int lda,
-                                                         const float *__restrict__ B, int ldb, float *__restrict__ C,
-                                                         int ldc, int transA, int transB, const float *__restrict__ bias,
-                                                         float *__restrict__ colsum) {
-    // colsum (optional): column sums of B over its K rows next to the product -- the bias gradient of a fully connected layer
-    // out of its weight-gradient launch (dW = X^T dY, db = 1^T dY); the tile row 0 adds up what it stages anyway
-    __shared__ float As[4][32][17], Bs[4][16][33], red[4][32][33], cs[4][2][32];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int m0 = by * 32, n0 = bx * 32;
-    const int kchunks = (K + 15) / 16;
-    f32x16 acc;
-#pragma unroll
-    for (int v = 0; v < 16; ++v) acc[v] = 0.f;
-    float ra[8], rb[8];
-    auto fetch = [&](int ch) {
-        const int k0 = ch * 16;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int e = lane + 64 * i;
-            const int r = e >> 4, kk = e & 15;
-            // transA: A is stored [K][M] (the product is A^T ...), transB: B is stored [N][K]
-            const long long ia = transA ? (long long)(k0 + kk) * lda + m0 + r : (long long)(m0 + r) * lda + k0 + kk;
-            ra[i] = (ch < kchunks && m0 + r < M && k0 + kk < K) ? A[ia] : 0.f;
-            const int kb = e >> 5, c = e & 31;
-            const long long ib = transB ? (long long)(n0 + c) * ldb + k0 + kb : (long long)(k0 + kb) * ldb + n0 + c;
-            rb[i] = (ch < kchunks && k0 + kb < K && n0 + c < N) ? B[ib] : 0.f;
-        }
-    };
-    fetch(wave);
-    const bool sums = colsum != nullptr && by == 0;
-    float bsum = 0.f;                                // column lane & 31 over the rows (lane >> 5) + 2 i of this wave's chunks
-    for (int ch = wave; ch < kchunks; ch += 4) {
-        __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int e = lane + 64 * i;
-            As[wave][e >> 4][e & 15] = ra[i];
-            Bs[wave][e >> 5][e & 31] = rb[i];
-        }
-        if (sums) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) bsum += rb[i];
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        fetch(ch + 4);                              // the next chunk's loads fly under this chunk's MFMAs
-#pragma unroll
-        for (int st = 0; st < 8; ++st)
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(As[wave][lane & 31][2 * st + (lane >> 5)],
-                                                       Bs[wave][2 * st + (lane >> 5)][lane & 31], acc, 0, 0, 0);
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    }
-#pragma unroll
-    for (int v = 0; v < 16; ++v) red[wave][(v & 3) + 8 * (v >> 2) + 4 * (lane >> 5)][lane & 31] = acc[v];
-    cs[wave][lane >> 5][lane & 31] = bsum;
-    __syncthreads();
-    if (sums && tid < 32 && n0 + tid < N)            // fixed order: the run-to-run bits do not depend on the schedule
-        colsum[n0 + tid] = ((cs[0][0][tid] + cs[0][1][tid]) + (cs[1][0][tid] + cs[1][1][tid])) +
-                           ((cs[2][0][tid] + cs[2][1][tid]) + (cs[3][0][tid] + cs[3][1][tid]));
-    for (int e = tid; e < 32 * 32; e += 256) {
-        const int r = e >> 5, c = e & 31;
-        if (m0 + r < M && n0 + c < N)
-            C[(long long)(m0 + r) * ldc + n0 + c] =
-                ((red[0][r][c] + red[1][r][c]) + (red[2][r][c] + red[3][r][c])) + (bias ? bias[n0 + c] : 0.f);
-    }
-}
-
-__global__ __launch_bounds__(256) void small_gemm_kernel(int M, int K, int N, const float *__restrict__ A, int lda,
-                                                         const float *__restrict__ B, int ldb, float *__restrict__ C,
-                                                         int ldc, int transA, int transB, const float *__restrict__ bias,
-                                                         float *__restrict__ colsum) {
-    small_gemm_tile(blockIdx.x, blockIdx.y, M, K, N, A, lda, B, ldb, C, ldc, transA, transB, bias, colsum);
-}
-
-// TWO independent products in one launch (the data and the weight gradient of a fully connected layer, dX = dY W^T and
-// dW = X^T dY: each alone fills half the chip with 16 us of dependent chunks; the pooled top layer's W diag(q) W^T and gram W diag(q)):
-// workgroups [0, tiles0) take the first problem's tiles, the rest the second's -- one call site, the operands chosen by a uniform test
-struct SgProblem {
-    int M, K, N, lda, ldb, ldc, transA, transB;
-    const float *A, *B, *bias;
-    float *C, *colsum;
-};
-__global__ __launch_bounds__(256) void small_gemm_pair_kernel(SgProblem p0, SgProblem p1, int tiles0, int gx0, int gx1) {
-    const bool second = (int)blockIdx.x >= tiles0;
-    const int t = second ? (int)blockIdx.x - tiles0 : (int)blockIdx.x, gx = second ? gx1 : gx0;
-    small_gemm_tile(t % gx, t / gx, second ? p1.M : p0.M, second ? p1.K : p0.K, second ? p1.N : p0.N, second ? p1.A : p0.A,
-                    second ? p1.lda : p0.lda, second ? p1.B : p0.B, second ? p1.ldb : p0.ldb, second ? p1.C : p0.C,
-                    second ? p1.ldc : p0.ldc, second ? p1.transA : p0.transA, second ? p1.transB : p0.transB,
-                    second ? p1.bias : p0.bias, second ? p1.colsum : p0.colsum);
-}
-
-#endif  // PCOPS_PART(0)
 
 // ============================================================================ C ABI
 // ---- launchers of the weight-gradient, one-pass-backward and Gram kernels: build parts 4 and 5 (PCOPS_MLP_PART)
@@ -5808,9 +4459,7 @@ int wgrad_impl(WgradArgs &a, float *partial, float *dW, float *db, hipStream_t s
     const int rc = wgrad_launch(a, pl, st);
     if (rc) return rc;
     // dW and db partials are adjacent ([splits][K*N] then [splits][N]): one launch sums both
-    hipLaunchKernelGGL(sum_partials2_kernel, dim3(cdiv(L, 64) + (db ? cdiv(a.N, 64) : 0)), dim3(1024), 0, st, pl.groups, L,
-                       partial, dW, (long long)a.N, a.dbpart, db);
-    return pcops_launch_status();
+    return pcops_mlp_sum_partials2(pl.groups, L, partial, dW, (long long)a.N, a.dbpart, db, st);
 }
 #endif
 
@@ -5925,9 +4574,7 @@ int bwd_fused_launch(WgradArgs &a, bool xyz, int groups, float *partial, float *
         return pcops_launch_status();
     }
     const long long L = (long long)K * N;
-    hipLaunchKernelGGL(sum_partials2_kernel, dim3(cdiv(L, 64) + (db ? cdiv(N, 64) : 0)), dim3(1024), 0, st, groups, L,
-                       partial, dW, (long long)N, a.dbpart, db);
-    return pcops_launch_status();
+    return pcops_mlp_sum_partials2(groups, L, partial, dW, (long long)N, a.dbpart, db, st);
 }
 
 int gram_full_launch(GramArgs &g, int nbk, bool bnrelu, int gg, size_t lds, hipStream_t st) {
@@ -5953,12 +4600,6 @@ int gram_rows_bf3_launch(GramArgs &g, int gg, hipStream_t st) {
 #endif
 
 #if PCOPS_PART(0)
-static int rows_ok(const pcops_rows_t *rows) {
-    if (!rows) return PCOPS_OK;
-    PCOPS_REQUIRE_PTR(rows->blocks); PCOPS_REQUIRE_PTR(rows->block_start); PCOPS_REQUIRE_PTR(rows->rows);
-    if (reinterpret_cast<uintptr_t>(rows->blocks) & 15) return PCOPS_ERR_UNSUPPORTED;
-    return PCOPS_OK;
-}
 // a compacted row set (may be NULL: all rows) into GemmArgs / WgradArgs
 template <typename Args>
 static int set_rows(Args &a, const pcops_rows_t *rows) {
@@ -5986,10 +4627,6 @@ int pcops_mlp_stats_rows(int M) {
     int tpb = 1;
     while (tiles / tpb > 512) tpb *= 2;
     return (tiles + tpb - 1) / tpb;
-}
-
-unsigned long long pcops_mlp_reduce_workspace_bytes(int N) {
-    return (unsigned long long)kRedSlices * 2 * (unsigned long long)N * sizeof(double);
 }
 
 int pcops_mlp_gemm_fwd_rows(int M, int K, int N, const float *X, int ldx, const float *pro_scale,
@@ -6097,182 +4734,6 @@ int pcops_mlp_gemm_fwd_pool_rows_supported(int M, int K, int N) {
     a.M = M; a.K = K; a.N = N; a.ldx = K; a.ldy = N; a.pool_sub = 1;
     WsPlan pl;
     return ws_enabled() && ws_plan(a, A_BNRELU, &pl) ? 1 : 0;
-}
-
-int pcops_mlp_pool_combine_rows(long long G, int C, const float *ypart, const unsigned char *ppart,
-                                const float *gamma, const float *scale, const float *shift,
-                                const pcops_rows_t *rows, float *out, unsigned char *argmax, float *ysel,
-                                pcops_stream_t stream) {
-    PCOPS_REQUIRE_SHAPE(G >= 0 && C >= 1);
-    if (G == 0) return PCOPS_OK;
-    PCOPS_REQUIRE_PTR(ypart); PCOPS_REQUIRE_PTR(ppart); PCOPS_REQUIRE_PTR(gamma); PCOPS_REQUIRE_PTR(scale);
-    PCOPS_REQUIRE_PTR(shift); PCOPS_REQUIRE_PTR(out); PCOPS_REQUIRE_PTR(rows);
-    const int rrc = rows_ok(rows);
-    if (rrc) return rrc;
-    const long long total = G * C;
-    const unsigned grid = cdiv(total, 256) < 16384u ? cdiv(total, 256) : 16384u;
-    hipLaunchKernelGGL(pool_combine_rows_kernel, dim3(grid), dim3(256), 0, as_stream(stream), total, C, ypart, ppart,
-                       gamma, scale, shift, rows->block_start, out, argmax, ysel);
-    return pcops_launch_status();
-}
-
-int pcops_mlp_pool_select(long long G, int C, const float *ysel, const float *scale, const float *shift,
-                          float *out, pcops_stream_t stream) {
-    PCOPS_REQUIRE_SHAPE(G >= 0 && C >= 1);
-    if (G == 0) return PCOPS_OK;
-    PCOPS_REQUIRE_PTR(ysel); PCOPS_REQUIRE_PTR(scale); PCOPS_REQUIRE_PTR(shift); PCOPS_REQUIRE_PTR(out);
-    const long long total = G * C;
-    const unsigned grid = cdiv(total, 256) < 16384u ? cdiv(total, 256) : 16384u;
-    hipLaunchKernelGGL(pool_select_kernel, dim3(grid), dim3(256), 0, as_stream(stream), total, C, ysel, scale,
-                       shift, out);
-    return pcops_launch_status();
-}
-
-int pcops_mlp_bn_finalize(int P, int N, long long R, const float *stats_partial, const float *stat_pivot,
-                          void *workspace, const float *gamma, const float *beta, float eps, float decay,
-                          int unbiased_moving_var, float *moving_mean, float *moving_var, float *mean,
-                          float *rstd, float *scale, float *shift, pcops_stream_t stream) {
-    PCOPS_REQUIRE_SHAPE(P >= 1 && N >= 1 && R >= 1);
-    PCOPS_REQUIRE_PTR(stats_partial); PCOPS_REQUIRE_PTR(workspace); PCOPS_REQUIRE_PTR(gamma);
-    PCOPS_REQUIRE_PTR(beta); PCOPS_REQUIRE_PTR(mean); PCOPS_REQUIRE_PTR(rstd); PCOPS_REQUIRE_PTR(scale);
-    PCOPS_REQUIRE_PTR(shift);
-    PCOPS_REQUIRE_ARG((moving_mean == nullptr) == (moving_var == nullptr));
-    hipStream_t st = as_stream(stream);
-    if (P <= kFusedRows) {
-        hipLaunchKernelGGL(bn_finalize_fused_kernel, dim3((N + 31) / 32), dim3(1024), 0, st, P, N, (double)R,
-                           stats_partial, stat_pivot, gamma, beta, eps, decay, unbiased_moving_var, moving_mean, moving_var, mean,
-                           rstd, scale, shift);
-        return pcops_launch_status();
-    }
-    double *ws = static_cast<double *>(workspace);
-    int rc = reduce_stats(P, N, stats_partial, ws, st);
-    if (rc) return rc;
-    hipLaunchKernelGGL(bn_finalize_kernel, dim3((N + 255) / 256), dim3(256), 0, st, N, (double)R, ws, stat_pivot,
-                       gamma, beta, eps, decay, unbiased_moving_var, moving_mean, moving_var, mean, rstd, scale, shift);
-    return pcops_launch_status();
-}
-
-int pcops_mlp_bn_eval_coeffs(int N, const float *gamma, const float *beta, const float *moving_mean,
-                             const float *moving_var, float eps, float *scale, float *shift,
-                             pcops_stream_t stream) {
-    PCOPS_REQUIRE_SHAPE(N >= 1);
-    PCOPS_REQUIRE_PTR(gamma); PCOPS_REQUIRE_PTR(beta); PCOPS_REQUIRE_PTR(moving_mean);
-    PCOPS_REQUIRE_PTR(moving_var); PCOPS_REQUIRE_PTR(scale); PCOPS_REQUIRE_PTR(shift);
-    hipLaunchKernelGGL(bn_eval_coeffs_kernel, dim3((N + 255) / 256), dim3(256), 0, as_stream(stream), N, gamma,
-                       beta, moving_mean, moving_var, eps, scale, shift);
-    return pcops_launch_status();
-}
-
-int pcops_mlp_bn_relu_maxpool(long long G, int S, int C, const float *Y, const float *scale,
-                              const float *shift, float *out, unsigned char *argmax, float *ysel,
-                              pcops_stream_t stream) {
-    PCOPS_REQUIRE_SHAPE(G >= 0 && S >= 1 && S <= 256 && C >= 4 && C % 4 == 0);
-    if (G == 0) return PCOPS_OK;
-    PCOPS_REQUIRE_PTR(Y); PCOPS_REQUIRE_PTR(scale); PCOPS_REQUIRE_PTR(shift); PCOPS_REQUIRE_PTR(out);
-    const long long total = G * (C / 4);
-    const unsigned grid = cdiv(total, 256) < 32768u ? cdiv(total, 256) : 32768u;
-    hipLaunchKernelGGL(bn_relu_maxpool_kernel, dim3(grid), dim3(256), 0, as_stream(stream), G, S, C, Y, scale,
-                       shift, out, argmax, ysel);
-    return pcops_launch_status();
-}
-
-int pcops_mlp_bn_relu_maxpool_rows(long long G, int C, const float *Y, const float *scale, const float *shift,
-                                   const pcops_rows_t *rows, float *out, unsigned char *argmax, float *ysel,
-                                   pcops_stream_t stream) {
-    PCOPS_REQUIRE_SHAPE(G >= 0 && C >= 4 && C % 4 == 0);
-    if (G == 0) return PCOPS_OK;
-    PCOPS_REQUIRE_PTR(Y); PCOPS_REQUIRE_PTR(scale); PCOPS_REQUIRE_PTR(shift); PCOPS_REQUIRE_PTR(out);
-    PCOPS_REQUIRE_PTR(rows);
-    const int rrc = rows_ok(rows);
-    if (rrc) return rrc;
-    const long long total = G * (C / 4);
-    const unsigned grid = cdiv(total, 256) < 32768u ? cdiv(total, 256) : 32768u;
-    hipLaunchKernelGGL(bn_relu_maxpool_rows_kernel, dim3(grid), dim3(256), 0, as_stream(stream), G, C, Y, scale,
-                       shift, rows->block_start, out, argmax, ysel);
-    return pcops_launch_status();
-}
-
-int pcops_mlp_bn_relu_apply(long long R, int C, const float *Y, const float *scale, const float *shift,
-                            float *out, pcops_stream_t stream) {
-    PCOPS_REQUIRE_SHAPE(R >= 0 && C >= 4 && C % 4 == 0);
-    if (R == 0) return PCOPS_OK;
-    PCOPS_REQUIRE_PTR(Y); PCOPS_REQUIRE_PTR(scale); PCOPS_REQUIRE_PTR(shift); PCOPS_REQUIRE_PTR(out);
-    const long long total4 = R * C / 4;
-    const unsigned grid = cdiv(total4, 256) < 32768u ? cdiv(total4, 256) : 32768u;
-    hipLaunchKernelGGL(bn_relu_apply_kernel, dim3(grid), dim3(256), 0, as_stream(stream), total4, C, Y, scale,
-                       shift, out);
-    return pcops_launch_status();
-}
-
-// ---- backward ---------------------------------------------------------------------------------
-int pcops_mlp_bwd_stats_rows(long long R) { return (int)((R + 511) / 512); }
-int pcops_mlp_bwd_pool_stats_rows(long long G) { return (int)((G + 15) / 16); }
-
-/* Gm = Gout * [relu(bn(Y)) > 0]; partial sums (sum Gm, sum Gm*Y) -> stats [pcops_mlp_bwd_stats_rows(R)][2][C] */
-int pcops_mlp_relu_mask_stats(long long R, int C, const float *Gout, const float *Y, const float *scale,
-                              const float *shift, float *Gm, float *stats_partial, pcops_stream_t stream) {
-    PCOPS_REQUIRE_SHAPE(R >= 1 && C >= 4 && C % 4 == 0);
-    PCOPS_REQUIRE_PTR(Gout); PCOPS_REQUIRE_PTR(Y); PCOPS_REQUIRE_PTR(scale); PCOPS_REQUIRE_PTR(shift);
-    PCOPS_REQUIRE_PTR(Gm); PCOPS_REQUIRE_PTR(stats_partial);
-    const int c4n = C / 4;
-    PCOPS_REQUIRE_SHAPE(c4n >= 256 || 256 % c4n == 0);
-    const int rl = c4n >= 256 ? 1 : 256 / c4n;
-    const size_t lds = (size_t)rl * 2 * C * sizeof(float);
-    if (lds > 64 * 1024) return PCOPS_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(relu_mask_stats_kernel, dim3(pcops_mlp_bwd_stats_rows(R)), dim3(256), lds,
-                       as_stream(stream), R, C, Gout, Y, scale, shift, Gm, stats_partial, 512);
-    return pcops_launch_status();
-}
-
-int pcops_mlp_pool_bwd_stats(long long G, int C, const float *gpool, const float *ysel, const float *scale,
-                             const float *shift, float *stats_partial, float *gmasked, pcops_stream_t stream) {
-    PCOPS_REQUIRE_SHAPE(G >= 1 && C >= 4 && C % 4 == 0);
-    PCOPS_REQUIRE_PTR(gpool); PCOPS_REQUIRE_PTR(ysel); PCOPS_REQUIRE_PTR(scale);
-    PCOPS_REQUIRE_PTR(shift); PCOPS_REQUIRE_PTR(stats_partial);
-    const int c4n = C / 4;
-    const int rl = c4n >= 256 ? 1 : 256 / c4n;        // threads beyond rl * c4n idle when c4n does not divide 256
-    const size_t lds = (size_t)rl * 2 * C * sizeof(float);
-    if (lds > 64 * 1024) return PCOPS_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(pool_bwd_stats_sel_kernel, dim3(pcops_mlp_bwd_pool_stats_rows(G)), dim3(256), lds,
-                       as_stream(stream), G, C, gpool, ysel, scale, shift, stats_partial, 16, gmasked);
-    return pcops_launch_status();
-}
-
-int pcops_mlp_pool_bwd_stats_sum(long long G, int C, const float *ga, long long lda, const float *gb, long long ldb,
-                                 const float *ysel, const float *scale, const float *shift, float *stats_partial,
-                                 float *gsum, pcops_stream_t stream) {
-    PCOPS_REQUIRE_SHAPE(G >= 1 && C >= 4 && C % 4 == 0 && lda >= C && lda % 4 == 0 && (!gb || (ldb >= C && ldb % 4 == 0)));
-    PCOPS_REQUIRE_PTR(ga); PCOPS_REQUIRE_PTR(ysel); PCOPS_REQUIRE_PTR(scale);
-    PCOPS_REQUIRE_PTR(shift); PCOPS_REQUIRE_PTR(stats_partial); PCOPS_REQUIRE_PTR(gsum);
-    PCOPS_REQUIRE_ARG(((uintptr_t)ga | (uintptr_t)gb | (uintptr_t)gsum) % 16 == 0);
-    const int c4n = C / 4;
-    const int rl = c4n >= 256 ? 1 : 256 / c4n;
-    const size_t lds = (size_t)rl * 2 * C * sizeof(float);
-    if (lds > 64 * 1024) return PCOPS_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(pool_bwd_stats_sum_kernel, dim3(pcops_mlp_bwd_pool_stats_rows(G)), dim3(256), lds,
-                       as_stream(stream), G, C, ga, lda, gb, ldb, ysel, scale, shift, stats_partial, 16, gsum);
-    return pcops_launch_status();
-}
-
-int pcops_mlp_bn_bwd_coeffs(int P, int N, long long R, const float *stats_partial, void *workspace,
-                            const float *gamma, const float *mean, const float *rstd, float *dgamma,
-                            float *dbeta, float *p, float *q, float *t, pcops_stream_t stream) {
-    PCOPS_REQUIRE_SHAPE(P >= 1 && N >= 1 && R >= 1);
-    PCOPS_REQUIRE_PTR(stats_partial); PCOPS_REQUIRE_PTR(workspace); PCOPS_REQUIRE_PTR(gamma);
-    PCOPS_REQUIRE_PTR(mean); PCOPS_REQUIRE_PTR(rstd); PCOPS_REQUIRE_PTR(dgamma); PCOPS_REQUIRE_PTR(dbeta);
-    PCOPS_REQUIRE_PTR(p); PCOPS_REQUIRE_PTR(q); PCOPS_REQUIRE_PTR(t);
-    hipStream_t st = as_stream(stream);
-    if (P <= kFusedRows) {
-        hipLaunchKernelGGL(bn_bwd_coeffs_fused_kernel, dim3((N + 31) / 32), dim3(1024), 0, st, P, N, (double)R,
-                           stats_partial, gamma, mean, rstd, dgamma, dbeta, p, q, t);
-        return pcops_launch_status();
-    }
-    double *ws = static_cast<double *>(workspace);
-    int rc = reduce_stats(P, N, stats_partial, ws, st);
-    if (rc) return rc;
-    hipLaunchKernelGGL(bn_bwd_coeffs_kernel, dim3((N + 255) / 256), dim3(256), 0, st, N, (double)R, ws, gamma,
-                       mean, rstd, dgamma, dbeta, p, q, t);
-    return pcops_launch_status();
 }
 
 /* Gprev[M][Nout] = mask . (dY[M][K] Wt[K][Nout]),  dY = p.G + q.Y + t  (or the pooled form when gpool!=NULL)
@@ -6651,7 +5112,8 @@ int pcops_mlp_wgrad_xyz_rows(long long M, int K, int N, const float *off4, const
     return wgrad_impl(a, partial, dW, db, as_stream(stream));
 }
 
-/* ---- algebraic backward of a pooled top layer (see pool_top_addend_kernel) */
+/* ---- algebraic backward of a pooled top layer (pooltop_sparse.hip has the algebra and the sparse halves): the shape queries,
+ * the dense data gradient and the Gram matrix */
 static bool dgrad_top_plan(int M, int Kp, WsPlan *pl) {
     GemmArgs a = {};
     a.M = M; a.K = Kp; a.N = Kp; a.ldx = Kp; a.ldy = Kp;
@@ -6667,25 +5129,6 @@ int pcops_mlp_pool_top_supported(int M, int Kp, int N, int S) {
     return slots * Kp * 4 < (long long)kOOB ? 1 : 0;
 }
 
-/* compact arg-max rows of the data gradient: addend [(M/S) min(S,N)][Kp], rowmap [M] (slot or -1) */
-int pcops_mlp_pool_top_addend(int M, int Kp, int N, int S, const float *gout, const float *ysel,
-                            const unsigned char *argmax, const float *pool_scale, const float *pool_shift,
-                            const float *p, const float *Wt, float *addend, int *rowmap, pcops_stream_t stream) {
-    PCOPS_REQUIRE_SHAPE(M >= 1 && S >= 1 && S <= 256 && M % S == 0 && Kp % 4 == 0 && N >= 1 && N <= 65535);
-    PCOPS_REQUIRE_PTR(gout); PCOPS_REQUIRE_PTR(ysel); PCOPS_REQUIRE_PTR(argmax); PCOPS_REQUIRE_PTR(pool_scale);
-    PCOPS_REQUIRE_PTR(pool_shift); PCOPS_REQUIRE_PTR(p); PCOPS_REQUIRE_PTR(Wt); PCOPS_REQUIRE_PTR(addend);
-    PCOPS_REQUIRE_PTR(rowmap);
-    if (reinterpret_cast<uintptr_t>(Wt) & 15 || reinterpret_cast<uintptr_t>(addend) & 15) return PCOPS_ERR_UNSUPPORTED;
-    if (N > 1024 || Kp > 512) return PCOPS_ERR_UNSUPPORTED;
-    if (M / S <= 512)
-        hipLaunchKernelGGL(pool_top_addend_kernel<1024>, dim3(M / S), dim3(1024), 0, as_stream(stream), S, N, Kp,
-                           S < N ? S : N, gout, ysel, argmax, pool_scale, pool_shift, p, Wt, addend, rowmap);
-    else
-        hipLaunchKernelGGL(pool_top_addend_kernel<256>, dim3(M / S), dim3(256), 0, as_stream(stream), S, N, Kp,
-                           S < N ? S : N, gout, ysel, argmax, pool_scale, pool_shift, p, Wt, addend, rowmap);
-    return pcops_launch_status();
-}
-
 /* Gprev = mask . (relu(bn(Yprev)) Mq + addend[rowmap] + vconst), statistics as pcops_mlp_gemm_dgrad */
 int pcops_mlp_gemm_dgrad_top(int M, int Kp, const float *Yprev, const float *prev_scale, const float *prev_shift,
                              const float *Mq, const float *vconst, const float *addend, long long addend_rows,
@@ -6697,8 +5140,7 @@ int pcops_mlp_gemm_dgrad_top(int M, int Kp, const float *Yprev, const float *pre
 // what follows a single-pass Gram kernel: its gg partial copies summed into gram (upper blocks) and xsum, the lower triangle mirrored
 static int gram_finish(const GramArgs &g, int gg, float *gram, float *xsum, hipStream_t st) {
     const long long L = (long long)g.K * g.K;
-    hipLaunchKernelGGL(sum_partials2_kernel, dim3(cdiv(L, 64) + (xsum ? cdiv(g.K, 64) : 0)), dim3(1024), 0, st, gg, L,
-                       g.part, gram, (long long)g.K, g.xpart, xsum);
+    if (const int rc = pcops_mlp_sum_partials2(gg, L, g.part, gram, (long long)g.K, g.xpart, xsum, st)) return rc;
     hipLaunchKernelGGL(mirror_lower_kernel, dim3(g.K), dim3(256), 0, st, g.K, gram);
     return pcops_launch_status();
 }
@@ -6728,114 +5170,11 @@ int pcops_mlp_gram(long long M, int Kp, const float *Yprev, int ldx, const float
     return wgrad_impl(a, partial, gram, xsum, as_stream(stream));
 }
 
-/* Ssp [Kp][N] = X^T (p.G) (the arg-max rows only), cfsum [N] = column sums of p.G */
-int pcops_mlp_pool_top_wsparse(int M, int Kp, int N, int S, const float *gout, const float *ysel,
-                               const unsigned char *argmax, const float *pool_scale, const float *pool_shift,
-                               const float *p, const float *Yprev, const float *prev_scale, const float *prev_shift,
-                               float *Ssp, float *cfsum, pcops_stream_t stream) {
-    PCOPS_REQUIRE_SHAPE(M >= 1 && S >= 1 && S <= 256 && M % S == 0 && Kp >= 1 && Kp <= 512 && N >= 1);
-    PCOPS_REQUIRE_PTR(gout); PCOPS_REQUIRE_PTR(ysel); PCOPS_REQUIRE_PTR(argmax); PCOPS_REQUIRE_PTR(pool_scale);
-    PCOPS_REQUIRE_PTR(pool_shift); PCOPS_REQUIRE_PTR(p); PCOPS_REQUIRE_PTR(Yprev);
-    PCOPS_REQUIRE_ARG((prev_scale == nullptr) == (prev_shift == nullptr));
-    PCOPS_REQUIRE_PTR(Ssp); PCOPS_REQUIRE_PTR(cfsum);
-    hipLaunchKernelGGL(pool_top_wsparse_kernel, dim3(N), dim3(256), 0, as_stream(stream), (long long)(M / S), S, N,
-                       Kp, gout, ysel, argmax, pool_scale, pool_shift, p, Yprev, prev_scale, prev_shift, Ssp, cfsum);
-    return pcops_launch_status();
-}
-
-
-/* ---- the four algebraic entry points over COMPACTED rows (pcops.h): rows == NULL is the entry point without the suffix */
-static const int kTopRowsWs = 512;        // workgroups (= partial copies) of pool_top_wsparse_rows_kernel
-
-// what the two addend kernels over compacted rows need of the shape (the addend is indexed by the compacted row: at most M
-// rows of Kp floats behind a 32-bit offset); pcops_mlp_pool_top_rows_supported adds what the other three calls need
-static bool addend_rows_shape_ok(int M, int Kp, int N, int S) {
-    return S % kBlk == 0 && S <= 128 && (Kp == 64 || Kp == 128) && N <= 256 && N % 32 == 0 &&
-           (long long)M * Kp * 4 < (long long)kOOB;
-}
-
+/* ---- ... over COMPACTED rows (pcops.h): rows == NULL is the entry point without the suffix */
 int pcops_mlp_pool_top_rows_supported(int M, int Kp, int N, int S) {
     if (!pcops_mlp_pool_top_supported(M, Kp, N, S)) return 0;
     if (M < 65536 || !addend_rows_shape_ok(M, Kp, N, S)) return 0;
     return gram_full_groups(M, Kp, Kp, nullptr) ? 1 : 0;
-}
-
-unsigned long long pcops_mlp_pool_top_wsparse_rows_partial(int Kp, int N) {
-    return (unsigned long long)kTopRowsWs * ((unsigned long long)Kp * N + N);
-}
-
-int pcops_mlp_pool_top_addend_rows(int M, int Kp, int N, int S, const float *gout, const float *ysel,
-                                   const unsigned char *argmax, const float *pool_scale, const float *pool_shift,
-                                   const float *p, const float *Wt, float *addend, int *rowmap, const pcops_rows_t *rows,
-                                   pcops_stream_t stream) {
-    if (!rows) return pcops_mlp_pool_top_addend(M, Kp, N, S, gout, ysel, argmax, pool_scale, pool_shift, p, Wt, addend, rowmap, stream);
-    PCOPS_REQUIRE_SHAPE(M >= 1 && S >= 1 && M % S == 0);
-    PCOPS_REQUIRE_PTR(gout); PCOPS_REQUIRE_PTR(ysel); PCOPS_REQUIRE_PTR(argmax); PCOPS_REQUIRE_PTR(pool_scale);
-    PCOPS_REQUIRE_PTR(pool_shift); PCOPS_REQUIRE_PTR(p); PCOPS_REQUIRE_PTR(Wt); PCOPS_REQUIRE_PTR(addend);
-    PCOPS_REQUIRE_PTR(rowmap);
-    { const int rrc = rows_ok(rows); if (rrc) return rrc; }
-    // this call's own share of pcops_mlp_pool_top_rows_supported: the floor on M there belongs to the Gram pass and the dense
-    // products, the addend kernels take any number of groups
-    if (!addend_rows_shape_ok(M, Kp, N, S)) return PCOPS_ERR_UNSUPPORTED;
-    if (reinterpret_cast<uintptr_t>(Wt) & 15 || reinterpret_cast<uintptr_t>(addend) & 15) return PCOPS_ERR_UNSUPPORTED;
-    const int G = M / S;
-    const size_t lds = ((size_t)N * Kp + 4 * 256 + 4 * 128 * 8) * sizeof(float);
-    const int grid = (G + 3) / 4 < 256 ? (G + 3) / 4 : 256;
-    hipStream_t st = as_stream(stream);
-    // PCOPS_OPT_POOL_TOP_ROWS_PIPELINED = 1 (default): the wave-per-group kernel (both widths, S <= 64 and S <= 128; a wave takes
-    // a group, 16 groups per workgroup and round).  Only W^T lives in LDS, behind one spare row.  Same rows, same rowmap, same bits.
-    const bool piped = pcops_get_option(PCOPS_OPT_POOL_TOP_ROWS_PIPELINED) != 0;
-    const size_t lds_pipe = (size_t)(N + 1) * Kp * sizeof(float);     // one spare row in front
-    const int grid_pipe = (G + 15) / 16 < 256 ? (G + 15) / 16 : 256;
-    return pcops_dispatch<64, 128>(Kp, PCOPS_ERR_UNSUPPORTED, [&](auto kp_) {
-        constexpr int KP = decltype(kp_)::value;
-        auto kern = !piped ? pool_top_addend_rows_kernel<KP>
-                  : S <= 64 ? pool_top_addend_rows_pipe_kernel<KP, 64> : pool_top_addend_rows_pipe_kernel<KP, 128>;
-        return pcops_launch_lds(kern, dim3(piped ? grid_pipe : grid), dim3(1024), piped ? lds_pipe : lds, 160 * 1024, st, G, N,
-                                gout, ysel, argmax, pool_scale, pool_shift, p, Wt, rows->block_start, addend, rowmap);
-    });
-}
-
-int pcops_mlp_pool_top_wsparse_rows(int M, int Kp, int N, int S, const float *gout, const float *ysel,
-                                    const unsigned char *argmax, const float *pool_scale, const float *pool_shift,
-                                    const float *p, const float *Yprev, const float *prev_scale, const float *prev_shift,
-                                    float *Ssp, float *cfsum, float *partial, const pcops_rows_t *rows,
-                                    pcops_stream_t stream) {
-    if (!rows) return pcops_mlp_pool_top_wsparse(M, Kp, N, S, gout, ysel, argmax, pool_scale, pool_shift, p, Yprev, prev_scale, prev_shift, Ssp, cfsum, stream);
-    PCOPS_REQUIRE_SHAPE(M >= 1 && S >= 1 && M % S == 0);
-    PCOPS_REQUIRE_PTR(gout); PCOPS_REQUIRE_PTR(ysel); PCOPS_REQUIRE_PTR(argmax); PCOPS_REQUIRE_PTR(pool_scale);
-    PCOPS_REQUIRE_PTR(pool_shift); PCOPS_REQUIRE_PTR(p); PCOPS_REQUIRE_PTR(Yprev); PCOPS_REQUIRE_PTR(prev_scale);
-    PCOPS_REQUIRE_PTR(prev_shift); PCOPS_REQUIRE_PTR(Ssp); PCOPS_REQUIRE_PTR(cfsum); PCOPS_REQUIRE_PTR(partial);
-    { const int rrc = rows_ok(rows); if (rrc) return rrc; }
-    if (!pcops_mlp_pool_top_rows_supported(M, Kp, N, S)) return PCOPS_ERR_UNSUPPORTED;
-    if (reinterpret_cast<uintptr_t>(Yprev) & 15 || reinterpret_cast<uintptr_t>(prev_scale) & 15 ||
-        reinterpret_cast<uintptr_t>(prev_shift) & 15)
-        return PCOPS_ERR_UNSUPPORTED;
-    const int G = M / S;
-    const int grid = G < kTopRowsWs ? G : kTopRowsWs;
-    const size_t lds = (size_t)S * (Kp + 1) * sizeof(float);
-    float *part2 = partial + (long long)kTopRowsWs * Kp * N;
-    hipStream_t st = as_stream(stream);
-    // PCOPS_OPT_POOL_TOP_ROWS_PIPELINED = 1 (default): the software-pipelined kernel (both widths; NR = the float4 a thread
-    // holds of a group of S rows).  Same grid, so pcops_mlp_pool_top_wsparse_rows_partial covers both.
-    // two images of NR x (256 / (Kp / 4)) = 64 or 128 rows each: every row a group can have, because
-    // pcops_mlp_pool_top_rows_supported (checked above) caps S at 128
-    const int img_rows = S <= 64 ? 64 : 128;
-    if (S > img_rows) return PCOPS_ERR_UNSUPPORTED;
-    const size_t lds_pipe = (size_t)2 * img_rows * (Kp + 4) * sizeof(float);
-    const bool piped = pcops_get_option(PCOPS_OPT_POOL_TOP_ROWS_PIPELINED) != 0;
-    const int rc = pcops_dispatch<64, 128>(Kp, PCOPS_ERR_UNSUPPORTED, [&](auto kp_) {
-        constexpr int KP = decltype(kp_)::value;
-        auto kern = !piped ? pool_top_wsparse_rows_kernel<KP>
-                  : S <= 64 ? pool_top_wsparse_rows_pipe_kernel<KP, KP / 16> : pool_top_wsparse_rows_pipe_kernel<KP, KP / 8>;
-        return pcops_launch_lds(kern, dim3(grid), dim3(256), piped ? lds_pipe : lds, 160 * 1024, st, G, N, S, gout, ysel, argmax,
-                                pool_scale, pool_shift, p, Yprev, prev_scale, prev_shift, rows->block_start, partial, part2);
-    });
-    if (rc) return rc;
-    const long long L = (long long)Kp * N;
-    hipLaunchKernelGGL(sum_partials2_kernel, dim3(cdiv(L, 64) + cdiv(N, 64)), dim3(1024), 0, st, grid, L, partial, Ssp,
-                       (long long)N, part2, cfsum);
-    return pcops_launch_status();
 }
 
 int pcops_mlp_gemm_dgrad_top_rows(int M, int Kp, const float *Yprev, const float *prev_scale, const float *prev_shift,
@@ -6886,82 +5225,6 @@ int pcops_mlp_gram_rows(long long M, int Kp, const float *Yprev, int ldx, const 
     return gram_finish(g, gg, gram, xsum, st);
 }
 
-int pcops_mlp_dy_apply(long long M, int N, const float *G, const float *Y, const float *p, const float *q, const float *t,
-                       float *out, pcops_stream_t stream) {
-    PCOPS_REQUIRE_SHAPE(M >= 0 && N >= 4 && N % 4 == 0);
-    if (M == 0) return PCOPS_OK;
-    PCOPS_REQUIRE_PTR(G); PCOPS_REQUIRE_PTR(Y); PCOPS_REQUIRE_PTR(p); PCOPS_REQUIRE_PTR(q); PCOPS_REQUIRE_PTR(t); PCOPS_REQUIRE_PTR(out);
-    PCOPS_REQUIRE_ARG(((uintptr_t)G | (uintptr_t)Y | (uintptr_t)p | (uintptr_t)q | (uintptr_t)t | (uintptr_t)out) % 16 == 0);
-    const long long total4 = M * (N / 4);
-    const unsigned grid = (unsigned)(cdiv(total4, 256) < 8192 ? cdiv(total4, 256) : 8192);
-    hipLaunchKernelGGL(dy_apply_kernel, dim3(grid), dim3(256), 0, as_stream(stream), total4, N / 4,
-                       reinterpret_cast<const float4 *>(G), reinterpret_cast<const float4 *>(Y),
-                       reinterpret_cast<const float4 *>(p), reinterpret_cast<const float4 *>(q),
-                       reinterpret_cast<const float4 *>(t), reinterpret_cast<float4 *>(out));
-    return pcops_launch_status();
-}
-
-int pcops_mlp_pool_top_prep(int Kp, int N, const float *W, const float *b, const float *q, const float *t, float *Wt,
-                            float *Wq, float *u, float *v, pcops_stream_t stream) {
-    PCOPS_REQUIRE_SHAPE(Kp >= 1 && N >= 1);
-    PCOPS_REQUIRE_PTR(W); PCOPS_REQUIRE_PTR(b); PCOPS_REQUIRE_PTR(q); PCOPS_REQUIRE_PTR(t);
-    PCOPS_REQUIRE_PTR(Wt); PCOPS_REQUIRE_PTR(Wq); PCOPS_REQUIRE_PTR(u);
-    const int gx = (N + 31) / 32;
-    hipLaunchKernelGGL(pool_top_prep_kernel, dim3(gx, (Kp + 31) / 32 + (v ? ((Kp + 7) / 8 + gx - 1) / gx : 0)), dim3(256), 0,
-                       as_stream(stream), Kp, N, W, b, q, t, Wt, Wq, u, v);
-    return pcops_launch_status();
-}
-
-int pcops_mlp_pool_top_finish(int Kp, int N, long long M, float *dW, const float *Ssp, const float *xsum, const float *u,
-                              const float *cfsum, const float *q, const float *W, const float *b, const float *t,
-                              float *db, pcops_stream_t stream) {
-    PCOPS_REQUIRE_SHAPE(Kp >= 1 && N >= 1 && M >= 1);
-    PCOPS_REQUIRE_PTR(dW); PCOPS_REQUIRE_PTR(Ssp); PCOPS_REQUIRE_PTR(xsum); PCOPS_REQUIRE_PTR(u); PCOPS_REQUIRE_PTR(cfsum);
-    PCOPS_REQUIRE_PTR(q); PCOPS_REQUIRE_PTR(W); PCOPS_REQUIRE_PTR(b); PCOPS_REQUIRE_PTR(t); PCOPS_REQUIRE_PTR(db);
-    hipLaunchKernelGGL(pool_top_finish_kernel, dim3((N + 255) / 256, 8 + (Kp + 7) / 8), dim3(256), 0, as_stream(stream), Kp, N,
-                       (float)M, dW, Ssp, xsum, u, cfsum, q, W, b, t, db);
-    return pcops_launch_status();
-}
-
-int pcops_small_gemm(int M, int K, int N, const float *A, int lda, const float *B, int ldb, float *C, int ldc,
-                     pcops_stream_t stream) {
-    return pcops_small_gemm_ex(M, K, N, A, lda, 0, B, ldb, 0, nullptr, C, ldc, stream);
-}
-
-int pcops_small_gemm_ex(int M, int K, int N, const float *A, int lda, int transA, const float *B, int ldb, int transB,
-                        const float *bias, float *C, int ldc, pcops_stream_t stream) {
-    return pcops_small_gemm_colsum(M, K, N, A, lda, transA, B, ldb, transB, bias, C, ldc, nullptr, stream);
-}
-
-int pcops_small_gemm_colsum(int M, int K, int N, const float *A, int lda, int transA, const float *B, int ldb, int transB,
-                            const float *bias, float *C, int ldc, float *colsum, pcops_stream_t stream) {
-    PCOPS_REQUIRE_SHAPE(M >= 1 && K >= 1 && N >= 1 && lda >= (transA ? M : K) && ldb >= (transB ? K : N) && ldc >= N);
-    PCOPS_REQUIRE_PTR(A); PCOPS_REQUIRE_PTR(B); PCOPS_REQUIRE_PTR(C);
-    pcops_note_pipe(0);                                     // fp32 MFMA (bench labels read pcops_last_launch_pipe per launch)
-    hipLaunchKernelGGL(small_gemm_kernel, dim3((N + 31) / 32, (M + 31) / 32), dim3(256), 0, as_stream(stream), M, K, N, A,
-                       lda, B, ldb, C, ldc, transA ? 1 : 0, transB ? 1 : 0, bias, colsum);
-    return pcops_launch_status();
-}
-
-int pcops_small_gemm_pair(const pcops_gemm_problem_t *p, pcops_stream_t stream) {
-    PCOPS_REQUIRE_PTR(p);
-    SgProblem q[2];
-    int tiles[2], gx[2];
-    for (int i = 0; i < 2; ++i) {
-        const pcops_gemm_problem_t &a = p[i];
-        PCOPS_REQUIRE_SHAPE(a.M >= 1 && a.K >= 1 && a.N >= 1 && a.lda >= (a.transA ? a.M : a.K) && a.ldb >= (a.transB ? a.K : a.N) &&
-                            a.ldc >= a.N);
-        PCOPS_REQUIRE_PTR(a.A); PCOPS_REQUIRE_PTR(a.B); PCOPS_REQUIRE_PTR(a.C);
-        q[i] = SgProblem{a.M, a.K, a.N, a.lda, a.ldb, a.ldc, a.transA ? 1 : 0, a.transB ? 1 : 0, a.A, a.B, a.bias, a.C, a.colsum};
-        gx[i] = (a.N + 31) / 32;
-        tiles[i] = gx[i] * ((a.M + 31) / 32);
-    }
-    pcops_note_pipe(0);
-    hipLaunchKernelGGL(small_gemm_pair_kernel, dim3(tiles[0] + tiles[1]), dim3(256), 0, as_stream(stream), q[0], q[1], tiles[0],
-                       gx[0], gx[1]);
-    return pcops_launch_status();
-}
-
 #ifdef PCOPS_PHASE_PROF
 /* tools only: out[0..5] = summed shader cycles (stage, MFMA loop, epilogue, whole kernel), tiles, waves; then cleared */
 int pcops_debug_phase_prof(unsigned long long *out) {
@@ -6972,14 +5235,6 @@ int pcops_debug_phase_prof(unsigned long long *out) {
     return PCOPS_OK;
 }
 #endif
-
-int pcops_mlp_transpose(int K, int N, const float *W, float *Wt, pcops_stream_t stream) {
-    PCOPS_REQUIRE_SHAPE(K >= 1 && N >= 1);
-    PCOPS_REQUIRE_PTR(W); PCOPS_REQUIRE_PTR(Wt);
-    hipLaunchKernelGGL(transpose_kernel, dim3((N + 31) / 32, (K + 31) / 32), dim3(256), 0, as_stream(stream), K, N,
-                       W, Wt);
-    return pcops_launch_status();
-}
 
 }  // extern "C"
 #endif  // PCOPS_PART(0)

@@ -1,5 +1,6 @@
 """float64 restatement of pcops_mlp_dgrad_top_groups / pcops_mlp_wgrad_top_groups (pcops.h) from their arguments, and of
-the small operands around them (pcops_mlp_pool_top_prep / _finish, the two K-sized products), in plain torch."""
+the small operands around them (pcops_mlp_pool_top_prep / _finish of csrc/pooltop_sparse.hip, the two K-sized products of
+csrc/small_gemm.hip), in plain torch."""
 import torch
 
 

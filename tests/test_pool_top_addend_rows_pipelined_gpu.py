@@ -1,4 +1,4 @@
-"""pcops_mlp_pool_top_addend_rows under PCOPS_OPT_POOL_TOP_ROWS_PIPELINED = 1 (mlp.hip pool_top_addend_rows_pipe_kernel: a
+"""pcops_mlp_pool_top_addend_rows under PCOPS_OPT_POOL_TOP_ROWS_PIPELINED = 1 (pooltop_sparse.hip pool_top_addend_rows_pipe_kernel: a
 wave per group, the row's hits as ballots, the next row's W^T reads in flight) against the kernel it replaces (option 0)
 and against float64 (2e-5 of the largest element, the bound of that file's _close), on the row sets and pool inputs of test_pool_top_rows_gpu.py.
 

@@ -1,6 +1,7 @@
 """The algebraic backward of a pooled top layer over COMPACTED rows (pcops.h: pcops_mlp_gram_rows,
 pcops_mlp_gemm_dgrad_top_rows, pcops_mlp_pool_top_addend_rows, pcops_mlp_pool_top_wsparse_rows, and
-pcops_mlp_gemm_fwd_pool_rows without the Y store).
+pcops_mlp_gemm_fwd_pool_rows without the Y store; the products in csrc/mlp.hip, the two sparse halves in
+csrc/pooltop_sparse.hip).
 
 Every entry point against a float64 restatement on row sets built by pcops_rows_plan from hand-made pts_cnt, to a
 relative error of 2e-5 of the largest element (the bound test_bwd_fused_gpu.py holds the split-operand products to);

@@ -1,5 +1,5 @@
 """pcops_mlp_gram_rows on the bf16 matrix pipe with split operands (PCOPS_OPT_GRAM_SPLIT_BF16, mlp.hip gram_rows_bf3_kernel)
-and the software-pipelined pcops_mlp_pool_top_wsparse_rows (PCOPS_OPT_POOL_TOP_ROWS_PIPELINED, pool_top_wsparse_rows_pipe_kernel)
+and the software-pipelined pcops_mlp_pool_top_wsparse_rows (PCOPS_OPT_POOL_TOP_ROWS_PIPELINED, pooltop_sparse.hip pool_top_wsparse_rows_pipe_kernel)
 against float64 and against the kernels they replace, on the row sets of test_pool_top_rows_gpu.py (hand-made member
 counts 1, 15, 16, 17, S - 1, S; the all-zero, the one-live-channel and the everything-on-the-weighted-row group), then
 the SA2-shaped stack of that file with both options on against both off.

@@ -1,5 +1,5 @@
-"""Which part of the one-pass backward sets its time?  Needs the -DPCOPS_BF_DEBUG build of mlp.hip's parts 0 and 5
-(scanobjectnn_amd/libpcops_bfdbg.so): PCOPS_BF_DEBUG = bit mask  1: no dX matrix instructions, 2: no epilogue (mask, column sums,
+"""Which part of the one-pass backward sets its time?  Needs the -DPCOPS_BF_DEBUG build of mlp.hip's part 5 (bwd_fused_kernel and its
+launcher; tools/build_variant.sh bfdbg "-DPCOPS_BF_DEBUG" builds scanobjectnn_amd/libpcops_bfdbg.so): PCOPS_BF_DEBUG = bit mask  1: no dX matrix instructions, 2: no epilogue (mask, column sums,
 Gprev stores), 4: no dW matrix instructions, 8: producers do not stage, 16: producers do not load.  SA1's pooled layer, plain form
 (default) or, with `xyz`, SA1's 64 -> 64 layer above the arithmetic first layer (dense upstream gradient).
     PCOPS_LIB=$PWD/scanobjectnn_amd/libpcops_bfdbg.so python tools/ablate_bwd_fused.py [xyz]"""

@@ -1,4 +1,5 @@
-"""reads gfx950 assembly of mlp.hip parts (hipcc -S --cuda-device-only) and reports, per gemm_ws / bwd_fused / wgrad kernel:
+"""reads gfx950 assembly of mlp.hip parts (hipcc -S --cuda-device-only -DPCOPS_MLP_PART=1..6: the matrix products; kernels without
+matrix instructions, such as those of mlp_bn.hip and pooltop_sparse.hip, are skipped) and reports, per gemm_ws / bwd_fused / wgrad kernel:
    * scratch loads / stores that sit inside a loop (a scratch reload is a vector-memory load: the first use of the reloaded
      register waits on vmcnt, and behind a prefetch that means waiting for the prefetch),
    * `s_waitcnt vmcnt(0)` between a group of prefetch loads (buffer_load_dwordx4) and the next matrix instruction.

@@ -2,6 +2,8 @@
 visible through the branch targets: how many MFMA / VALU / SALU / LDS / VMEM instructions a block issues.
     hipcc --offload-arch=gfx950 -O3 ... -S --cuda-device-only -o /tmp/mlp.s scanobjectnn_amd/csrc/mlp.hip
     python tools/isa_stats.py /tmp/mlp.s 'gemm_ws_kernelILi4ELi1ELi0ELi64ELi8ELi2ELi1E'
+(mlp.hip: the matrix-product kernels; the statistics / pooling / elementwise kernels list from mlp_bn.hip, the sparse halves of
+the pooled top layer from pooltop_sparse.hip, the small products from small_gemm.hip)
 """
 import re
 import sys

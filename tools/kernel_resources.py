@@ -3,6 +3,8 @@ occupancy).  Usage:
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -Rpass-analysis=kernel-resource-usage \\
           -c scanobjectnn_amd/csrc/mlp.hip -o /tmp/x.o 2> /tmp/res.txt
     python tools/kernel_resources.py /tmp/res.txt [filter]
+mlp.hip without -DPCOPS_MLP_PART is every matrix-product kernel in one translation unit; the kernels around the products are
+in mlp_bn.hip, pooltop_sparse.hip and small_gemm.hip next to it.
 """
 import re
 import subprocess

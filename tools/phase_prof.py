@@ -1,5 +1,10 @@
 """Where does a wave of gemm_ws_kernel spend its cycles?  Needs a -DPCOPS_PHASE_PROF build of the library:
-    hipcc ... -DPCOPS_PHASE_PROF -c mlp.hip -o /tmp/mlp_prof.o ; link as scanobjectnn_amd/libpcops_prof.so
+mlp.hip as ONE translation unit (no part macro: the counters are one device variable) next to every other object of the Makefile,
+    cd scanobjectnn_amd/csrc && make -j8
+    hipcc <the Makefile's CXXFLAGS> -DPCOPS_PHASE_PROF -c mlp.hip -o /tmp/mlp_prof.o
+    hipcc --offload-arch=gfx950 -shared -fPIC -o ../libpcops_prof.so /tmp/mlp_prof.o $(ls *.o | grep -v '^mlp_p[0-6]\.o$')
+(the objects linked are abi.o ... feed.o and mlp_bn.o, pooltop_sparse.o, small_gemm.o: without the last three the library lacks
+the statistics, pooling and small-product entry points this script calls)
     PCOPS_LIB=scanobjectnn_amd/libpcops_prof.so python tools/phase_prof.py
 Per launch: shader cycles per 32-row tile and wave in the three phases (operand staging, MFMA loop, epilogue), next to
 the cycles the tile's MFMAs occupy the matrix pipe (64 per v_mfma_f32_32x32x2_f32) -- with two waves per SIMD a wave's

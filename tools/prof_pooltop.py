@@ -1,6 +1,6 @@
 """Per-call HIP-event timings of the algebraic top-layer backward (fused_mlp._pool_top_backward) against the plain
-dgrad + wgrad it replaces, at the benchmark shapes; then SA2's compacted case: pcops_mlp_gram_rows,
-pcops_mlp_pool_top_wsparse_rows and pcops_mlp_pool_top_addend_rows alone, HIP events around the entry point, under both
+dgrad + wgrad it replaces, at the benchmark shapes; then SA2's compacted case: pcops_mlp_gram_rows (csrc/mlp.hip),
+pcops_mlp_pool_top_wsparse_rows and pcops_mlp_pool_top_addend_rows (csrc/pooltop_sparse.hip) alone, HIP events around the entry point, under both
 values of PCOPS_OPT_GRAM_SPLIT_BF16 / PCOPS_OPT_POOL_TOP_ROWS_PIPELINED (DESIGN.md sections 4.21, 4.23).
 python tools/prof_pooltop.py [--rows-only]"""
 import collections
